@@ -8,12 +8,19 @@ bf16 compute with fp32 master weights/BN statistics, SGD+momentum (fused HIP
 kernel), data parallel with bucketed RCCL all-reduce overlapped with
 backward. Per-GPU batch (default 3072, 113 GB of the 288 GB HBM) is fixed as N grows (weak scaling).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line; ``value`` is the whole-job images/sec computed
 from the MAX per-rank wall time over exactly K timed steps bracketed by a
 barrier + device synchronize on both sides.
+
+A plain run sets up, warms up, times the K steps and prints the line. The
+data-parallel checks (step-0 transport self-check, identical replicas) and the
+exposed-communication time belong to a live gradient transport (N > 1 or
+``--force-dist``) and always run with one; ``--full`` runs and reports them
+without one as well. ``--dump-outputs DIR`` writes what the last timed step
+computed (loss, logits, updated weights) as ``DIR/<name>.npy``.
 """
 from __future__ import annotations
 
@@ -64,7 +71,35 @@ def parse(argv=None):
     ap.add_argument("--profile-steps", type=int, default=0, help="(internal) roctx-free short run")
     ap.add_argument("--force-dist", action="store_true",
                     help="create the process group and run the gradient transport even at world 1 (RCCL on one GPU)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's loss, logits and updated weights as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the data-parallel checks and the exposed-communication measurement when no gradient "
+                         "transport is live (with one they always run)")
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_MAX_ELEMS = {"logits": 8 << 20, "weights": 4 << 20}  # float32: 32 MB + 16 MB, under 64 MB with the loss
+
+
+def _dump_outputs(path, loss, logits, store):
+    """The arrays a caller of the timed step receives, from its last run: the loss, the logits and the updated fp32
+    master weights, as float32 ``<name>.npy``. An array over its element budget is written as a fixed, seeded sample
+    of its flattened elements (same positions in every run), which keeps the whole dump under 64 MB."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1), "logits": logits.detach(), "weights": store.master.detach()}
+    for name, t in arrays.items():
+        limit = DUMP_MAX_ELEMS.get(name)
+        if limit is not None and t.numel() > limit:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (limit,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def _launch_local_ranks(a, argv) -> int:
@@ -160,10 +195,13 @@ def main(argv=None):
     # what the collectives actually ran on, read from the process group after its first collective (the broadcast
     # above): the driver's multi-GPU record must show by itself that RCCL initialised with every rank
     comm = _comm_record(n, dev)
+    # the data-parallel checks and the exposed-communication time say something only about a live gradient
+    # transport: a plain one-GPU run leaves them out, --full asks for them regardless
+    extras = a.full or n > 1 or a.force_dist
     # step-0 transport self-check (untimed): one gradient bucket through the configured transport vs a plain fp32
     # all_reduce of the same data; a mismatch beyond the transport's rounding fails the run before any number
-    check = reducer.self_check()
-    if not check["ok"]:
+    check = reducer.self_check() if extras else None
+    if check is not None and not check["ok"]:
         if info.rank == 0:
             print("error: gradient transport self-check failed: %s" % json.dumps(check), file=sys.stderr)
         kdist.destroy()
@@ -184,23 +222,23 @@ def main(argv=None):
         logits = model(x)
         loss = K.cross_entropy(logits, labels)
         loss.backward()
-        if timed and dev.type == "cuda":
+        if not (timed and extras):
+            reducer.finish()
+        elif dev.type == "cuda":
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             reducer.finish()
             e1.record()
             marks.append((e0, e1))
-        elif timed:
+        else:
             t = time.perf_counter()
             reducer.finish()
             marks.append(time.perf_counter() - t)
-        else:
-            reducer.finish()
         opt.step(grad_scale=reducer.grad_scale)
-        return loss
+        return loss, logits
 
     for i in range(a.warmup):
-        loss = step()
+        step()
         if info.rank == 0:  # progress on stderr (the first step JIT-loads kernels)
             print("warmup step %d/%d issued" % (i + 1, a.warmup), file=sys.stderr, flush=True)
     sync = torch.cuda.synchronize if dev.type == "cuda" else (lambda: None)
@@ -209,22 +247,27 @@ def main(argv=None):
     sync()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        loss = step(timed=True)
+        loss, logits = step(timed=True)
     sync()
     kdist.barrier()
     sync()
     dt = time.perf_counter() - t0
     dt_max = kdist.all_reduce_max(dt, dev)
-    if dev.type == "cuda":
-        exposed = [e0.elapsed_time(e1) for e0, e1 in marks]
-    else:
-        exposed = [1000.0 * t for t in marks]
-    exposed_ms = kdist.all_reduce_max(sum(exposed) / max(1, len(exposed)), dev)
     final_loss = float(loss.detach().float().item())
-    # data-parallel sanity (outside the timed region): every replica must hold the same weights
-    csum = float(store.master.double().sum().item())
-    identical = kdist.all_reduce_max(csum, dev) == -kdist.all_reduce_max(-csum, dev)
+    more = {}
+    if extras:
+        if dev.type == "cuda":
+            exposed = [e0.elapsed_time(e1) for e0, e1 in marks]
+        else:
+            exposed = [1000.0 * t for t in marks]
+        exposed_ms = kdist.all_reduce_max(sum(exposed) / max(1, len(exposed)), dev)
+        # data-parallel sanity (outside the timed region): every replica must hold the same weights
+        csum = float(store.master.double().sum().item())
+        identical = kdist.all_reduce_max(csum, dev) == -kdist.all_reduce_max(-csum, dev)
+        more = {"replicas_identical": identical, "comm_exposed_ms": round(exposed_ms, 3), "transport_check": check}
     ips = n * a.batch * a.steps / dt_max
+    if a.dump_outputs and info.rank == 0:  # rank 0's loss and logits; the weights are the same on every rank
+        _dump_outputs(a.dump_outputs, loss, logits, store)
     if info.rank == 0:
         out = {
             "metric": "images/sec ResNet-50 TfJob (train, synthetic ImageNet)",
@@ -250,10 +293,8 @@ def main(argv=None):
                 "bucket_mb": a.bucket_mb,
             },
             "final_loss": round(final_loss, 4),
-            "replicas_identical": identical,
-            "comm_exposed_ms": round(exposed_ms, 3),
+            **more,
             "comm": comm,
-            "transport_check": check,
             "grad_comm_fallbacks": dict(reducer.fallbacks),
             "peak_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1) if dev.type == "cuda" else None,
         }

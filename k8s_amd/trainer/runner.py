@@ -370,6 +370,7 @@ def train(a) -> int:
         metrics.event(event="transport_check", **check)
         if not check["ok"]:
             metrics.event(event="error", error="gradient transport self-check failed")
+            kdist.destroy()  # a live group at interpreter exit can abort the process and lose the exit code
             return EXIT_PERMANENT
 
     def save(step):
@@ -469,6 +470,7 @@ def train(a) -> int:
                     bad = bool(flag.item() > 0)
                 if bad:
                     metrics.event(event="error", step=step, error="non-finite loss")
+                    kdist.destroy()
                     return EXIT_PERMANENT
                 sync()
                 now = time.time()

@@ -104,6 +104,34 @@ def test_bench_world_mismatch_fails_closed():
     assert "world size 1" in r.stderr
 
 
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain one-rank run reports the headline fields only (the data-parallel checks need ``--full`` or a live
+    transport), times exactly ``--steps`` steps, and ``--dump-outputs`` writes the last step's loss, logits and
+    weights as float32 ``.npy`` files that a second run with the same arguments reproduces."""
+    import numpy as np
+
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--image", "32"]
+    dumps = []
+    for name in ("a", "b"):
+        (r,) = _run("bench.py", args + ["--dump-outputs", str(tmp_path / name)], launcher=False)
+        assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["unit"] == "images/s" and r["dtype"] == "fp32"
+        assert abs(r["value"] - 2 / (r["ms_per_step"] / 1000.0)) / r["value"] < 0.02
+        for k in ("replicas_identical", "comm_exposed_ms", "transport_check"):
+            assert k not in r, k
+        assert sorted(os.listdir(tmp_path / name)) == ["logits.npy", "loss.npy", "weights.npy"]
+        dumps.append({f: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)})
+    a, b = dumps
+    assert a["logits.npy"].shape == (2, 1000) and a["loss.npy"].shape == (1,)
+    assert abs(float(a["loss.npy"][0]) - r["final_loss"]) < 1e-3
+    for f in a:
+        assert a[f].dtype == np.float32 and np.isfinite(a[f]).all()
+        assert np.array_equal(a[f], b[f]), f
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+
+    (r,) = _run("bench.py", args + ["--full"], launcher=False)
+    assert r["replicas_identical"] is True and r["comm_exposed_ms"] >= 0 and r["transport_check"]["ok"] is True
+
+
 def test_collectives_bench_busbw():
     recs = _run("benchmarks/collectives.py", ["--device", "cpu", "--sizes-mb", "0.25", "--iters", "2",
                                               "--warmup", "1"])
