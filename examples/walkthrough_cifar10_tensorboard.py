@@ -10,11 +10,12 @@ it is Done. This is the same flow on one box, with every piece real:
    download here) whose ``tensorboard.logDir`` is where the trainer writes ``events.out.tfevents.*``;
 3. the operator's TensorBoard Deployment + Service (port 80 -> 6006), served on this box by
    ``k8s_amd.tools.tensorboard`` (TensorBoard's scalar REST API over the same event files);
-4. the job polled to ``phase: Done``, then the loss curve read back through TensorBoard's HTTP API.
+4. the job polled to ``phase: Done``, then the loss curve and the evaluation accuracy (``eval/top1``, from the
+   trainer's ``--eval-every``) read back through TensorBoard's HTTP API.
 
     python examples/walkthrough_cifar10_tensorboard.py [--steps 100] [--gpus 0]
 
-Prints a JSON summary (job state, TensorBoard URL, runs/tags, the loss series) and exits 0 on success.
+Prints a JSON summary (job state, TensorBoard URL, runs/tags, the loss and eval/top1 series) and exits 0 on success.
 """
 from __future__ import annotations
 
@@ -24,6 +25,7 @@ import os
 import sys
 import tempfile
 import time
+import urllib.parse
 import urllib.request
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -33,7 +35,10 @@ from k8s_amd.fakeapi.cluster import LocalCluster  # noqa: E402
 
 def manifest(name: str, logdir: str, steps: int, gpu: bool) -> dict:
     container = {"name": "tensorflow", "image": "k8s-amd/trainer:rocm7-gfx950",
-                 "args": ["--model", "resnet_tiny", "--steps", str(steps), "--log-every", "5", "--logdir", logdir],
+                 "args": ["--model", "resnet_tiny", "--steps", str(steps), "--log-every", "5", "--logdir", logdir,
+                          # accuracy on the (fixed, synthetic) training batch every 10 steps and after the last one:
+                          # the eval/loss, eval/top1 and eval/top5 series next to the loss curve
+                          "--eval-every", "10", "--eval-data", "train"],
                  "volumeMounts": [{"name": "logs", "mountPath": logdir}]}
     if gpu:
         container["resources"] = {"limits": {"amd.com/gpu": 1}}
@@ -96,11 +101,14 @@ def run(steps: int = 100, gpus=None, job: str = "cifar10-resnet", logdir: str = 
         tags = _get_json(tb + "/data/plugin/scalars/tags")
         run_name = runs[0] if runs else "."
         loss = _get_json(tb + "/data/plugin/scalars/scalars?run=%s&tag=loss" % run_name) if runs else []
+        top1 = _get_json(tb + "/data/plugin/scalars/scalars?run=%s&tag=%s"
+                         % (run_name, urllib.parse.quote("eval/top1", safe=""))) if runs else []
         index = urllib.request.urlopen(tb + "/", timeout=5).read().decode()
     out = {"job": job, "phase": status.get("phase"), "state": status.get("state"), "tensorboard": tb,
            "logdir": logdir, "runs": runs, "tags": {r: sorted(t) for r, t in tags.items()},
            "loss_points": len(loss), "loss_first": loss[0][2] if loss else None,
-           "loss_last": loss[-1][2] if loss else None, "loss_steps": [p[1] for p in loss]}
+           "loss_last": loss[-1][2] if loss else None, "loss_steps": [p[1] for p in loss],
+           "eval_top1": [[p[1], p[2]] for p in top1]}
     say(index.strip())
     return out
 

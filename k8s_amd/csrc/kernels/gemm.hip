@@ -373,8 +373,12 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 // its LDS slot by ds_write instead of by LDS-DMA (same lane-linear image, same swizzle). The staging registers of
 // the next K step are filled behind this step's MFMAs and written after them, before the step's barrier.
 // BST (lean only): the BatchNorm-backward sums epilogue of a data gradient (Epi::bb) instead of the statistics.
+// IEPI (lean only, XF == 0): the inference epilogue of a convolution followed by a folded BatchNorm -- a per-column
+// fp32 affine (scale = XForm::p, shift = Epi::bias, both [N]) in the register pass, one rounding into the staged
+// tile; the copy-out adds an optional bf16 residual (Epi::addsrc, the output's layout, ldc == N) and applies the
+// ReLU (Epi::act). Identity rows, plain stores, no statistics; its own instantiation, as XEPI.
 template <class ASrc, class BSrc, int NBUF, int WM = 2, int WN = 2, bool LEAN = false, bool XEPI = false,
-          bool F32S = false, int XF = 0, bool BST = false>
+          bool F32S = false, int XF = 0, bool BST = false, bool IEPI = false>
 __global__ void __launch_bounds__(GEMM_THREADS, (NBUF == 1 && (XF == 0 || (XF == 1 && WM == 2))) ? 3 : 2)
 gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XForm X) {
   constexpr int BM = 64 * WM, BN = 64 * WN;
@@ -382,6 +386,7 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
   static_assert(WM * WN == 4, "4 waves");
   static_assert((WM == 2 || ASrc::kmajor) && (WN == 2 || BSrc::kmajor), "MN-major operands need a 128 side");
   static_assert(BM * BN * 2 <= TA + TB, "the C tile fits one operand buffer");
+  static_assert(!IEPI || (LEAN && !XEPI && !BST && XF == 0), "the inference epilogue is a plain lean instantiation");
   __shared__ __attribute__((aligned(1024))) char smem[NBUF * (TA + TB)];  // [buf][A|B]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
@@ -608,15 +613,27 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
     }
     // bias (fp32, added before the one bf16 rounding of the staged value): this lane's 4 columns of each j
     float bj[4][4];
+    float sj[IEPI ? 4 : 1][4];  // IEPI: the columns' scale (bj holds their shift)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int n = n0 + wn * 64 + j * 16 + (lane >> 4) * 4;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) bj[j][r] = (XEPI && E.bias && n + r < N) ? E.bias[n + r] : 0.f;
+      for (int r = 0; r < 4; ++r) bj[j][r] = ((XEPI || IEPI) && E.bias && n + r < N) ? E.bias[n + r] : 0.f;
+      if constexpr (IEPI) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sj[j][r] = n + r < N ? X.p[n + r] : 0.f;
+      }
     }
     // alpha is 1 for every convolution and data gradient: the scaling pass runs only when it is not (one
     // wave-uniform branch instead of 64 multiplies per lane on every tile)
-    if (XEPI || E.alpha != 1.f) {
+    if constexpr (IEPI) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc[i][j][r] = __builtin_fmaf(acc[i][j][r], sj[j][r], bj[j][r]);
+    } else if (XEPI || E.alpha != 1.f) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -637,6 +654,43 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
       }
     }
     __syncthreads();
+    if constexpr (IEPI) {
+      // inference copy-out (identity rows, ldc == N): thread t owns 16-B chunk c = t % CPR of rows row0 + i RSTEP;
+      // the residual walks with the output, one 16-B load per stored chunk, added before the ReLU
+      constexpr int RSTEP = GEMM_THREADS / CPR;
+      const int c = tid % CPR, row0 = tid / CPR;
+      const int n = n0 + c * 8;
+      if (n < N) {
+        const long ldc = E.ldc;
+        const long off0 = (long)(m0 + row0) * ldc + n;
+        uint16_t* cp = reinterpret_cast<uint16_t*>(E.c) + off0;
+        const uint16_t* rp = E.addsrc ? E.addsrc + off0 : nullptr;
+        const uint16_t* lp = ctile + row0 * BN;
+        const bool relu = E.act != 0;
+#pragma unroll 4
+        for (int row = row0; row < BM; row += RSTEP) {
+          if (m0 + row < M) {
+            bf16x8_t o = *reinterpret_cast<const bf16x8_t*>(lp + ((c ^ (row % CPR)) << 3));
+            if (rp || relu) {
+              bf16x8_t rv = bf16x8_t{0, 0, 0, 0, 0, 0, 0, 0};
+              if (rp) rv = *reinterpret_cast<const bf16x8_t*>(rp);
+              float f[8];
+#pragma unroll
+              for (int r = 0; r < 8; ++r) {
+                const float v = bf2f((uint16_t)o[r]) + bf2f((uint16_t)rv[r]);
+                f[r] = relu ? fmaxf(v, 0.f) : v;
+              }
+              o = pack_bf16x8(f);
+            }
+            *reinterpret_cast<bf16x8_t*>(cp) = o;
+          }
+          cp += (long)RSTEP * ldc;
+          lp += RSTEP * BN;
+          if (rp) rp += (long)RSTEP * ldc;
+        }
+      }
+      return;
+    }
     // copy-out: thread t always handles 16-B chunk c = t % CPR of its rows (GEMM_THREADS % CPR == 0), so it
     // also accumulates the BN statistics (sum, sum of squares) of those 8 columns from the bf16 values it stores
     float* const stat_out = BST ? E.bb.sums : E.stats;
@@ -1070,15 +1124,15 @@ static int effective_splits(int K, int splits) {
 }
 
 template <class ASrc, class BSrc, int WM, int WN, bool LEAN, bool XEPI = false, bool F32S = false, int XF = 0,
-          bool BST = false>
+          bool BST = false, bool IEPI = false>
 static void launch_tiles2(const ASrc& a, const BSrc& b, const Epi& e, int M, int N, int K, int kps, int splits,
                           hipStream_t st, const XForm& x = XForm{nullptr, 0, FastDiv{}}) {
   const int tiles = ((M + 64 * WM - 1) / (64 * WM)) * ((N + 64 * WN - 1) / (64 * WN));
   if (kps <= single_buf_maxk())
-    hipLaunchKernelGGL((gemm_bf16_kernel<ASrc, BSrc, 1, WM, WN, LEAN, XEPI, F32S, XF, BST>), dim3(tiles, 1, splits),
+    hipLaunchKernelGGL((gemm_bf16_kernel<ASrc, BSrc, 1, WM, WN, LEAN, XEPI, F32S, XF, BST, IEPI>), dim3(tiles, 1, splits),
                        dim3(GEMM_THREADS), 0, st, a, b, e, M, N, K, kps, x);
   else
-    hipLaunchKernelGGL((gemm_bf16_kernel<ASrc, BSrc, 2, WM, WN, LEAN, XEPI, F32S, XF, BST>), dim3(tiles, 1, splits),
+    hipLaunchKernelGGL((gemm_bf16_kernel<ASrc, BSrc, 2, WM, WN, LEAN, XEPI, F32S, XF, BST, IEPI>), dim3(tiles, 1, splits),
                        dim3(GEMM_THREADS), 0, st, a, b, e, M, N, K, kps, x);
 }
 
@@ -1382,6 +1436,47 @@ void launch_conv_fwd(const uint16_t* x, const uint16_t* w, void* y, bool y_f32, 
     ConvAG a{x, N, H, W, C, Ho, Wo, S, stride, pad, dil, M, RSC,
              make_fastdiv(C), make_fastdiv(S), make_fastdiv(Ho * Wo), make_fastdiv(Wo)};
     launch(a, b, e, M, K, RSC, 1, st);
+  }
+}
+
+// Inference convolution with the following BatchNorm folded to a per-channel affine, an optional residual and ReLU
+// (the IEPI epilogue): y = act(bf16(conv(x, w) * scale + shift) + res). Every shape runs on the tile kernel: the
+// K-major source for a plain 1x1, the per-tile im2col for C % 64 == 0, the per-unit one for any other C % 8 == 0.
+template <class ASrc>
+static void launch_infer(const ASrc& a, const KMajor& b, const Epi& e, int M, int N, int K, const XForm& x,
+                         hipStream_t st) {
+  const int kps = (K + BK - 1) / BK * BK;
+  if (N <= 64)
+    launch_tiles2<ASrc, KMajor, 4, 1, true, false, false, 0, false, true>(a, b, e, M, N, K, kps, 1, st, x);
+  else
+    launch_tiles2<ASrc, KMajor, 2, 2, true, false, false, 0, false, true>(a, b, e, M, N, K, kps, 1, st, x);
+}
+
+void launch_conv_infer(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int C, int K, int R,
+                       int S, int stride, int pad, int Ho, int Wo, const float* scale, const float* shift,
+                       const uint16_t* res, bool relu, hipStream_t st) {
+  const long M = (long)N * Ho * Wo, RSC = (long)R * S * C;
+  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+  if (C % 8 || K % 8 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride <= 0 || pad < 0 || Ho <= 0 || Wo <= 0 ||
+      M >= (1L << 31) || RSC >= (1L << 31) || !scale || !shift || misaligned(x) || misaligned(w) || misaligned(y) ||
+      misaligned(res))
+    throw std::runtime_error("conv_infer: C % 8 == 0, K % 8 == 0, 16-B aligned x / w / y / res, fp32 scale and "
+                             "shift, fewer than 2^31 output pixels");
+  if (M == 0) return;
+  KMajor b{w, RSC, K, (int)RSC};
+  Epi e = make_epi(y, K, false, shift, relu ? 1 : 0, nullptr, 0, 1.f);
+  e.addsrc = res;
+  const XForm xs{scale, 0, FastDiv{}};
+  if (R == 1 && S == 1 && stride == 1 && pad == 0 && C % 64 == 0) {
+    launch_infer(KMajor{x, (long)C, (int)M}, b, e, (int)M, K, (int)RSC, xs, st);
+  } else if (C % 64 == 0) {
+    ConvA a{x, N, H, W, C, Ho, Wo, S, stride, pad, 1, (int)M,
+            make_fastdiv(C), make_fastdiv(S), make_fastdiv(Ho * Wo), make_fastdiv(Wo)};
+    launch_infer(a, b, e, (int)M, K, (int)RSC, xs, st);
+  } else {
+    ConvAG a{x, N, H, W, C, Ho, Wo, S, stride, pad, 1, (int)M, (int)RSC,
+             make_fastdiv(C), make_fastdiv(S), make_fastdiv(Ho * Wo), make_fastdiv(Wo)};
+    launch_infer(a, b, e, (int)M, K, (int)RSC, xs, st);
   }
 }
 

@@ -85,6 +85,9 @@ void launch_xent_fwd(const void* logits, bool bf16, const int64_t* labels, long 
 void launch_xent_bwd(const void* logits, bool bf16, const int64_t* labels, const float* lse, const float* dscale,
                      bool per_row, long R, long V, long ld, void* dlogits, long ignore_index, float smoothing,
                      hipStream_t st);
+// per-row loss and the label's rank among the first V columns (ties to the lower index; ignored rows: 0 and V)
+void launch_xent_eval(const void* logits, bool bf16, const int64_t* labels, long R, long V, long ld, float* loss,
+                      int* rank, long ignore_index, hipStream_t st);
 
 // gemm.hip
 int gemm_choose_splits(int M, int N, int K);
@@ -197,6 +200,12 @@ void launch_conv_fwd(const uint16_t* x, const uint16_t* w, void* y, bool y_f32, 
                      int R, int S, int stride, int pad, int dil, int Ho, int Wo, const float* bias, int act,
                      int mode, float* stats, hipStream_t st, const SubGrid* sg = nullptr, const float* xform = nullptr,
                      const BnBwdSums* bb = nullptr);
+// Inference convolution + folded BatchNorm (+ residual) (+ ReLU) on the tile kernel (gemm.hip IEPI):
+//   y = act(bf16(conv(x, w) * scale[k] + shift[k]) + res), scale / shift fp32 [K], res bf16 with y's layout or null.
+// C % 8 == 0, K % 8 == 0, dilation 1, 16-B aligned pointers; throws outside that contract.
+void launch_conv_infer(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int C, int K, int R,
+                       int S, int stride, int pad, int Ho, int Wo, const float* scale, const float* shift,
+                       const uint16_t* res, bool relu, hipStream_t st);
 // xform (here and in launch_gemm / launch_wgrad_stream): fp32 [2][C] BatchNorm (scale | shift): the activation
 // operand x is consumed as relu(x * scale + shift), normalised as it is loaded (gemm.hip XForm)
 void launch_conv_wgrad(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, int C, int K, int R,

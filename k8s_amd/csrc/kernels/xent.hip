@@ -78,6 +78,63 @@ __global__ void __launch_bounds__(256) xent_fwd_kernel(const T* __restrict__ log
   }
 }
 
+// Evaluation metrics of one row in the forward's single streaming pass: the cross-entropy loss and the label's rank
+//   rank = #{j : l[j] > l[y]} + #{j < y : l[j] == l[y]}      (ties go to the lower index: exact, deterministic)
+// so top-k is rank < k. l[y] is read first and the comparisons ride the sweep that keeps the online (max, sum-exp);
+// the per-thread counts take one more block reduction (as floats: exact below 2^24 columns, checked by the binding).
+// Ignored rows -- and labels outside [0, V), which are never dereferenced -- get rank V; ignored rows loss 0.
+template <typename T>
+__global__ void __launch_bounds__(256) xent_eval_kernel(const T* __restrict__ logits,
+                                                        const int64_t* __restrict__ labels, long V, long ld,
+                                                        float* __restrict__ loss, int* __restrict__ rank,
+                                                        long ignore_index) {
+  __shared__ float red[8];
+  const long row = blockIdx.x;
+  const T* x = logits + row * ld;
+  const long lab = labels[row];
+  if (lab == ignore_index || lab < 0 || lab >= V) {  // block-uniform
+    if (threadIdx.x == 0) {
+      loss[row] = lab == ignore_index ? 0.f : NAN;
+      rank[row] = (int)V;
+    }
+    return;
+  }
+  const float xl = load1<T>(x + lab);
+  float m = -INFINITY, s = 0.f, cnt = 0.f;
+  const long V8 = ((ld & 7) == 0 && (((uintptr_t)logits) & 15) == 0) ? (V / 8) * 8 : 0;
+  for (long i = threadIdx.x * 8; i < V8; i += 256 * 8) {
+    float v[8];
+    load8_any<T>(x + i, v);
+    float lm = v[0];
+#pragma unroll
+    for (int j = 1; j < 8; ++j) lm = fmaxf(lm, v[j]);
+    const float nm = fmaxf(m, lm);
+    float acc = s * __expf(m - nm);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      acc += __expf(v[j] - nm);
+      cnt += (v[j] > xl || (v[j] == xl && i + j < lab)) ? 1.f : 0.f;
+    }
+    s = acc;
+    m = nm;
+  }
+  for (long i = V8 + threadIdx.x; i < V; i += 256) {
+    const float v = load1<T>(x + i);
+    const float nm = fmaxf(m, v);
+    s = s * __expf(m - nm) + __expf(v - nm);
+    m = nm;
+    cnt += (v > xl || (v == xl && i < lab)) ? 1.f : 0.f;
+  }
+  const float gm = block_max(m, red);
+  const float sc = (m == -INFINITY) ? 0.f : s * __expf(m - gm);
+  const float gs = block_sum(sc, red);
+  const float gc = block_sum(cnt, red);
+  if (threadIdx.x == 0) {
+    loss[row] = gm + __logf(gs) - xl;
+    rank[row] = (int)gc;
+  }
+}
+
 template <typename T>
 __device__ __forceinline__ void store8_any(T* p, const float (&o)[8]);
 template <>
@@ -137,6 +194,17 @@ void launch_xent_fwd(const void* logits, bool bf16, const int64_t* labels, long 
   else
     hipLaunchKernelGGL(xent_fwd_kernel<float>, dim3(R), dim3(256), 0, st, (const float*)logits, labels, V, ld, loss,
                        lse, ignore_index, smoothing);
+}
+
+void launch_xent_eval(const void* logits, bool bf16, const int64_t* labels, long R, long V, long ld, float* loss,
+                      int* rank, long ignore_index, hipStream_t st) {
+  if (R <= 0) return;
+  if (bf16)
+    hipLaunchKernelGGL(xent_eval_kernel<uint16_t>, dim3(R), dim3(256), 0, st, (const uint16_t*)logits, labels, V, ld,
+                       loss, rank, ignore_index);
+  else
+    hipLaunchKernelGGL(xent_eval_kernel<float>, dim3(R), dim3(256), 0, st, (const float*)logits, labels, V, ld, loss,
+                       rank, ignore_index);
 }
 
 void launch_xent_bwd(const void* logits, bool bf16, const int64_t* labels, const float* lse, const float* dscale,

@@ -451,6 +451,22 @@ std::vector<Tensor> xent_fwd(Tensor logits, Tensor labels, int64_t ignore_index,
   return {loss, lse};
 }
 
+// evaluation metrics: (loss[R] fp32, rank[R] int32) over the columns of `logits` (pass a [:, :valid] view for a
+// padded vocabulary); rank = #{j : l[j] > l[y]} + #{j < y : l[j] == l[y]}, ignored rows loss 0 / rank V
+std::vector<Tensor> xent_eval(Tensor logits, Tensor labels, int64_t ignore_index) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits must be [R, V] row-major");
+  TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat);
+  check_cuda(labels, "labels"); check_dtype(labels, at::kLong, "labels");
+  const long R = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(labels.numel() == R);
+  TORCH_CHECK(V > 0 && V < (1L << 24), "xent_eval: 0 < V < 2^24 (the rank is counted in fp32)");
+  auto loss = torch::empty({R}, logits.options().dtype(at::kFloat));
+  auto rank = torch::empty({R}, logits.options().dtype(at::kInt));
+  k8s_amd::launch_xent_eval(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, labels.data_ptr<int64_t>(), R, V,
+                            logits.stride(0), f32(loss), rank.data_ptr<int>(), ignore_index, cur_stream());
+  return {loss, rank};
+}
+
 // logits [R, Vpad] dense; classes are the first V columns; returns dlogits [R, Vpad] (pad columns zero)
 Tensor xent_bwd(Tensor logits, Tensor labels, Tensor lse, Tensor dscale, int64_t ignore_index, double smoothing,
                 int64_t V) {
@@ -997,6 +1013,44 @@ Tensor conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad, int64_t dil, bo
   return y;
 }
 
+// Inference convolution with the following BatchNorm folded into the epilogue (gemm.hip IEPI):
+//   y = act(bf16(conv(x, w) * scale + shift) + res); scale / shift fp32 [K], res bf16 [N, Ho, Wo, K] or None.
+// Always the tile kernel; a shape outside its contract raises. `out`: write into this bf16 [N, Ho, Wo, K] tensor.
+Tensor conv_infer(Tensor x, Tensor w, int64_t stride, int64_t pad, Tensor scale, Tensor shift,
+                  c10::optional<Tensor> res, bool relu, c10::optional<Tensor> out) {
+  check_cuda(x, "x"); check_cuda(w, "w"); check_cuda(scale, "scale"); check_cuda(shift, "shift");
+  check_dtype(x, at::kBFloat16, "x"); check_dtype(w, at::kBFloat16, "w");
+  check_dtype(scale, at::kFloat, "scale"); check_dtype(shift, at::kFloat, "shift");
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "x [N,H,W,C], w [K,R,S,C]");
+  const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  const int K = w.size(0), R = w.size(1), S = w.size(2);
+  TORCH_CHECK(w.size(3) == C, "channel mismatch");
+  TORCH_CHECK(C % 8 == 0 && K % 8 == 0, "conv_infer needs C % 8 == 0 and K % 8 == 0");
+  TORCH_CHECK(stride >= 1 && pad >= 0, "conv_infer: stride >= 1, pad >= 0");
+  TORCH_CHECK(scale.numel() == K && shift.numel() == K, "scale / shift: fp32 [K]");
+  check_aligned(x, "x"); check_aligned(w, "w");
+  TORCH_CHECK(H + 2 * pad >= R && W + 2 * pad >= S, "conv_infer: the filter does not fit the padded image");
+  const int Ho = conv_out(H, R, stride, pad, 1), Wo = conv_out(W, S, stride, pad, 1);
+  TORCH_CHECK((long)N * Ho * Wo < (1L << 31), "conv_infer: fewer than 2^31 output pixels");
+  Tensor y;
+  if (out) {
+    check_cuda(*out, "out"); check_dtype(*out, at::kBFloat16, "out"); check_aligned(*out, "out");
+    TORCH_CHECK(out->sizes().vec() == (std::vector<int64_t>{N, Ho, Wo, K}), "out must be [N, Ho, Wo, K]");
+    y = *out;
+  } else {
+    y = torch::empty({N, Ho, Wo, K}, x.options());
+  }
+  const uint16_t* rp = nullptr;
+  if (res) {
+    check_cuda(*res, "res"); check_dtype(*res, at::kBFloat16, "res"); check_aligned(*res, "res");
+    TORCH_CHECK(res->sizes() == y.sizes(), "res must have the output's shape [N, Ho, Wo, K]");
+    rp = cbf(*res);
+  }
+  k8s_amd::launch_conv_infer(cbf(x), cbf(w), bf(y), N, H, W, C, K, R, S, (int)stride, (int)pad, Ho, Wo, f32(scale),
+                             f32(shift), rp, relu, cur_stream());
+  return y;
+}
+
 // One output-parity piece of a stride-s data gradient: out[n, i*s+a, j*s+b, :] = conv(dy, wsub, stride 1, pad)
 // over an Hs x Ws grid (i < Hs, j < Ws). wsub [C, Tr, Ts, K] holds the taps of that parity
 // (ops/conv.py _dgrad_strided_hip builds it); out is the full bf16 dx [N, H, W, C].
@@ -1516,6 +1570,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dres"), py::arg("dgamma"), py::arg("dbeta"), py::arg("rms"), py::arg("dsum") = py::none());
   m.def("xent_fwd", &xent_fwd);
   m.def("xent_bwd", &xent_bwd);
+  m.def("xent_eval", &xent_eval, py::arg("logits"), py::arg("labels"), py::arg("ignore_index") = -100);
   m.def("wgrad_stream_eligible", &k8s_amd::wgrad_stream_eligible, "tall-K weight-gradient kernel takes this shape");
   m.def("gemm", &gemm, py::arg("a"), py::arg("a_kmajor"), py::arg("b"), py::arg("b_kmajor"), py::arg("out"),
         py::arg("out_f32"), py::arg("bias"), py::arg("act"), py::arg("pre"), py::arg("accumulate"), py::arg("alpha"),
@@ -1572,6 +1627,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_fwd", &conv_fwd, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"), py::arg("dil"),
         py::arg("out_f32"), py::arg("bias"), py::arg("act"), py::arg("stats"),
         py::arg("xform") = py::none());
+  m.def("conv_infer", &conv_infer, py::arg("x"), py::arg("w"), py::arg("stride"), py::arg("pad"), py::arg("scale"),
+        py::arg("shift"), py::arg("res") = py::none(), py::arg("relu") = true, py::arg("out") = py::none());
   m.def("conv3x3_staged_ok", [](int H, int W, int C, int K, int R, int S, int stride, int pad) {
     // the staged-window forward / data gradient (conv3x3.hip) and the tiled weight gradient (wgrad_tile.hip) both
     // take this layer: BatchNorm + ReLU can be normalised on load in all three products

@@ -28,12 +28,35 @@ class Workload:
     optimizer: str = "sgd"                 # default optimizer family
     lr: float = 0.1
     meta: Dict = field(default_factory=dict)
+    # ---- evaluation (no autograd, nothing written to parameters, statistics or gradient slots)
+    # evaluate(inputs, folded=None) -> sums as device tensors: {"loss_sum" fp64, "count" int64} (+ {"top1", "top5"}
+    # int64 for ResNet); ``folded``: eval_state()'s tensor, computed here when None
+    evaluate: Optional[Callable] = None
+    # eval_batch(i, batch=None) -> held-out batch i (its own generator seed: identical every time it is requested)
+    eval_batch: Optional[Callable] = None
+    # eval_state() -> the flat tensor an evaluation pass shares between ranks (ResNet: the folded BatchNorms), or None
+    eval_state: Optional[Callable] = None
 
 
 MODELS = ("resnet50", "resnet_tiny", "bert_base", "bert_tiny", "llama3_8b", "llama_1b", "llama_tiny")
 # each model's default optimizer family (Workload.optimizer), known before the model is built
 MODEL_OPTIMIZER = {"resnet50": "sgd", "resnet_tiny": "sgd", "bert_base": "adam", "bert_tiny": "adam",
                    "llama3_8b": "adam", "llama_1b": "adam", "llama_tiny": "adam"}
+
+
+# ResNet evaluation path: ``ResNet.forward_infer`` (BatchNorms folded into the convolutions' epilogue) or, False, the
+# model's eval-mode forward (separate BatchNorm passes). Set from benchmarks/eval_throughput.py's A/B.
+EVAL_FOLDED = True
+
+
+def _plain_eval_forward(model, x):
+    """Logits of the model's own forward in eval mode, its training flag restored afterwards."""
+    was = model.training
+    model.eval()
+    try:
+        return model(x)
+    finally:
+        model.train(was)
 
 
 def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optional[int] = None,
@@ -46,6 +69,26 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
     store = ParamStore()
     gen = torch.Generator(device=device)
     gen.manual_seed(1000 + (seed if data_seed is None else data_seed))
+    # held-out data: a generator of its own, re-seeded per requested batch, so batch i never depends on what was
+    # drawn before it and never overlaps the training stream's seed
+    eval_gen = torch.Generator(device=device)
+    eval_seed = 1000 + (seed if data_seed is None else data_seed) + 2 ** 20
+
+    def heldout(make_with):
+        def get(i, batch_=None):
+            eval_gen.manual_seed(eval_seed + int(i))
+            return make_with(batch_ or batch, eval_gen)
+
+        return get
+
+    def token_eval(loss_of, labels_of):
+        """Evaluation of a model without mode-dependent layers: its own forward under no_grad."""
+        def evaluate(b, folded=None):
+            with torch.no_grad():
+                count = (labels_of(b) != -100).sum()
+                return {"loss_sum": loss_of(b).double() * count.double(), "count": count}
+
+        return evaluate
 
     def cached(make):
         box = {}
@@ -67,13 +110,20 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
         model = (resnet50(store, ncls) if name == "resnet50" else resnet_tiny(store, ncls))
         model = model.finalize(device, grad_dtype=grad_dtype, seed=seed, pad_to=pad_to)
 
-        def make():
-            x = torch.randn(batch, image, image, 3, device=device, generator=gen).to(dtype)
-            return model.prepare_input(x).contiguous(), torch.randint(0, ncls, (batch,), device=device,
-                                                                      generator=gen)
+        def make(n=batch, g=gen):
+            x = torch.randn(n, image, image, 3, device=device, generator=g).to(dtype)
+            return model.prepare_input(x).contiguous(), torch.randint(0, ncls, (n,), device=device, generator=g)
+
+        def evaluate(b, folded=None):
+            with torch.no_grad():
+                logits = model.forward_infer(b[0], folded) if EVAL_FOLDED else _plain_eval_forward(model, b[0])
+                loss, rank = K.xent_eval(logits, b[1])
+                return {"loss_sum": loss.double().sum(), "count": (b[1] != -100).sum(),
+                        "top1": (rank < 1).sum(), "top5": (rank < 5).sum()}
 
         return Workload(name, model, store, cached(make), lambda b: K.cross_entropy(model(b[0]), b[1]), batch,
-                        "images", "sgd", 0.1, {"image": image, "classes": ncls})
+                        "images", "sgd", 0.1, {"image": image, "classes": ncls}, evaluate=evaluate,
+                        eval_batch=heldout(make), eval_state=lambda: model.fold_bn()[0])
 
     if name in ("bert_base", "bert_tiny"):
         from k8s_amd.models import bert as M
@@ -86,11 +136,13 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
         seq = seq or (128 if name == "bert_base" else 32)
         model = M.BertForPreTraining(store, cfg).finalize(device, grad_dtype=grad_dtype, seed=seed, pad_to=pad_to)
 
-        def make():
-            return M.synthetic_batch(cfg, batch, seq, device, generator=gen)
+        def make(n=batch, g=gen):
+            return M.synthetic_batch(cfg, n, seq, device, generator=g)
 
         return Workload(name, model, store, cached(make), lambda b: model(*b, dtype=dtype)[0], batch * seq,
-                        "tokens", "adam", 1e-4, {"seq": seq})
+                        "tokens", "adam", 1e-4, {"seq": seq},
+                        evaluate=token_eval(lambda b: model(*b, dtype=dtype)[0], lambda b: b[2]),
+                        eval_batch=heldout(make))
 
     if name in ("llama3_8b", "llama_1b", "llama_tiny"):
         from k8s_amd.models import llama as M
@@ -99,10 +151,12 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
         seq = seq or (4096 if name != "llama_tiny" else 64)
         model = M.LlamaForCausalLM(store, cfg).finalize(device, grad_dtype=grad_dtype, seed=seed, pad_to=pad_to)
 
-        def make():
-            return M.synthetic_batch(cfg, batch, seq, device, generator=gen)
+        def make(n=batch, g=gen):
+            return M.synthetic_batch(cfg, n, seq, device, generator=g)
 
         return Workload(name, model, store, cached(make), lambda b: model(*b, dtype=dtype), batch * seq, "tokens",
-                        "adam", 3e-4, {"seq": seq})
+                        "adam", 3e-4, {"seq": seq},
+                        evaluate=token_eval(lambda b: model(*b, dtype=dtype), lambda b: b[1]),
+                        eval_batch=heldout(make))
 
     raise ValueError("unknown model %r (choose from %s)" % (name, ", ".join(MODELS)))

@@ -162,6 +162,76 @@ class ResNet(nn.Module):
         y = K.global_avg_pool_nhwc(y)
         return K.linear(y, self.fc_w, self.fc_b)
 
+    # ----------------------------------------------------------------------------------------- inference
+    def batch_norms(self):
+        """Every BatchNorm in forward order (the layout of ``fold_bn``'s flat tensor)."""
+        out = [self.bn1]
+        for b in self.blocks:
+            out += [b.bn1, b.bn2, b.bn3] + ([b.down_bn] if b.down is not None else [])
+        return out
+
+    def folded_views(self, flat: torch.Tensor):
+        """[(scale, shift)] views into a flat tensor laid out by ``fold_bn`` (e.g. a broadcast copy of it)."""
+        views, off = [], 0
+        for bn in self.batch_norms():
+            c = bn.running_mean.numel()
+            views.append((flat[off:off + c], flat[off + c:off + 2 * c]))
+            off += 2 * c
+        assert off == flat.numel(), "folded BatchNorm tensor of another model"
+        return views
+
+    @torch.no_grad()
+    def fold_bn(self):
+        """Every BatchNorm folded to its inference affine, from the fp32 masters and the running statistics:
+        ``scale = gamma / sqrt(var + eps)``, ``shift = beta - mean * scale``. Returns ``(flat, views)``: one flat
+        fp32 tensor ([scale | shift] per BatchNorm, forward order -- one broadcast moves all of it) and the per-BN
+        ``(scale, shift)`` views into it. Once per evaluation, not per batch."""
+        bns = self.batch_norms()
+        dev = self.bn1.running_mean.device
+        flat = torch.empty(2 * sum(bn.running_mean.numel() for bn in bns), device=dev, dtype=torch.float32)
+        views = self.folded_views(flat)
+        for bn, (scale, shift) in zip(bns, views):
+            torch.mul(bn.gamma.master.float(), torch.rsqrt(bn.running_var.float() + bn.eps), out=scale)
+            torch.sub(bn.beta.master.float(), bn.running_mean.float() * scale, out=shift)
+        return flat, views
+
+    @torch.no_grad()
+    def forward_infer(self, x, folded=None):
+        """Inference logits: every bottleneck convolution runs with its BatchNorm folded into the convolution's
+        epilogue (``ops.nn.conv_bn_act_infer``: conv1 / conv2 with ReLU, the downsample convolution without, conv3
+        with the identity / downsample output as the residual and ReLU) -- no statistics, masks or gradient links,
+        and no running statistic, parameter or gradient slot is written. ``folded``: ``fold_bn()``'s result, or just
+        its flat tensor (None: folded here).
+
+        The stem follows the input ``prepare_input`` made: the 8-channel image goes through ``conv_bn_act_infer`` +
+        ``max_pool_nhwc``; the space-to-depth image (16 channels, GPU) through the stem kernel, the eval-mode
+        BatchNorm kernel and ``max_pool_nhwc``. Numerics: two bf16 roundings per layer (the affine, then residual +
+        activation), as many as the training path."""
+        if folded is None:
+            folded = self.fold_bn()
+        views = self.folded_views(folded) if torch.is_tensor(folded) else folded[1]
+        it = iter(views)
+        sc, sh = next(it)
+        if x.shape[-1] == 16 and self.stem_s2d and x.is_cuda:
+            t = K.stem_conv_s2d(x, self.conv1.w)[0]
+            bn = self.bn1
+            t = K.batch_norm_act(t, bn.gamma, bn.beta, bn.running_mean, bn.running_var, None, True, False,
+                                 bn.momentum, bn.eps)
+        else:
+            t = K.conv_bn_act_infer(x, self.conv1.w, sc, sh, self.conv1.stride, self.conv1.pad)
+        y = K.max_pool_nhwc(t, 3, 2, 1)
+        for b in self.blocks:
+            (s1, h1), (s2, h2), (s3, h3) = next(it), next(it), next(it)
+            idn = y
+            if b.down is not None:
+                sd, hd = next(it)
+                idn = K.conv_bn_act_infer(y, b.down.w, sd, hd, b.down.stride, b.down.pad, relu=False)
+            t = K.conv_bn_act_infer(y, b.conv1.w, s1, h1, b.conv1.stride, b.conv1.pad)
+            t = K.conv_bn_act_infer(t, b.conv2.w, s2, h2, b.conv2.stride, b.conv2.pad)
+            y = K.conv_bn_act_infer(t, b.conv3.w, s3, h3, b.conv3.stride, b.conv3.pad, residual=idn)
+        y = K.global_avg_pool_nhwc(y)
+        return K.linear(y, self.fc_w, self.fc_b)
+
 
 def resnet50(store: ParamStore, num_classes: int = 1000) -> ResNet:
     return ResNet(store, (3, 4, 6, 3), num_classes)

@@ -38,7 +38,7 @@ from k8s_amd.ops._ext import load as _load
 # and 12.02k vs 12.20k with only the long-K dgrads in round 3 (scripts/gpurun/env_ab.sh), and was removed.)
 
 STATS = {"hip_fwd": 0, "aten_fwd": 0, "hip_wgrad": 0, "aten_wgrad": 0, "hip_dgrad": 0, "aten_dgrad": 0,
-         "bn_bstats": 0}
+         "bn_bstats": 0, "hip_infer": 0, "aten_infer": 0}
 
 # (Round 5 built weight gradients on a second HIP stream -- each conv's dW kernel forked off the compute stream to
 # overlap the data gradient and BatchNorm passes after it. The streams co-ran, but the HBM-bound kernels stretched:
@@ -94,6 +94,33 @@ def conv_fwd(x, w, stride, padding, stats=None):
         return _load().conv_fwd(x, w, stride, padding, 1, False, None, 0, stats)
     _vendor("fwd", x, w, stride, padding)
     return _nhwc(F.conv2d(_nchw(x), _nchw(w), None, stride, padding))
+
+
+def infer_ok(x, w, scale, shift, residual=None) -> bool:
+    """The inference epilogue's contract (gemm.hip IEPI): bf16 GPU operands, C % 8 == 0, K % 8 == 0, contiguous
+    16-B aligned tensors, fp32 scale / shift."""
+    ts = [x, w] + ([residual] if residual is not None else [])
+    return (_hip(*ts) and x.shape[-1] % 8 == 0 and w.shape[0] % 8 == 0
+            and all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts)
+            and scale.is_cuda and shift.is_cuda and scale.dtype == torch.float32 and shift.dtype == torch.float32
+            and scale.is_contiguous() and shift.is_contiguous())
+
+
+def conv_infer(x, w, stride, padding, scale, shift, residual=None, relu=True):
+    """y = act(bf16(conv(x, w) * scale + shift) + residual): an inference convolution with its BatchNorm folded to a
+    per-channel fp32 affine, on the tile kernel's inference epilogue inside its contract; outside it (GPU) an ATen
+    composite with the same two roundings, counted in ``STATS["aten_infer"]`` and warned about once."""
+    if infer_ok(x, w, scale, shift, residual):
+        STATS["hip_infer"] += 1
+        return _load().conv_infer(x, w, stride, padding, scale, shift, residual, relu)
+    _vendor("infer", x, w, stride, padding)
+    y = F.conv2d(_nchw(x), _nchw(w), None, stride, padding).permute(0, 2, 3, 1)
+    y = (y.float() * scale.float() + shift.float()).to(x.dtype)
+    if residual is not None:
+        y = y.float() + residual.float()
+    if relu:
+        y = torch.relu(y)
+    return y.to(x.dtype).contiguous()
 
 
 def _aten_bwd(gy, x, w, stride, padding, need_dx, need_dw):

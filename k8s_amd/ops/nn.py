@@ -221,6 +221,24 @@ def conv2d_nhwc(x: torch.Tensor, p, stride: int = 1, padding: int = 0, with_stat
     return (y, sums) if with_stats else y
 
 
+def conv_bn_act_infer(x, pw, scale, shift, stride: int = 1, padding: int = 0, residual=None, relu: bool = True):
+    """Inference convolution with its BatchNorm folded into the epilogue:
+    ``y = act(conv(x, w) * scale + shift + residual)`` for NHWC ``x``, KRSC weight ``pw`` (a store parameter or a
+    tensor) and fp32 [K] ``scale`` / ``shift`` (``ResNet.fold_bn``). No autograd: call it under ``torch.no_grad()``.
+
+    GPU bf16 inside the kernel's contract (C % 8 == 0, K % 8 == 0): the tile kernel's inference epilogue, two bf16
+    roundings (the affine, then residual + activation); outside it an ATen composite (``ops.conv.STATS``). CPU: the
+    fp32 oracle of ``ops.reference``."""
+    assert not torch.is_grad_enabled(), "conv_bn_act_infer is an inference op: call it under torch.no_grad()"
+    if torch.is_tensor(pw):
+        w = pw
+    else:
+        w = pw.weight if x.dtype == pw.weight.dtype else pw.master.to(x.dtype)
+    if _gpu(x):
+        return _conv_impl().conv_infer(x, w, stride, padding, scale, shift, residual, relu)
+    return ref.conv_bn_act_infer(x, w, scale, shift, stride, padding, residual, relu)
+
+
 class _StemS2D(torch.autograd.Function):
     """The 7x7 / stride-2 / pad-3 stem as a 4x4 / stride-1 conv over the 2x2 space-to-depth image
     (csrc/kernels/stem.hip): the master weight stays [K, 7, 7, C]; forward maps it to [K, 4, 4, 16], backward maps
@@ -825,6 +843,21 @@ def cross_entropy(logits, labels, ignore_index: int = -100, smoothing: float = 0
     """Mean softmax cross-entropy over valid rows of [R, V] logits (classes = first ``valid`` columns)."""
     return _CrossEntropy.apply(logits.reshape(-1, logits.shape[-1]), labels.reshape(-1), ignore_index, smoothing,
                                valid)
+
+
+def xent_eval(logits, labels, ignore_index: int = -100, valid: int = None):
+    """Evaluation metrics of [R, V] logits: ``(loss[R] fp32, rank[R] int32)``, the per-row cross-entropy and the
+    label's rank ``#{j : l[j] > l[y]} + #{j < y : l[j] == l[y]}`` over the first ``valid`` columns (ties go to the
+    lower index, so the rank is exact and deterministic). Ignored rows: loss 0, rank V. Top-k is ``rank < k``."""
+    logits = logits.reshape(-1, logits.shape[-1])
+    labels = labels.reshape(-1)
+    logits = logits if logits.stride(-1) == 1 else logits.contiguous()
+    if valid is not None and valid != logits.shape[1]:
+        logits = logits[:, :valid]
+    if _gpu(logits):
+        loss, rank = _C().xent_eval(logits.detach(), labels.contiguous(), ignore_index)
+        return loss, rank
+    return ref.xent_eval(logits.detach(), labels, ignore_index)
 
 
 # =========================================================================== pooling (NHWC)

@@ -110,6 +110,36 @@ def xent_bwd(logits, labels, lse, dscale, ignore_index=-100, smoothing=0.0):
     return (p * sc.unsqueeze(-1)).to(logits.dtype)
 
 
+def xent_eval(logits, labels, ignore_index=-100):
+    """(loss[R] fp32, rank[R] int32): per-row cross-entropy and the label's rank among the columns,
+    rank = #{j : l[j] > l[y]} + #{j < y : l[j] == l[y]} (ties to the lower index). Ignored rows: loss 0, rank V."""
+    lf = logits.float()
+    V = lf.shape[-1]
+    valid = labels != ignore_index
+    safe = torch.where(valid, labels, torch.zeros_like(labels))
+    picked = lf.gather(-1, safe.unsqueeze(-1))
+    loss = torch.logsumexp(lf, -1) - picked.squeeze(-1)
+    before = torch.arange(V, device=lf.device).unsqueeze(0) < safe.unsqueeze(-1)
+    rank = ((lf > picked) | ((lf == picked) & before)).sum(-1)
+    loss = torch.where(valid, loss, torch.zeros_like(loss))
+    rank = torch.where(valid, rank, torch.full_like(rank, V))
+    return loss, rank.to(torch.int32)
+
+
+# --------------------------------------------------------------------------- inference convolution
+def conv_bn_act_infer(x, w, scale, shift, stride, padding, residual=None, relu=True):
+    """act(conv(x, w) * scale + shift + residual) on NHWC ``x`` / KRSC ``w`` with a folded BatchNorm (fp32 [K] scale
+    / shift), in fp32, rounded once to ``x``'s dtype."""
+    y = torch.nn.functional.conv2d(x.float().permute(0, 3, 1, 2), w.float().permute(0, 3, 1, 2), None, stride,
+                                   padding).permute(0, 2, 3, 1)
+    y = y * scale.float() + shift.float()
+    if residual is not None:
+        y = y + residual.float()
+    if relu:
+        y = torch.relu(y)
+    return y.to(x.dtype).contiguous()
+
+
 # --------------------------------------------------------------------------- optimizers
 def _decay_vec(mask, n, wd, device):
     if mask is None:

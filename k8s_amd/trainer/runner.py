@@ -16,6 +16,8 @@ process exit code (`/root/reference/pkg/trainer/training.go:45-73`):
   reference treats OOMKilled as permanent); 128+ retryable (collective /
   rendezvous / connection failures, SIGTERM): the operator restarts the
   replica and it resumes from the latest checkpoint;
+* evaluation (``--eval-every N`` / ``--eval-only``): forward-only passes over held-out synthetic batches or the
+  fixed training batch, an ``eval`` event (loss, top-1 / top-5 or perplexity) and ``eval/*`` TensorBoard scalars;
 * outputs (chief only): ``<logdir>/events.out.tfevents.*`` (TensorBoard),
   ``<logdir>/metrics.jsonl`` (one JSON record per logged step, plus
   ``start`` / ``step0`` / ``done`` events with wall-clock times so the
@@ -30,6 +32,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import signal
 import sys
@@ -90,6 +93,16 @@ def parse(argv=None):
     ap.add_argument("--fresh-batches", action="store_true", help="draw a new synthetic batch every step")
     ap.add_argument("--graph", action="store_true", default=os.environ.get("K8S_AMD_GRAPH", "0") == "1",
                     help="capture the whole step in a hipGraph after warmup (single rank, all-reduce strategy)")
+    ap.add_argument("--eval-every", type=int, default=0,
+                    help="evaluate every N steps and after the last step (0: off): an 'eval' event in metrics.jsonl "
+                         "and eval/* TensorBoard scalars")
+    ap.add_argument("--eval-batches", type=int, default=1, help="batches per evaluation, per rank")
+    ap.add_argument("--eval-batch", type=int, default=None, help="per-rank evaluation batch (default: --batch)")
+    ap.add_argument("--eval-data", default="heldout", choices=["heldout", "train"],
+                    help="heldout: synthetic batches from a generator seed of their own; train: the fixed training "
+                         "batch (not with --fresh-batches)")
+    ap.add_argument("--eval-only", action="store_true",
+                    help="restore the newest checkpoint / PS snapshot, evaluate once, exit 0")
     ap.add_argument("--fail-at-step", type=int, default=-1, help="(testing) raise a retryable failure once")
     ap.add_argument("--hang-timeout", type=float, default=float(os.environ.get("K8S_AMD_HANG_TIMEOUT", "0")),
                     help="exit 143 (retryable) when no step completes for this many seconds (0: off)")
@@ -294,6 +307,20 @@ def train(a) -> int:
     t_start = time.time()
     t_proc = _process_start_time()
     tf_config = os.environ.get("TF_CONFIG")
+    evaluating = a.eval_every > 0 or a.eval_only
+    config_error = None
+    if evaluating and a.graph:
+        config_error = "--eval-every / --eval-only cannot be combined with --graph (the captured step has no " \
+                       "evaluation pass)"
+    elif evaluating and a.eval_data == "train" and a.fresh_batches:
+        config_error = "--eval-data train evaluates the fixed training batch: not with --fresh-batches"
+    elif evaluating and (a.eval_batches < 1 or (a.eval_batch is not None and a.eval_batch < 1)):
+        config_error = "--eval-batches and --eval-batch must be positive"
+    elif a.eval_every < 0:
+        config_error = "--eval-every must be >= 0"
+    if config_error:
+        print("error: %s" % config_error, file=sys.stderr, flush=True)
+        return EXIT_PERMANENT
     info = kdist.rank_from_env()
     if info is not None and info.role == "ps" and tf_config:
         return _run_ps(info, tf_config)
@@ -362,6 +389,12 @@ def train(a) -> int:
         psv = PsVariables(ps_addrs)
     start_step = _restore(a, w, opt, dev, chief, world, metrics, psv, svc)
     t_ready = time.time()  # model, optimizer and data built, checkpoint restored
+    if a.eval_only and start_step == 0:  # (start_step is broadcast: every rank leaves together)
+        metrics.event(event="error", error="--eval-only: no checkpoint in --ckpt-dir and no PS variable snapshot "
+                      "to restore")
+        metrics.close()
+        kdist.destroy()
+        return EXIT_PERMANENT
     if world > 1:
         # step-0 transport self-check: one gradient bucket through the configured transport
         # (fp32 / bf16 all-reduce, ZeRO-1 push) against a plain fp32 all_reduce; the verdict is the same on every
@@ -430,6 +463,48 @@ def train(a) -> int:
     elif a.graph:
         metrics.event(event="warning", message="--graph needs one GPU rank, --strategy allreduce, no --trace "
                       "and no kernel debug mode")
+    def evaluate(step) -> float:
+        """One evaluation pass (collective); returns the seconds it took. Rank 0's evaluation state (ResNet: the
+        BatchNorms folded from its fp32 masters and running statistics -- what a checkpoint would hold) is broadcast,
+        every rank runs its batches accumulating on the device, one all_reduce combines the sums and one host read
+        per evaluation fetches them."""
+        if svc is not None:
+            svc.sync_master()  # the sharded service keeps only each rank's owned fp32 slices current
+        sync()
+        t0 = time.time()
+        state = w.eval_state() if w.eval_state is not None else None
+        if state is not None and world > 1:
+            torch.distributed.broadcast(state, 0)
+        keys = ("loss_sum", "count", "top1", "top5")
+        tot = torch.zeros(len(keys), dtype=torch.float64, device=dev)  # counts are exact in fp64 below 2^53
+        for i in range(a.eval_batches):
+            if a.eval_data == "train":
+                inputs = w.batch(step)
+            else:
+                inputs = w.eval_batch(i, a.eval_batch)
+            sums = w.evaluate(inputs, state)
+            tot += torch.stack([sums[k].double() if k in sums else tot.new_zeros(()) for k in keys])
+            if watchdog is not None:
+                watchdog.kick()
+        if world > 1:
+            torch.distributed.all_reduce(tot)
+        loss_sum, count, top1, top5 = tot.tolist()  # the one host synchronisation of the evaluation
+        dt = time.time() - t0
+        if chief:
+            n = max(count, 1.0)
+            rec = {"loss": loss_sum / n}
+            if w.unit == "images":
+                rec.update(top1=top1 / n, top5=top5 / n)
+            elif a.model.startswith("llama"):
+                rec["perplexity"] = math.exp(min(loss_sum / n, 700.0))
+            metrics.event(event="eval", step=step, examples=int(count), data=a.eval_data,
+                          **{"%s_per_sec" % w.unit: round(count / max(dt, 1e-9), 2)}, **rec)
+            metrics.scalars(step, {"eval/" + k: v for k, v in rec.items()})
+        return dt
+
+    if a.eval_only:
+        a.steps = start_step  # no training step, no new checkpoint: evaluate the restored state and finish
+        evaluate(start_step - 1)
     t_last, n_last = time.time(), 0
     loss_v = float("nan")
     try:
@@ -484,6 +559,8 @@ def train(a) -> int:
                                   **{"%s_per_sec" % w.unit: round(rate, 2)}, **extra)
                     metrics.scalars(step, {"loss": loss_v, "%s_per_sec" % w.unit: rate, "learning_rate": cur_lr})
                 t_last, n_last = now, 0
+            if a.eval_every and ((step + 1) % a.eval_every == 0 or step + 1 == a.steps):
+                t_last += evaluate(step)  # evaluation time is not part of the training throughput window
             if a.ckpt_dir and a.ckpt_every and (step + 1) % a.ckpt_every == 0 and step + 1 < a.steps:
                 save(step)
             if sync_every and ps_addrs and ((step + 1) % sync_every == 0 or step + 1 == a.steps):
