@@ -102,6 +102,28 @@ __device__ __forceinline__ void store8(uint16_t* p, const float (&o)[8]) {
   *reinterpret_cast<bf16x8_t*>(p) = pack_bf16x8(o);
 }
 
+// 4 gradient values (fp32 or bf16) as floats / 4 floats as bf16: the flat optimizers' 16-B and 8-B accesses
+template <typename GT>
+__device__ __forceinline__ void load_grad4(const GT* g, long i, float (&o)[4]);
+
+template <>
+__device__ __forceinline__ void load_grad4<float>(const float* g, long i, float (&o)[4]) {
+  float4 v = *reinterpret_cast<const float4*>(g + i);
+  o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+}
+template <>
+__device__ __forceinline__ void load_grad4<uint16_t>(const uint16_t* g, long i, float (&o)[4]) {
+  bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(g + i);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = bf2f((uint16_t)v[j]);
+}
+
+__device__ __forceinline__ void store_bf4(uint16_t* p, long i, const float4& v) {
+  bf16x4_t o;
+  o[0] = (short)f2bf(v.x); o[1] = (short)f2bf(v.y); o[2] = (short)f2bf(v.z); o[3] = (short)f2bf(v.w);
+  *reinterpret_cast<bf16x4_t*>(p + i) = o;
+}
+
 // Division by a runtime-invariant divisor as multiply-high + shift (valid for 0 <= n < 2^31).
 struct FastDiv {
   uint32_t d, m, s;

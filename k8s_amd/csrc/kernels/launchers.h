@@ -23,6 +23,22 @@ void launch_clip_factor(const float* stats, float max_norm, float* factor, hipSt
 void launch_slice_sum(const uint16_t* in, long n, int world, float* out, uint16_t* out_bf, hipStream_t st);
 void launch_cast_bf16(const float* in, uint16_t* out, long n, hipStream_t st);
 
+// layerwise.hip: LARS / LAMB over a work-item table, items = long[n_items][4] {flat offset, state offset, length,
+// segment}; flags = per-segment bits (1 decay, 2 low-precision copy); partial [n_items][2], sums [n_seg][2]
+constexpr int kLayerItemMax = 16384;  // elements per work item, at most
+void launch_layer_sums(const long* items, int n_items, const float* p, float* m1, float* m2, const void* g,
+                       bool g_bf16, const uint8_t* flags, float* partial, bool lamb, float b1, float b2, float eps,
+                       float wd, float scale, const float* scale_ptr, const float* hyper, float bc1, float bc2,
+                       hipStream_t st);
+void launch_layer_fold(const float* partial, const int* seg_start, int n_seg, float* sums, const float* scale_ptr,
+                       hipStream_t st);
+void launch_layer_ratio(const float* sums, const uint8_t* flags, int n_seg, float* ratio, bool lamb, float eta,
+                        float wd, const float* scale_ptr, hipStream_t st);
+void launch_layer_update(const long* items, int n_items, float* p, float* m1, const float* m2, const void* g,
+                         bool g_bf16, uint16_t* pbf, const uint8_t* flags, const float* ratio, bool lamb, float lr,
+                         float mu, float b1, float b2, float eps, float wd, float scale, const float* scale_ptr,
+                         const float* hyper, float bc1, float bc2, bool first_step, hipStream_t st);
+
 // batchnorm.hip
 int bn_workspace_floats(long M, int C);
 // params: fp32 workspace, [2][C] for the forward (scale, shift), [4][C] for the backward (sc, B, D, shift)

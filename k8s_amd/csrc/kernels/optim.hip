@@ -24,27 +24,6 @@
 namespace k8s_amd {
 
 template <typename GT>
-__device__ __forceinline__ void load_grad4(const GT* g, long i, float (&o)[4]);
-
-template <>
-__device__ __forceinline__ void load_grad4<float>(const float* g, long i, float (&o)[4]) {
-  float4 v = *reinterpret_cast<const float4*>(g + i);
-  o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-}
-template <>
-__device__ __forceinline__ void load_grad4<uint16_t>(const uint16_t* g, long i, float (&o)[4]) {
-  bf16x4_t v = *reinterpret_cast<const bf16x4_t*>(g + i);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = bf2f((uint16_t)v[j]);
-}
-
-__device__ __forceinline__ void store_bf4(uint16_t* p, long i, const float4& v) {
-  bf16x4_t o;
-  o[0] = (short)f2bf(v.x); o[1] = (short)f2bf(v.y); o[2] = (short)f2bf(v.z); o[3] = (short)f2bf(v.w);
-  *reinterpret_cast<bf16x4_t*>(p + i) = o;
-}
-
-template <typename GT>
 __global__ void __launch_bounds__(256) sgd_kernel(float* __restrict__ p, float* __restrict__ mom,
                                                   const GT* __restrict__ g, uint16_t* __restrict__ pbf,
                                                   long n4, const uint8_t* __restrict__ decay_mask, float lr, float mu, float wd,

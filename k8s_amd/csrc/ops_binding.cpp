@@ -8,8 +8,11 @@
 
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
+#include <utility>
+#include <vector>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
@@ -97,6 +100,132 @@ Tensor clip_factor(Tensor stats, double max_norm) {
   auto f = torch::empty({1}, stats.options());
   k8s_amd::launch_clip_factor(f32(stats), (float)max_norm, f32(f), cur_stream());
   return f;
+}
+
+// ------------------------------------------------------------------ layer-wise optimizers (LARS / LAMB)
+// The work-item table of kernels/layerwise.hip, validated ONCE on the host against the buffer sizes it will index
+// (the kernels trust it), then kept on the device: every launch below only has to compare buffer sizes with the
+// sizes the table was validated for.
+struct LayerTable {
+  Tensor items;      // int64 [n_items][4] on the device
+  Tensor seg_start;  // int32 [n_seg + 1] on the device
+  int64_t n_items = 0, n_seg = 0, n_master = 0, n_state = 0;
+};
+
+LayerTable layer_table(Tensor items, int64_t n_master, int64_t n_state, int64_t n_seg, at::Device device) {
+  TORCH_CHECK(!items.is_cuda() && items.scalar_type() == at::kLong && items.is_contiguous(),
+              "items must be a contiguous int64 host tensor");
+  TORCH_CHECK(items.dim() == 2 && items.size(1) == 4, "items must be [n, 4] {flat offset, state offset, length, segment}");
+  TORCH_CHECK(device.is_cuda(), "the table lives on the GPU");
+  TORCH_CHECK(n_master >= 0 && n_state >= 0 && n_seg >= 0 && n_seg < (1 << 30), "bad sizes");
+  const int64_t n = items.size(0);
+  TORCH_CHECK(n < (int64_t(1) << 30), "too many work items");
+  const int64_t* e = items.data_ptr<int64_t>();
+  std::vector<int32_t> start(n_seg + 1, 0);
+  std::vector<std::pair<int64_t, int64_t>> flat(n), state(n);
+  int64_t prev = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t off = e[4 * i], soff = e[4 * i + 1], len = e[4 * i + 2], seg = e[4 * i + 3];
+    TORCH_CHECK(len > 0 && len <= k8s_amd::kLayerItemMax && len % 64 == 0, "item ", i, ": length ", len);
+    TORCH_CHECK(off >= 0 && off % 64 == 0 && off + len <= n_master, "item ", i, ": flat range outside the buffers");
+    TORCH_CHECK(soff >= 0 && soff % 64 == 0 && soff + len <= n_state, "item ", i, ": state range outside the state");
+    TORCH_CHECK(seg >= prev && seg < n_seg, "item ", i, ": segments must be in [0, n_seg) and contiguous in the table");
+    prev = seg;
+    ++start[seg + 1];
+    flat[i] = {off, len};
+    state[i] = {soff, len};
+  }
+  for (int64_t s = 0; s < n_seg; ++s) start[s + 1] += start[s];
+  for (auto* v : {&flat, &state}) {  // two items on the same elements would race
+    std::sort(v->begin(), v->end());
+    for (int64_t i = 1; i < n; ++i)
+      TORCH_CHECK((*v)[i - 1].first + (*v)[i - 1].second <= (*v)[i].first, "work items overlap");
+  }
+  LayerTable t;
+  t.items = items.to(device);
+  t.seg_start = torch::from_blob(start.data(), {n_seg + 1}, at::kInt).clone().to(device);
+  t.n_items = n; t.n_seg = n_seg; t.n_master = n_master; t.n_state = n_state;
+  return t;
+}
+
+void check_f32(const LayerTable& tab, const Tensor& t, int64_t n, const char* name) {
+  check_cuda(t, name); check_dtype(t, at::kFloat, name); check_aligned(t, name);
+  TORCH_CHECK(t.device() == tab.items.device(), name, " is not on the item table's device");
+  TORCH_CHECK(t.numel() == n, name, " has ", t.numel(), " elements, the item table was built for ", n);
+}
+const uint8_t* seg_flags(const LayerTable& tab, const Tensor& flags) {
+  TORCH_CHECK(flags.is_cuda() && flags.scalar_type() == at::kByte && flags.is_contiguous() && flags.numel() == tab.n_seg,
+              "flags must be uint8 GPU, one per segment");
+  return flags.data_ptr<uint8_t>();
+}
+bool grad_bf16(const LayerTable& tab, const Tensor& g) {
+  check_cuda(g, "grad"); check_aligned(g, "grad");
+  TORCH_CHECK(g.scalar_type() == at::kFloat || g.scalar_type() == at::kBFloat16, "grad must be fp32 or bf16");
+  TORCH_CHECK(g.numel() == tab.n_master, "grad size mismatch");
+  return g.scalar_type() == at::kBFloat16;
+}
+const float* clip_ptr(const c10::optional<Tensor>& t) {
+  if (!t) return nullptr;
+  check_cuda(*t, "scale_t"); check_dtype(*t, at::kFloat, "scale_t");
+  TORCH_CHECK(t->numel() >= 1, "scale_t is empty");
+  return t->data_ptr<float>();
+}
+
+// pass 1. m1 / m2: LAMB's moments (advanced here); both absent for LARS.
+void layer_sums(const LayerTable& tab, Tensor p, c10::optional<Tensor> m1, c10::optional<Tensor> m2, Tensor g,
+                Tensor flags, Tensor partial, double b1, double b2, double eps, double wd, double scale,
+                c10::optional<Tensor> scale_t, int64_t step, c10::optional<Tensor> hyper) {
+  const bool lamb = m1.has_value();
+  TORCH_CHECK(lamb == m2.has_value(), "LAMB takes both moments, LARS neither");
+  check_f32(tab, p, tab.n_master, "param");
+  if (lamb) { check_f32(tab, *m1, tab.n_state, "exp_avg"); check_f32(tab, *m2, tab.n_state, "exp_avg_sq"); }
+  check_f32(tab, partial, 2 * tab.n_items, "partial");
+  const bool gb = grad_bf16(tab, g);
+  const float bc1 = 1.f - std::pow((float)b1, (float)step);
+  const float bc2 = 1.f - std::pow((float)b2, (float)step);
+  k8s_amd::launch_layer_sums(tab.items.data_ptr<int64_t>(), (int)tab.n_items, f32(p), lamb ? f32(*m1) : nullptr,
+                             lamb ? f32(*m2) : nullptr, g.data_ptr(), gb, seg_flags(tab, flags), f32(partial), lamb,
+                             (float)b1, (float)b2, (float)eps, (float)wd, (float)scale, clip_ptr(scale_t),
+                             hyper_ptr(hyper), bc1, bc2, cur_stream());
+}
+
+void layer_fold(const LayerTable& tab, Tensor partial, Tensor sums, c10::optional<Tensor> scale_t) {
+  check_f32(tab, partial, 2 * tab.n_items, "partial");
+  check_f32(tab, sums, 2 * tab.n_seg, "sums");
+  k8s_amd::launch_layer_fold(f32(partial), tab.seg_start.data_ptr<int32_t>(), (int)tab.n_seg, f32(sums),
+                             clip_ptr(scale_t), cur_stream());
+}
+
+void layer_ratio(const LayerTable& tab, Tensor sums, Tensor flags, Tensor ratio, bool lamb, double eta, double wd,
+                 c10::optional<Tensor> scale_t) {
+  check_f32(tab, sums, 2 * tab.n_seg, "sums");
+  check_f32(tab, ratio, tab.n_seg, "ratio");
+  k8s_amd::launch_layer_ratio(f32(sums), seg_flags(tab, flags), (int)tab.n_seg, f32(ratio), lamb, (float)eta,
+                              (float)wd, clip_ptr(scale_t), cur_stream());
+}
+
+// pass 2. LARS: st1 = momentum, st2 absent. LAMB: st1 / st2 = the moments pass 1 advanced.
+void layer_update(const LayerTable& tab, Tensor p, Tensor st1, c10::optional<Tensor> st2, Tensor g,
+                  c10::optional<Tensor> pbf, Tensor flags, Tensor ratio, double lr, double mu, double b1, double b2,
+                  double eps, double wd, double scale, c10::optional<Tensor> scale_t, int64_t step, bool first_step,
+                  c10::optional<Tensor> hyper) {
+  const bool lamb = st2.has_value();
+  check_f32(tab, p, tab.n_master, "param");
+  check_f32(tab, st1, tab.n_state, lamb ? "exp_avg" : "momentum");
+  if (lamb) check_f32(tab, *st2, tab.n_state, "exp_avg_sq");
+  check_f32(tab, ratio, tab.n_seg, "ratio");
+  const bool gb = grad_bf16(tab, g);
+  if (pbf) {
+    check_cuda(*pbf, "param_bf16"); check_dtype(*pbf, at::kBFloat16, "param_bf16"); check_aligned(*pbf, "param_bf16");
+    TORCH_CHECK(pbf->numel() == tab.n_master, "param_bf16 size mismatch");
+  }
+  const float bc1 = 1.f - std::pow((float)b1, (float)step);
+  const float bc2 = 1.f - std::pow((float)b2, (float)step);
+  k8s_amd::launch_layer_update(tab.items.data_ptr<int64_t>(), (int)tab.n_items, f32(p), f32(st1),
+                               lamb ? f32(*st2) : nullptr, g.data_ptr(), gb, pbf ? bf(*pbf) : nullptr,
+                               seg_flags(tab, flags), f32(ratio), lamb, (float)lr, (float)mu, (float)b1, (float)b2,
+                               (float)eps, (float)wd, (float)scale, clip_ptr(scale_t), hyper_ptr(hyper), bc1, bc2,
+                               first_step, cur_stream());
 }
 
 // ------------------------------------------------------------------ bf16 gradient transport
@@ -1552,6 +1681,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("decay_mask"), py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
         py::arg("scale"), py::arg("scale_t"), py::arg("step"), py::arg("decoupled"), py::arg("hyper") = py::none());
   m.def("grad_sumsq", &grad_sumsq);
+  py::class_<LayerTable>(m, "LayerTable", "validated work-item table of the layer-wise optimizers")
+      .def_readonly("items", &LayerTable::items).def_readonly("seg_start", &LayerTable::seg_start)
+      .def_readonly("n_items", &LayerTable::n_items).def_readonly("n_seg", &LayerTable::n_seg)
+      .def_readonly("n_master", &LayerTable::n_master).def_readonly("n_state", &LayerTable::n_state);
+  m.attr("layer_item_max") = k8s_amd::kLayerItemMax;
+  m.def("layer_table", &layer_table, py::arg("items"), py::arg("n_master"), py::arg("n_state"), py::arg("n_seg"),
+        py::arg("device"));
+  m.def("layer_sums", &layer_sums, py::arg("table"), py::arg("p"), py::arg("m1"), py::arg("m2"), py::arg("g"),
+        py::arg("flags"), py::arg("partial"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
+        py::arg("scale"), py::arg("scale_t"), py::arg("step"), py::arg("hyper") = py::none());
+  m.def("layer_fold", &layer_fold, py::arg("table"), py::arg("partial"), py::arg("sums"), py::arg("scale_t"));
+  m.def("layer_ratio", &layer_ratio, py::arg("table"), py::arg("sums"), py::arg("flags"), py::arg("ratio"),
+        py::arg("lamb"), py::arg("eta"), py::arg("wd"), py::arg("scale_t"));
+  m.def("layer_update", &layer_update, py::arg("table"), py::arg("p"), py::arg("st1"), py::arg("st2"), py::arg("g"),
+        py::arg("pbf"), py::arg("flags"), py::arg("ratio"), py::arg("lr"), py::arg("mu"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("scale"), py::arg("scale_t"), py::arg("step"),
+        py::arg("first_step"), py::arg("hyper") = py::none());
   m.def("clip_factor", &clip_factor);
   m.def("slice_sum", &slice_sum, py::arg("recv"), py::arg("world"), py::arg("out") = py::none(),
         py::arg("out_bf") = py::none(), "fp32 rank-order sum of an all-to-all's bf16 chunks");

@@ -187,3 +187,53 @@ def adam(p, m1, m2, g, pbf, mask, lr, b1, b2, eps, wd, scale, scale_t, step, dec
 def grad_sumsq(g):
     gf = g.float()
     return torch.stack([(gf * gf).sum(), (~torch.isfinite(gf)).sum().float()])
+
+
+# --------------------------------------------------------------------------- layer-wise optimizers (LARS / LAMB)
+# These work on one PIECE of one parameter slot at a time (a slot, or the part of it inside one owned range of a
+# sharded update); ``ops/optim.py`` walks the pieces. ``s`` is grad_scale times the clip factor, ``w`` the slot's
+# weight decay (0 where it does not decay).
+def lamb_moments(m1, m2, g, s, b1, b2):
+    gr = g.float() * s
+    m1.mul_(b1).add_((1 - b1) * gr)
+    m2.mul_(b2).add_((1 - b2) * gr * gr)
+
+
+def lamb_u(p, m1, m2, b1, b2, eps, w, step):
+    """LAMB's direction from the advanced moments: the Adam step plus decay."""
+    bc1 = 1 - b1 ** step
+    bc2 = 1 - b2 ** step
+    return (m1 / bc1) / ((m2 / bc2).sqrt() + eps) + w * p
+
+
+def layer_sums(p, x):
+    """(sum p^2, sum x^2) of one piece, fp32 [2]; the per-slot sums are these added over the slot's pieces."""
+    return torch.stack([(p * p).sum(), (x * x).sum()])
+
+
+def trust_ratio(sums, decay, lamb, eta=0.001, wd=0.0):
+    """Per-slot trust ratio from sums [n][2] and the decay flags [n]: LAMB ||p|| / ||u||, LARS eta ||p|| / (||g|| +
+    wd ||p||); 1 where the slot does not decay or either norm is zero."""
+    pn, xn = sums[:, 0].sqrt(), sums[:, 1].sqrt()
+    ok = decay.bool() & (pn > 0) & (xn > 0)
+    den = xn if lamb else xn + wd * pn
+    r = pn / torch.where(ok, den, torch.ones_like(den))
+    if not lamb:
+        r = r * eta
+    return torch.where(ok, r, torch.ones_like(r))
+
+
+def lars(p, mom, g, pbf, r, lr, mu, w, s, first_step):
+    d = r * (g.float() * s + w * p)
+    m = d.clone() if first_step else mom * mu + d
+    mom.copy_(m)
+    p.sub_(lr * m)
+    if pbf is not None:
+        pbf.copy_(p)
+
+
+def lamb(p, m1, m2, pbf, r, lr, b1, b2, eps, w, step):
+    """Second half of a LAMB step (``lamb_moments`` has run): p -= lr r u."""
+    p.sub_(lr * r * lamb_u(p, m1, m2, b1, b2, eps, w, step))
+    if pbf is not None:
+        pbf.copy_(p)

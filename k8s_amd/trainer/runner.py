@@ -12,6 +12,8 @@ process exit code (`/root/reference/pkg/trainer/training.go:45-73`):
   overlapped with backward, ``parallel/ddp.py``) or ``ps`` (sharded parameter
   service: reduce-scatter push / owner update / all-gather pull,
   ``parallel/ps.py``);
+* optimizers: fused SGD / Adam, or their layer-wise adaptive forms for large global batches (``--optimizer lars`` /
+  ``lamb``); learning rate: linear warmup, then constant, polynomial or cosine decay (``trainer/schedule.py``);
 * exit codes: 0 success; 1 permanent (bad config, numerics, OOM -- the
   reference treats OOMKilled as permanent); 128+ retryable (collective /
   rendezvous / connection failures, SIGTERM): the operator restarts the
@@ -54,6 +56,7 @@ class RetryableError(RuntimeError):
 
 def parse(argv=None):
     from k8s_amd.models.registry import MODELS
+    from k8s_amd.trainer.schedule import SCHEDULES
 
     ap = argparse.ArgumentParser(prog="python -m k8s_amd.trainer", description="k8s_amd TfJob trainer")
     ap.add_argument("--model", default="resnet50", choices=MODELS)
@@ -61,10 +64,17 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="per-rank batch (default: model preset)")
     ap.add_argument("--seq", type=int, default=None)
     ap.add_argument("--image", type=int, default=None)
-    ap.add_argument("--optimizer", default=None, choices=["sgd", "adam"])
+    ap.add_argument("--optimizer", default=None, choices=["sgd", "adam", "lars", "lamb"],
+                    help="lars / lamb: layer-wise adaptive (per-tensor trust ratio) on momentum SGD / Adam, for "
+                         "large global batches")
+    ap.add_argument("--trust-coef", type=float, default=0.001, help="LARS trust coefficient (eta)")
     ap.add_argument("--lr", type=float, default=None)
     ap.add_argument("--weight-decay", type=float, default=None)
     ap.add_argument("--warmup-steps", type=int, default=0, help="linear LR warmup")
+    ap.add_argument("--lr-schedule", default="constant", choices=list(SCHEDULES),
+                    help="decay from --lr to --lr-end over the steps after the warmup (trainer/schedule.py)")
+    ap.add_argument("--lr-end", type=float, default=0.0, help="learning rate of the last step (poly / cosine)")
+    ap.add_argument("--lr-power", type=float, default=2.0, help="exponent of --lr-schedule poly")
     ap.add_argument("--max-grad-norm", type=float, default=None)
     ap.add_argument("--strategy", default="allreduce", choices=["allreduce", "ps"])
     ap.add_argument("--bucket-mb", type=float, default=64.0)
@@ -297,10 +307,11 @@ def _restore(a, w, opt, dev, chief: bool, world: int, metrics, psv=None, svc=Non
 
 def train(a) -> int:
     from k8s_amd.models.registry import build
-    from k8s_amd.ops.optim import FusedAdam, FusedSGD
+    from k8s_amd.ops.optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD
     from k8s_amd.parallel import dist as kdist
     from k8s_amd.parallel.ddp import GradReducer
     from k8s_amd.parallel.ps import ShardedParameterService
+    from k8s_amd.trainer.schedule import lr_at
     from k8s_amd.utils import checkpoint as ckpt
     from k8s_amd.utils.trace import Tracer, Watchdog
 
@@ -349,19 +360,24 @@ def train(a) -> int:
     metrics = _Metrics(a.logdir, chief)
     metrics.event(event="start", rank=rank, world=world, role=info.role, model=a.model, strategy=a.strategy,
                   device=str(dev), start_time=t_start, process_start_time=t_proc, zero1=bool(sharded and world > 1), grad_comm=comm,
-                  optimizer=opt_name, batch=batch)
+                  optimizer=opt_name, lr_schedule=a.lr_schedule, batch=batch)
 
     # the sharded parameter service needs the flat buffers divisible into world equal 64-aligned shards
     w = build(a.model, dev, batch, seq=a.seq, image=a.image, seed=a.seed, fixed_batch=not a.fresh_batches,
               pad_to=world * ALIGN if sharded else ALIGN, data_seed=a.seed * 7919 + rank,
               mlm_every_token=a.mlm_head == "every-token")
     lr = a.lr if a.lr is not None else w.lr
-    if opt_name == "sgd":
+    if opt_name in ("sgd", "lars"):
         wd = 5e-5 if a.weight_decay is None else a.weight_decay
-        opt = FusedSGD(w.store, lr=lr, momentum=0.9, weight_decay=wd, max_grad_norm=a.max_grad_norm)
+        if opt_name == "sgd":
+            opt = FusedSGD(w.store, lr=lr, momentum=0.9, weight_decay=wd, max_grad_norm=a.max_grad_norm)
+        else:
+            opt = FusedLARS(w.store, lr=lr, momentum=0.9, weight_decay=wd, trust_coef=a.trust_coef,
+                            max_grad_norm=a.max_grad_norm)
     else:
         wd = 0.01 if a.weight_decay is None else a.weight_decay
-        opt = FusedAdam(w.store, lr=lr, weight_decay=wd, max_grad_norm=a.max_grad_norm)
+        cls = FusedAdam if opt_name == "adam" else FusedLAMB
+        opt = cls(w.store, lr=lr, weight_decay=wd, max_grad_norm=a.max_grad_norm)
     if world > 1:  # identical initial weights everywhere
         torch.distributed.broadcast(w.store.master, 0)
         w.store.refresh_lowp()
@@ -517,7 +533,7 @@ def train(a) -> int:
                     raise RetryableError("injected failure at step %d" % step)
             if step == a.hang_at_step:
                 time.sleep(1e9)  # (testing) a stalled collective
-            cur_lr = lr * min(1.0, (step + 1) / a.warmup_steps) if a.warmup_steps else lr
+            cur_lr = lr_at(step, lr, a.warmup_steps, a.steps, a.lr_schedule, a.lr_end, a.lr_power)
             if graph is not None:
                 loss = graph(w.batch(step), cur_lr)
             else:
@@ -555,9 +571,13 @@ def train(a) -> int:
                                   setup_s=round(t_ready - t_start, 4), first_step_s=round(now - t_ready, 4))
                 else:
                     extra = {"phase_ms": tracer.summary_ms()} if tracer.sync else {}
+                    # lars / lamb: the per-tensor trust ratios of the latest step over the decaying slots (identical
+                    # on every rank: they come from the all-reduced sums)
+                    trust = (opt.trust_ratio_stats() if chief and opt_name in ("lars", "lamb") else None) or {}
                     metrics.event(event="step", step=step, loss=loss_v, lr=cur_lr,
-                                  **{"%s_per_sec" % w.unit: round(rate, 2)}, **extra)
-                    metrics.scalars(step, {"loss": loss_v, "%s_per_sec" % w.unit: rate, "learning_rate": cur_lr})
+                                  **{"%s_per_sec" % w.unit: round(rate, 2)}, **extra, **trust)
+                    metrics.scalars(step, {"loss": loss_v, "%s_per_sec" % w.unit: rate, "learning_rate": cur_lr,
+                                           **trust})
                 t_last, n_last = now, 0
             if a.eval_every and ((step + 1) % a.eval_every == 0 or step + 1 == a.steps):
                 t_last += evaluate(step)  # evaluation time is not part of the training throughput window
