@@ -38,12 +38,14 @@
 //   so no fp32 atomics; delta = rowsum(dO * O) is a tiny kernel ahead of both. lse / delta rows are padded
 //   to a multiple of 64 so a query tile's 256 B of each can be staged by one global_load_lds.
 #include <algorithm>
+#include <stdexcept>
 #include <type_traits>
 #include <cstdlib>
 
 #include "common.h"
 #include "launchers.h"
 #include "mfma.h"
+#include "rng.h"
 
 namespace k8s_amd {
 
@@ -108,8 +110,13 @@ __device__ __forceinline__ const uint16_t* kh_src(const uint16_t* base, long rst
 // NB: K/V stage buffers (1: every key in one tile, Sk <= TILE -- the short-sequence form, no second buffer).
 // QS: 16-query sets per wave (2: 128-query blocks. 1 -- 64-query blocks, 110 VGPRs / 4 blocks per CU -- measured
 // slower on BERT s128 b1024: 200 vs 182 us, scripts/gpurun/r5/faqs.sh)
-template <int D, int TILE, int NB = 2, int QS = 2>
-__global__ void __launch_bounds__(FA_THREADS, NB == 1 ? (QS == 1 ? 4 : 3) : 2) flash_fwd_kernel(AttnFwdArgs a) {
+// DROP: dropout on the probabilities (rng.h; row = (b * Hq + h) * Sq + query, col = key). The lane's QS rowkeys are
+// computed once; after the row sum (l keeps the undropped sum) each probability is kept or zeroed on its way into the
+// PV product, and the scale is folded into the epilogue's 1 / l.
+template <int D, int TILE, int NB = 2, int QS = 2, bool DROP = false>
+// (DROP on the one-tile form: 2 blocks per CU -- the mask's integer temporaries beside the 128-key score tile do not
+// fit the 168 registers of 3)
+__global__ void __launch_bounds__(FA_THREADS, NB == 1 && !DROP ? (QS == 1 ? 4 : 3) : 2) flash_fwd_kernel(AttnFwdArgs a) {
   constexpr int BM = 64 * QS;  // queries per block
   constexpr int FA_BN = TILE;  // keys per iteration
   constexpr int NI = FA_BN / 16;       // 16-key subtiles
@@ -154,12 +161,16 @@ __global__ void __launch_bounds__(FA_THREADS, NB == 1 ? (QS == 1 ? 4 : 3) : 2) f
 
   f32x4_t oacc[ND][QS];
   float m[QS], l[QS];
+  uint32_t rk[QS];
 #pragma unroll
   for (int qs = 0; qs < QS; ++qs) {
 #pragma unroll
     for (int i = 0; i < ND; ++i) oacc[i][qs] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     m[qs] = -1e30f;
     l[qs] = 0.f;
+    rk[qs] = 0;
+    if constexpr (DROP)
+      rk[qs] = drop_rowkey(a.drop, (uint64_t)(((long)b * a.Hq + h) * a.Sq + q0w + qs * 16 + li));
   }
 
   // Staging geometry, fixed across tiles: round rd moves K unit s = rd * 256 + tid (tile row, element offset inside
@@ -255,8 +266,11 @@ __global__ void __launch_bounds__(FA_THREADS, NB == 1 ? (QS == 1 ? 4 : 3) : 2) f
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float p = fexp2(fmaf(s[i][qs][r], a.scale_log2, -mn));
-            s[i][qs][r] = p;
             rs += p;
+            if constexpr (DROP)
+              s[i][qs][r] = drop_keep(rk[qs], (uint32_t)(key0 + i * 16 + g * 4 + r), a.drop.thr) ? p : 0.f;
+            else
+              s[i][qs][r] = p;
           }
         l[qs] = l[qs] * alpha + rs;
         // rescale only when some row's running max moved (wave-uniform branch; late key tiles rarely move it)
@@ -312,7 +326,8 @@ __global__ void __launch_bounds__(FA_THREADS, NB == 1 ? (QS == 1 ? 4 : 3) : 2) f
     lt += __shfl_xor(lt, 32, 64);
     const int qi = q0w + qs * 16 + li;
     if (qi >= a.Sq) continue;
-    const float inv = lt > 0.f ? 1.f / lt : 0.f;
+    float inv = lt > 0.f ? 1.f / lt : 0.f;
+    if constexpr (DROP) inv *= a.drop.scale;
 #pragma unroll
     for (int d = 0; d < ND; ++d) {
       bf16x4_t o;
@@ -786,10 +801,15 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
 constexpr int FS_S = 128;   // longest sequence of the one-block form
 constexpr int FS_DSR = 72;  // dS row stride in bf16: 64 keys + 8 pad (row r at bank 36 r: the dQ reads of 16 query rows
                             // x 2 lane groups cover the 64 banks once; the dS writes of 4g-apart rows land 16 banks apart)
+// DROP: the forward's dropout on the probabilities. The rowkeys of the block's queries are computed once in the
+// prologue (128 words behind lse | delta); P~ = keep ? P : 0 feeds dV (the scale folded into its copy-out and column
+// sums), dS = P (scale * keep * dP - delta), and delta = rowsum(dO * O) is unchanged: O carries the dropped, scaled
+// probabilities, so it still equals sum_k P dP'.
+template <bool DROP>
 __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_short_kernel(AttnBwdArgs a, const uint16_t* o, long sob,
                                                                        long sos, long soh) {
   constexpr int NK = 2, ND = 4, TQ = FS_S * 64 * 2;  // Q / dO / K tile bytes (16 KB, one K-major half)
-  __shared__ __attribute__((aligned(1024))) char smem[3 * TQ + FS_S * FS_DSR * 2 + 2 * FS_S * 4];
+  __shared__ __attribute__((aligned(1024))) char smem[3 * TQ + FS_S * FS_DSR * 2 + (DROP ? 3 : 2) * FS_S * 4];
   char* tq = smem;
   char* tdo = smem + TQ;
   char* tk = smem + 2 * TQ;
@@ -818,6 +838,13 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_short_kernel(AttnBwdA
     glds16(kh_src(kp, a.sks, FS_S, 0, a.Sk, s), tk + wb);
   }
   if (tid < FS_S) tl[tid] = tid < a.Sq ? a.lse[((long)b * a.Hq + h) * a.lse_ld + tid] : 0.f;
+  const uint32_t* trk = reinterpret_cast<const uint32_t*>(tl + 2 * FS_S);  // rowkeys [128] (DROP)
+  if constexpr (DROP) {
+    if (tid < FS_S)
+      reinterpret_cast<uint32_t*>(tl + 2 * FS_S)[tid] =
+          drop_rowkey(a.drop, (uint64_t)(((long)b * a.Hq + h) * a.Sq + tid));
+  }
+  const float dscale = DROP ? a.drop.scale : 1.f;
   {
     const int q = tid >> 1, c0 = (tid & 1) * 32;  // two lanes per query, 32 columns each
     float acc = 0.f;
@@ -899,8 +926,14 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_short_kernel(AttnBwdA
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float p = fexp2(sv[qs][r] * a.scale_log2 - l4[r]);
-          sv[qs][r] = p;
-          dp[qs][r] = p * (dp[qs][r] - d4[r]);
+          if constexpr (DROP) {
+            const bool keep = drop_keep(trk[q0 + qs * 16 + g * 4 + r], (uint32_t)key, a.drop.thr);
+            sv[qs][r] = keep ? p : 0.f;
+            dp[qs][r] = p * ((keep ? dp[qs][r] * dscale : 0.f) - d4[r]);
+          } else {
+            sv[qs][r] = p;
+            dp[qs][r] = p * (dp[qs][r] - d4[r]);
+          }
           dsl[(q0 + qs * 16 + g * 4 + r) * FS_DSR + wid_u * 16 + li] = f2bf(dp[qs][r]);
         }
       }
@@ -941,7 +974,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_short_kernel(AttnBwdA
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           x[r] = (short)f2bf(dka[d][r] * a.scale);
-          y[r] = (short)f2bf(dva[d][r]);
+          y[r] = (short)f2bf(DROP ? dva[d][r] * dscale : dva[d][r]);
         }
         *reinterpret_cast<bf16x4_t*>(dkp + d * 16 + g * 4) = x;
         *reinterpret_cast<bf16x4_t*>(dvp + d * 16 + g * 4) = y;
@@ -1010,7 +1043,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_short_kernel(AttnBwdA
           const int c = d * 16 + g * 4 + r;
           red[wid_u * 64 + c] = sq * a.scale;
           red[(4 + wid_u) * 64 + c] = sk * a.scale;
-          red[(8 + wid_u) * 64 + c] = sv;
+          red[(8 + wid_u) * 64 + c] = DROP ? sv * dscale : sv;
         }
       }
     __syncthreads();
@@ -1062,6 +1095,12 @@ static bool fwd_one_tile() {
 void launch_flash_fwd(const AttnFwdArgs& a, int D, hipStream_t st) {
   const int nqb = (a.Sq + FA_BM - 1) / FA_BM;
   const dim3 grid(nqb * a.Hq * a.B), blk(FA_THREADS);
+  if (a.drop.state) {  // the shapes of the one-block backward only (checked by the caller: flash_bwd_one_block)
+    if (D != 64 || a.Sq > FS_S || a.Sk > FS_S) throw std::runtime_error("flash_fwd: dropout needs a one-block shape");
+    if (fwd_one_tile()) hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 1, 2, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((flash_fwd_kernel<64, 64, 2, 2, true>), grid, blk, 0, st, a);
+    return;
+  }
   if (D == 128) hipLaunchKernelGGL((flash_fwd_kernel<128, 64>), grid, blk, 0, st, a);
   else if (big_tile(D, a.Sk)) hipLaunchKernelGGL((flash_fwd_kernel<64, 128>), grid, blk, 0, st, a);
   else if (a.Sk <= 128 && fwd_one_tile()) hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 1>), grid, blk, 0, st, a);
@@ -1071,11 +1110,17 @@ void launch_flash_fwd(const AttnFwdArgs& a, int D, hipStream_t st) {
 void launch_flash_bwd(const AttnBwdArgs& a, int D, const uint16_t* o, long sob, long sos, long soh,
                       hipStream_t st) {
   if (flash_bwd_one_block(D, a.Sq, a.Sk, a.Hq, a.Hkv, a.dkv_split)) {
-    if ((long)a.B * a.Hq > 0)
-      hipLaunchKernelGGL(flash_bwd_short_kernel, dim3((unsigned)(a.B * a.Hq)), dim3(FA_THREADS), 0, st, a, o, sob,
-                         sos, soh);
+    if ((long)a.B * a.Hq > 0) {
+      if (a.drop.state)
+        hipLaunchKernelGGL(flash_bwd_short_kernel<true>, dim3((unsigned)(a.B * a.Hq)), dim3(FA_THREADS), 0, st, a, o,
+                           sob, sos, soh);
+      else
+        hipLaunchKernelGGL(flash_bwd_short_kernel<false>, dim3((unsigned)(a.B * a.Hq)), dim3(FA_THREADS), 0, st, a, o,
+                           sob, sos, soh);
+    }
     return;
   }
+  if (a.drop.state) throw std::runtime_error("flash_bwd: dropout needs a one-block shape");
   const long R = (long)a.B * a.Sq * a.Hq;
   const int lpr = D / 8;
   const dim3 dgrid((unsigned)((R * lpr + 255) / 256));

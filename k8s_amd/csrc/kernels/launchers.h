@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rng.h"
+
 namespace k8s_amd {
 
 // planner.hip: the CU count every launch planner sizes its grid for (see common.h)
@@ -89,11 +91,20 @@ void launch_relu_mask(const uint16_t* y, uint8_t* mask, long nvec, hipStream_t s
 // norm.hip
 void launch_norm_fwd(bool rms, const uint16_t* x, const uint16_t* res, uint16_t* xsum, const float* gamma,
                      const float* beta, uint16_t* y, float* mean, float* rstd, long R, int D, float eps,
-                     hipStream_t st);
+                     hipStream_t st, const DropArgs* drop = nullptr);
 int norm_workspace_floats(long R, int D);
 void launch_norm_bwd(bool rms, const uint16_t* dy, const uint16_t* x, const float* gamma, const float* mean,
                      const float* rstd, const uint16_t* dres, uint16_t* dx, float* dgamma, float* dbeta, float* work,
-                     long R, int D, hipStream_t st, float* dsum = nullptr);
+                     long R, int D, hipStream_t st, float* dsum = nullptr, const DropArgs* drop = nullptr,
+                     uint16_t* da = nullptr);
+// drop (LayerNorm with a residual only): the first summand passes through dropout before the add,
+//   xsum = bf16(keep * scale * x + res); the backward also writes da = keep * scale * dx (the gradient of x; dx itself
+//   is the residual's), and dsum becomes the column sums of da.
+
+// dropout.hip: y = keep ? bf16(x * scale) : 0 over [R, D] bf16 (D % 8 == 0); the keep bits of rows row0 .. row0 + R - 1,
+// columns 0 .. C - 1 as uint8 (rng.h)
+void launch_dropout(const uint16_t* x, uint16_t* y, long R, int D, const DropArgs& dr, hipStream_t st);
+void launch_dropout_mask(uint8_t* out, long row0, long R, int C, const DropArgs& dr, hipStream_t st);
 
 // xent.hip
 void launch_xent_fwd(const void* logits, bool bf16, const int64_t* labels, long R, long V, long ld, float* loss,
@@ -269,6 +280,8 @@ struct AttnFwdArgs {
   long lse_ld;         // row stride of lse (Sq rounded up to 64)
   int B, Sq, Sk, Hq, Hkv, causal;
   float scale_log2;
+  // dropout on the probabilities (one-block shapes only, flash_bwd_one_block): row = (b * Hq + h) * Sq + q, col = key
+  DropArgs drop;
 };
 struct AttnBwdArgs {
   const uint16_t *q, *k, *v, *dO;
@@ -290,6 +303,7 @@ struct AttnBwdArgs {
   // fp32 [B][cpart_ld] (the projection's bias gradient once folded over B)
   float* cpart = nullptr;
   int cpart_ld = 0;
+  DropArgs drop;  // as the forward's
 };
 int flash_dkv_splits(int B, int Sq, int Sk, int Hkv, int causal);
 // the whole backward of one (batch, head) in one block (flash_bwd_short_kernel) applies to this shape

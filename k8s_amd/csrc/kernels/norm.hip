@@ -18,21 +18,26 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "rng.h"
 
 namespace k8s_amd {
 
 constexpr int NORM_WAVES = 4;
 
-template <int CPL, bool RMS>
+// DROP (with res): the first summand passes through dropout on its way into the add, xsum = keep * scale * x + res
+// (rng.h; one wave-uniform rowkey per row, the mask applied to the values already in registers).
+template <int CPL, bool RMS, bool DROP = false>
 __global__ void __launch_bounds__(256) norm_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ res,
                                                        uint16_t* __restrict__ xsum, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, uint16_t* __restrict__ y,
                                                        float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                       long R, int D, float eps) {
+                                                       long R, int D, float eps, DropArgs dr) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * NORM_WAVES + (threadIdx.x >> 6);
   if (row >= R) return;
   const int nch = D / 8;
+  uint32_t rk = 0;
+  if constexpr (DROP) rk = drop_rowkey(dr, (uint64_t)row);
   float v[CPL][8];
   // the affine parameters are loaded with the row (in flight together) rather than after the two reductions,
   // where they were a dependent L2 round trip at the end of every wave (one wave per row = a single round of waves);
@@ -60,7 +65,10 @@ __global__ void __launch_bounds__(256) norm_fwd_kernel(const uint16_t* __restric
         float r[8];
         load8(res + row * D + ch * 8, r);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[c][j] += r[j];
+        for (int j = 0; j < 8; ++j) {
+          if constexpr (DROP) v[c][j] = drop_keep(rk, (uint32_t)(ch * 8 + j), dr.thr) ? v[c][j] * dr.scale : 0.f;
+          v[c][j] += r[j];
+        }
         store8(xsum + row * D + ch * 8, v[c]);
       }
 #pragma unroll
@@ -116,7 +124,9 @@ __global__ void __launch_bounds__(256) norm_fwd_kernel(const uint16_t* __restric
 //    registers as raw bf16 across both passes -> every row in flight at once;
 //  * norm_bwd_param_kernel: dgamma / dbeta column partials over 64-row blocks (8 columns per thread, 4 rows per
 //    trip, mean / rstd broadcast per row), folded by norm_colsum_kernel.
-template <int CPL, bool RMS>
+// DROP (all three backward kernels): also da = keep * scale * dx, the gradient of the dropped summand, written by the
+// pass that forms dx; the dx column sums (BiasLink) become those of da.
+template <int CPL, bool RMS, bool DROP = false>
 __global__ void __launch_bounds__(256) norm_bwd_dx_kernel(const uint16_t* __restrict__ dy,
                                                           const uint16_t* __restrict__ x,
                                                           const float* __restrict__ gamma,
@@ -124,11 +134,13 @@ __global__ void __launch_bounds__(256) norm_bwd_dx_kernel(const uint16_t* __rest
                                                           const float* __restrict__ rstd,
                                                           const uint16_t* __restrict__ dres,
                                                           uint16_t* __restrict__ dx, float* __restrict__ rowab, long R,
-                                                          int D) {
+                                                          int D, DropArgs dr, uint16_t* __restrict__ da) {
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * NORM_WAVES + (threadIdx.x >> 6);
   if (row >= R) return;
   const int nch = D / 8;
+  uint32_t rk = 0;
+  if constexpr (DROP) rk = drop_rowkey(dr, (uint64_t)row);
   bf16x8_t gr[CPL], xr[CPL], rr[CPL];
 #pragma unroll
   for (int c = 0; c < CPL; ++c) {
@@ -175,6 +187,11 @@ __global__ void __launch_bounds__(256) norm_bwd_dx_kernel(const uint16_t* __rest
         for (int j = 0; j < 8; ++j) o[j] += bf2f((uint16_t)rr[c][j]);
       }
       store8(dx + row * D + ch * 8, o);
+      if constexpr (DROP) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = drop_keep(rk, (uint32_t)(ch * 8 + j), dr.thr) ? o[j] * dr.scale : 0.f;
+        store8(da + row * D + ch * 8, o);
+      }
     }
   }
 }
@@ -192,14 +209,15 @@ static int norm_param_rows(long R) {
 // chunks (256 columns) x 8 row groups, LDS combine of the row groups
 // With rowab (the dx kernel's per-row a, b): also part[..][2][k] = sum dx, dx recomputed from dy, x and the row
 // coefficients -- the bias gradient of the linear whose output this norm read (no separate column-sum pass).
-template <bool RMS>
+template <bool RMS, bool DROP = false>
 __global__ void __launch_bounds__(256) norm_bwd_param_kernel(const uint16_t* __restrict__ dy,
                                                              const uint16_t* __restrict__ x,
                                                              const float* __restrict__ mean,
                                                              const float* __restrict__ rstd,
                                                              const float* __restrict__ rowab,
                                                              const float* __restrict__ gamma,
-                                                             float* __restrict__ part, long R, int D, int prows) {
+                                                             float* __restrict__ part, long R, int D, int prows,
+                                                             DropArgs dr) {
   const int nch = D / 8;
   const int ch = blockIdx.y * 32 + (threadIdx.x & 31), rg = threadIdx.x >> 5;
   float pg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pb[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -235,9 +253,18 @@ __global__ void __launch_bounds__(256) norm_bwd_param_kernel(const uint16_t* __r
         for (int u = 0; u < 4; ++u) {
           const long rr = r + 8 * u < r1 ? r + 8 * u : r1 - 1;
           const float ra = RMS ? 0.f : rowab[2 * rr], rb = rowab[2 * rr + 1];
+          if constexpr (DROP) {  // sum da = sum keep * scale * dx
+            const uint32_t rk = drop_rowkey(dr, (uint64_t)rr);
 #pragma unroll
-          for (int j = 0; j < 8; ++j)
-            pd[j] += rs[u] * (g[u][j] * gm[j] - ra - (xv[u][j] - mu[u]) * rs[u] * rb);
+            for (int j = 0; j < 8; ++j) {
+              const float dxv = rs[u] * (g[u][j] * gm[j] - ra - (xv[u][j] - mu[u]) * rs[u] * rb);
+              pd[j] += drop_keep(rk, (uint32_t)(ch * 8 + j), dr.thr) ? dxv * dr.scale : 0.f;
+            }
+          } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              pd[j] += rs[u] * (g[u][j] * gm[j] - ra - (xv[u][j] - mu[u]) * rs[u] * rb);
+          }
         }
       }
     }
@@ -329,7 +356,7 @@ __global__ void __launch_bounds__(256) norm_colsum_kernel(const float* __restric
 // NS: register slots of the row prefetch (2: the next row's loads in flight during this row's math; 3: two rows ahead,
 // no residual gradient operand -- its slots would push D = 768 past 256 VGPRs)
 constexpr int NORM_FUSED_RPW = 32;
-template <int CPL, bool RMS, int NS = 2>
+template <int CPL, bool RMS, int NS = 2, bool DROP = false>
 __global__ void __launch_bounds__(256) norm_bwd_fused_kernel(const uint16_t* __restrict__ dy,
                                                              const uint16_t* __restrict__ x,
                                                              const float* __restrict__ gamma,
@@ -337,7 +364,8 @@ __global__ void __launch_bounds__(256) norm_bwd_fused_kernel(const uint16_t* __r
                                                              const float* __restrict__ rstd,
                                                              const uint16_t* __restrict__ dres,
                                                              uint16_t* __restrict__ dx, float* __restrict__ part,
-                                                             long R, int D, int want_dsum) {
+                                                             long R, int D, int want_dsum, DropArgs dr,
+                                                             uint16_t* __restrict__ da) {
   static_assert(CPL <= 2, "short rows only");
   constexpr int RPW = NORM_FUSED_RPW;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -386,6 +414,8 @@ __global__ void __launch_bounds__(256) norm_bwd_fused_kernel(const uint16_t* __r
     }
     a = wave_sum(a) / D;
     b = wave_sum(b) / D;
+    uint32_t rk = 0;
+    if constexpr (DROP) rk = drop_rowkey(dr, (uint64_t)row);
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
       const int ch = lane + c * 64;
@@ -398,7 +428,7 @@ __global__ void __launch_bounds__(256) norm_bwd_fused_kernel(const uint16_t* __r
           o[j] = rs * (g * gm[c][j] - (RMS ? 0.f : a) - xn * b);
           pg[c][j] += g * xn;
           pb[c][j] += g;
-          pd[c][j] += o[j];
+          if constexpr (!DROP) pd[c][j] += o[j];
         }
         if constexpr (NS == 2) {
           if (dres) {
@@ -407,6 +437,14 @@ __global__ void __launch_bounds__(256) norm_bwd_fused_kernel(const uint16_t* __r
           }
         }
         store8(dx + row * D + ch * 8, o);
+        if constexpr (DROP) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            o[j] = drop_keep(rk, (uint32_t)(ch * 8 + j), dr.thr) ? o[j] * dr.scale : 0.f;
+            pd[c][j] += o[j];
+          }
+          store8(da + row * D + ch * 8, o);
+        }
       }
     }
   };
@@ -459,11 +497,11 @@ __global__ void __launch_bounds__(256) norm_bwd_fused_kernel(const uint16_t* __r
   }
 }
 
-template <bool RMS>
+template <bool RMS, bool DROP>
 static void norm_fwd_dispatch(int cpl, dim3 g, hipStream_t st, const uint16_t* x, const uint16_t* res,
                               uint16_t* xsum, const float* gamma, const float* beta, uint16_t* y, float* mean,
-                              float* rstd, long R, int D, float eps) {
-#define NF(C) hipLaunchKernelGGL((norm_fwd_kernel<C, RMS>), g, dim3(256), 0, st, x, res, xsum, gamma, beta, y, mean, rstd, R, D, eps)
+                              float* rstd, long R, int D, float eps, const DropArgs& dr) {
+#define NF(C) hipLaunchKernelGGL((norm_fwd_kernel<C, RMS, DROP>), g, dim3(256), 0, st, x, res, xsum, gamma, beta, y, mean, rstd, R, D, eps, dr)
   switch (cpl) {
     case 1: NF(1); break;
     case 2: NF(2); break;
@@ -481,13 +519,17 @@ static int norm_cpl(int D) {
 
 void launch_norm_fwd(bool rms, const uint16_t* x, const uint16_t* res, uint16_t* xsum, const float* gamma,
                      const float* beta, uint16_t* y, float* mean, float* rstd, long R, int D, float eps,
-                     hipStream_t st) {
+                     hipStream_t st, const DropArgs* drop) {
   dim3 g(cdiv(R, NORM_WAVES));
   const int cpl = norm_cpl(D);
-  if (rms)
-    norm_fwd_dispatch<true>(cpl, g, st, x, res, xsum, gamma, beta, y, mean, rstd, R, D, eps);
-  else
-    norm_fwd_dispatch<false>(cpl, g, st, x, res, xsum, gamma, beta, y, mean, rstd, R, D, eps);
+  if (drop) {
+    if (rms || !res) throw std::runtime_error("norm_fwd: dropout needs LayerNorm with a residual");
+    norm_fwd_dispatch<false, true>(cpl, g, st, x, res, xsum, gamma, beta, y, mean, rstd, R, D, eps, *drop);
+  } else if (rms) {
+    norm_fwd_dispatch<true, false>(cpl, g, st, x, res, xsum, gamma, beta, y, mean, rstd, R, D, eps, DropArgs{});
+  } else {
+    norm_fwd_dispatch<false, false>(cpl, g, st, x, res, xsum, gamma, beta, y, mean, rstd, R, D, eps, DropArgs{});
+  }
 }
 
 static int norm_param_blocks(long R) { return (int)((R + norm_param_rows(R) - 1) / norm_param_rows(R)); }
@@ -505,8 +547,10 @@ int norm_workspace_floats(long R, int D) {
 
 void launch_norm_bwd(bool rms, const uint16_t* dy, const uint16_t* x, const float* gamma, const float* mean,
                      const float* rstd, const uint16_t* dres, uint16_t* dx, float* dgamma, float* dbeta, float* work,
-                     long R, int D, hipStream_t st, float* dsum) {
+                     long R, int D, hipStream_t st, float* dsum, const DropArgs* drop, uint16_t* da) {
   if (dsum && dres) throw std::runtime_error("norm_bwd: the dx column sums exclude a residual gradient");
+  if (drop && (rms || !da)) throw std::runtime_error("norm_bwd: dropout needs LayerNorm and the da output");
+  const DropArgs dr = drop ? *drop : DropArgs{};
   const int cpl = norm_cpl(D);
   if (norm_fused_ok(R, D)) {
     const int nbf = norm_fused_blocks(R);
@@ -514,17 +558,17 @@ void launch_norm_bwd(bool rms, const uint16_t* dy, const uint16_t* x, const floa
       const char* e = std::getenv("K8S_AMD_NORM_PREFETCH");
       return !(e && e[0] == '2');
     }();
-#define NBF(C, RM)                                                                                                    \
-  if (deep && !dres)                                                                                                  \
-    hipLaunchKernelGGL((norm_bwd_fused_kernel<C, RM, 3>), dim3(nbf), dim3(256), 0, st, dy, x, gamma, mean, rstd, dres, \
-                       dx, work, R, D, dsum ? 1 : 0);                                                                 \
-  else                                                                                                                \
-    hipLaunchKernelGGL((norm_bwd_fused_kernel<C, RM, 2>), dim3(nbf), dim3(256), 0, st, dy, x, gamma, mean, rstd, dres, \
-                       dx, work, R, D, dsum ? 1 : 0)
+#define NBF(C, RM, DR)                                                                                             \
+  if (deep && !dres)                                                                                               \
+    hipLaunchKernelGGL((norm_bwd_fused_kernel<C, RM, 3, DR>), dim3(nbf), dim3(256), 0, st, dy, x, gamma, mean, rstd, \
+                       dres, dx, work, R, D, dsum ? 1 : 0, dr, da);                                                \
+  else                                                                                                             \
+    hipLaunchKernelGGL((norm_bwd_fused_kernel<C, RM, 2, DR>), dim3(nbf), dim3(256), 0, st, dy, x, gamma, mean, rstd, \
+                       dres, dx, work, R, D, dsum ? 1 : 0, dr, da)
     if (cpl == 1) {
-      if (rms) NBF(1, true); else NBF(1, false);
+      if (drop) NBF(1, false, true); else if (rms) NBF(1, true, false); else NBF(1, false, false);
     } else {
-      if (rms) NBF(2, true); else NBF(2, false);
+      if (drop) NBF(2, false, true); else if (rms) NBF(2, true, false); else NBF(2, false, false);
     }
 #undef NBF
     // 1,024 partial rows at BERT b1024: folded in groups of 32 first (24 blocks walking them took 20 us a call)
@@ -542,13 +586,16 @@ void launch_norm_bwd(bool rms, const uint16_t* dy, const uint16_t* x, const floa
   const dim3 g(cdiv(R, NORM_WAVES));
   const int nb = norm_param_blocks(R);
   float* const rowab = dsum ? work + (long)nb * 3 * D : nullptr;
-#define NB(C)                                                                                                     \
-  if (rms)                                                                                                        \
-    hipLaunchKernelGGL((norm_bwd_dx_kernel<C, true>), g, dim3(256), 0, st, dy, x, gamma, mean, rstd, dres, dx, \
-                       rowab, R, D);                                                                             \
-  else                                                                                                            \
-    hipLaunchKernelGGL((norm_bwd_dx_kernel<C, false>), g, dim3(256), 0, st, dy, x, gamma, mean, rstd, dres, dx, \
-                       rowab, R, D);
+#define NB(C)                                                                                                          \
+  if (drop)                                                                                                            \
+    hipLaunchKernelGGL((norm_bwd_dx_kernel<C, false, true>), g, dim3(256), 0, st, dy, x, gamma, mean, rstd, dres, dx,  \
+                       rowab, R, D, dr, da);                                                                           \
+  else if (rms)                                                                                                        \
+    hipLaunchKernelGGL((norm_bwd_dx_kernel<C, true>), g, dim3(256), 0, st, dy, x, gamma, mean, rstd, dres, dx, rowab,  \
+                       R, D, dr, da);                                                                                  \
+  else                                                                                                                 \
+    hipLaunchKernelGGL((norm_bwd_dx_kernel<C, false>), g, dim3(256), 0, st, dy, x, gamma, mean, rstd, dres, dx, rowab, \
+                       R, D, dr, da);
   switch (cpl) {
     case 1: NB(1); break;
     case 2: NB(2); break;
@@ -558,12 +605,15 @@ void launch_norm_bwd(bool rms, const uint16_t* dy, const uint16_t* x, const floa
   }
 #undef NB
   const dim3 gp(nb, cdiv(D / 8, 32));
-  if (rms)
+  if (drop)
+    hipLaunchKernelGGL((norm_bwd_param_kernel<false, true>), gp, dim3(256), 0, st, dy, x, mean, rstd, rowab, gamma,
+                       work, R, D, norm_param_rows(R), dr);
+  else if (rms)
     hipLaunchKernelGGL(norm_bwd_param_kernel<true>, gp, dim3(256), 0, st, dy, x, mean, rstd, rowab, gamma, work, R,
-                       D, norm_param_rows(R));
+                       D, norm_param_rows(R), dr);
   else
     hipLaunchKernelGGL(norm_bwd_param_kernel<false>, gp, dim3(256), 0, st, dy, x, mean, rstd, rowab, gamma, work, R,
-                       D, norm_param_rows(R));
+                       D, norm_param_rows(R), dr);
   hipLaunchKernelGGL(norm_colsum_kernel, dim3(cdiv(D, 32)), dim3(256), 0, st, work, nb, D, dgamma,
                      rms ? nullptr : dbeta, dsum);
 }

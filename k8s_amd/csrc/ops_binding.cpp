@@ -523,10 +523,51 @@ std::vector<Tensor> bn_bwd_dual(Tensor dy, Tensor mask, Tensor x, Tensor mean, T
   return {dx, dx2};
 }
 
-// ------------------------------------------------------------------ layernorm / rmsnorm
-std::vector<Tensor> norm_fwd(Tensor x, c10::optional<Tensor> res, Tensor gamma, c10::optional<Tensor> beta, double eps,
-                             bool rms) {
+// ------------------------------------------------------------------ dropout (rng.h)
+// state: device int64 [seed, step], read by the kernels themselves (never by the host); thr / scale: the keep threshold
+// and 1 / (1 - thr / 2^32) (ops/reference.py drop_params); site: the call site's small integer
+k8s_amd::DropArgs drop_args(const Tensor& state, int64_t thr, double scale, int64_t site) {
+  check_cuda(state, "dropout state"); check_dtype(state, at::kLong, "dropout state");
+  TORCH_CHECK(state.numel() >= 2, "dropout state must be an int64 [seed, step] tensor");
+  TORCH_CHECK(thr > 0 && thr <= 0xffffffffLL, "dropout threshold out of range (p must be in (0, 1))");
+  TORCH_CHECK(site >= 0 && site <= 0x7fffffffLL, "dropout site out of range");
+  k8s_amd::DropArgs d;
+  d.state = state.data_ptr<int64_t>();
+  d.thr = (uint32_t)thr;
+  d.scale = (float)scale;
+  d.site = (int)site;
+  return d;
+}
+
+Tensor dropout(Tensor x, Tensor state, int64_t thr, double scale, int64_t site) {
   check_cuda(x, "x"); check_dtype(x, at::kBFloat16, "x"); check_aligned(x, "x");
+  TORCH_CHECK(x.dim() >= 1 && x.size(-1) % 8 == 0, "dropout row length must be a multiple of 8");
+  const int D = (int)x.size(-1);
+  auto y = torch::empty_like(x);
+  if (x.numel())
+    k8s_amd::launch_dropout(cbf(x), bf(y), x.numel() / D, D, drop_args(state, thr, scale, site), cur_stream());
+  return y;
+}
+
+Tensor dropout_mask(Tensor state, int64_t thr, int64_t site, int64_t row0, int64_t R, int64_t C) {
+  TORCH_CHECK(R >= 0 && C >= 0 && C <= 0x7fffffffLL && row0 >= 0, "bad mask shape");
+  auto out = torch::empty({R, C}, state.options().dtype(at::kByte));
+  k8s_amd::launch_dropout_mask(out.data_ptr<uint8_t>(), row0, R, (int)C, drop_args(state, thr, 1.0, site),
+                               cur_stream());
+  return out;
+}
+
+// ------------------------------------------------------------------ layernorm / rmsnorm
+// drop_state (optional, with res, LayerNorm only): xsum = bf16(keep * scale * x + res), see launch_norm_bwd
+std::vector<Tensor> norm_fwd(Tensor x, c10::optional<Tensor> res, Tensor gamma, c10::optional<Tensor> beta, double eps,
+                             bool rms, c10::optional<Tensor> drop_state, int64_t drop_thr, double drop_scale,
+                             int64_t drop_site) {
+  check_cuda(x, "x"); check_dtype(x, at::kBFloat16, "x"); check_aligned(x, "x");
+  k8s_amd::DropArgs dr;
+  if (drop_state) {
+    TORCH_CHECK(res.has_value() && !rms, "dropout in norm_fwd needs LayerNorm with a residual");
+    dr = drop_args(*drop_state, drop_thr, drop_scale, drop_site);
+  }
   const int D = (int)x.size(-1);
   TORCH_CHECK(D % 8 == 0 && D <= 8192, "norm row length must be a multiple of 8 and <= 8192");
   const long R = x.numel() / D;
@@ -539,14 +580,17 @@ std::vector<Tensor> norm_fwd(Tensor x, c10::optional<Tensor> res, Tensor gamma, 
   auto rstd = torch::empty({R}, gamma.options());
   k8s_amd::launch_norm_fwd(rms, cbf(x), res ? cbf(*res) : nullptr, res ? bf(xsum) : nullptr, f32(gamma),
                            beta ? beta->data_ptr<float>() : nullptr, bf(y), f32(mean), f32(rstd), R, D, (float)eps,
-                           cur_stream());
+                           cur_stream(), drop_state ? &dr : nullptr);
   return {y, mean, rstd, xsum};
 }
 
 // dsum (optional, fp32 [D]): also the column sums of dx -- the bias gradient of the linear that produced x's
 // first summand (no residual gradient allowed)
-Tensor norm_bwd(Tensor dy, Tensor x, Tensor gamma, Tensor mean, Tensor rstd, c10::optional<Tensor> dres,
-                Tensor dgamma, c10::optional<Tensor> dbeta, bool rms, c10::optional<Tensor> dsum) {
+// drop: the forward's dropout arguments; `da` then receives keep * scale * dx (the gradient of the dropped summand,
+// while the returned dx is the residual's) and dsum holds the column sums of da
+Tensor norm_bwd_impl(Tensor dy, Tensor x, Tensor gamma, Tensor mean, Tensor rstd, c10::optional<Tensor> dres,
+                     Tensor dgamma, c10::optional<Tensor> dbeta, bool rms, c10::optional<Tensor> dsum,
+                     const k8s_amd::DropArgs* drop, Tensor* da) {
   check_cuda(dy, "dy"); check_cuda(x, "x");
   check_dtype(dy, at::kBFloat16, "dy");
   TORCH_CHECK(dy.sizes() == x.sizes());
@@ -561,8 +605,25 @@ Tensor norm_bwd(Tensor dy, Tensor x, Tensor gamma, Tensor mean, Tensor rstd, c10
   auto work = torch::empty({k8s_amd::norm_workspace_floats(R, D)}, gamma.options());
   k8s_amd::launch_norm_bwd(rms, cbf(dy), cbf(x), f32(gamma), f32(mean), f32(rstd), dres ? cbf(*dres) : nullptr,
                            bf(dx), f32(dgamma), dbeta ? dbeta->data_ptr<float>() : nullptr, f32(work), R, D,
-                           cur_stream(), dsum ? dsum->data_ptr<float>() : nullptr);
+                           cur_stream(), dsum ? dsum->data_ptr<float>() : nullptr, drop, da ? bf(*da) : nullptr);
   return dx;
+}
+
+Tensor norm_bwd(Tensor dy, Tensor x, Tensor gamma, Tensor mean, Tensor rstd, c10::optional<Tensor> dres,
+                Tensor dgamma, c10::optional<Tensor> dbeta, bool rms, c10::optional<Tensor> dsum) {
+  return norm_bwd_impl(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, rms, dsum, nullptr, nullptr);
+}
+
+// (dx, da) of a LayerNorm whose forward ran with dropout on its first summand
+std::vector<Tensor> norm_bwd_dropout(Tensor dy, Tensor x, Tensor gamma, Tensor mean, Tensor rstd,
+                                     c10::optional<Tensor> dres, Tensor dgamma, Tensor dbeta,
+                                     c10::optional<Tensor> dsum, Tensor drop_state, int64_t drop_thr,
+                                     double drop_scale, int64_t drop_site) {
+  const k8s_amd::DropArgs dr = drop_args(drop_state, drop_thr, drop_scale, drop_site);
+  check_dtype(x, at::kBFloat16, "x");
+  auto da = torch::empty_like(x);
+  auto dx = norm_bwd_impl(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, false, dsum, &dr, &da);
+  return {dx, da};
 }
 
 // ------------------------------------------------------------------ cross entropy
@@ -1422,8 +1483,10 @@ const int* kv_lens_ptr(const c10::optional<Tensor>& kv_lens, long B) {
   return kv_lens->data_ptr<int>();
 }
 
+// drop_state (optional): dropout on the probabilities, one-block shapes only (flash_bwd_one_block, D = 64)
 std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, bool causal, c10::optional<Tensor> kv_lens,
-                              double scale) {
+                              double scale, c10::optional<Tensor> drop_state, int64_t drop_thr, double drop_scale,
+                              int64_t drop_site) {
   const long D = q.size(-1);
   TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
   check_attn_operand(q, "q", D); check_attn_operand(k, "k", D); check_attn_operand(v, "v", D);
@@ -1443,6 +1506,11 @@ std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, bool causal, c10::op
   a.lse_ld = ld;
   a.B = B; a.Sq = Sq; a.Sk = Sk; a.Hq = Hq; a.Hkv = Hkv; a.causal = causal;
   a.scale_log2 = (float)(scale * 1.4426950408889634);
+  if (drop_state) {
+    TORCH_CHECK(k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, 1),
+                "attention dropout needs a one-block shape (flash_bwd_one_block)");
+    a.drop = drop_args(*drop_state, drop_thr, drop_scale, drop_site);
+  }
   k8s_amd::launch_flash_fwd(a, (int)D, cur_stream());
   return {o, lse};
 }
@@ -1452,7 +1520,8 @@ std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, bool causal, c10::op
 // (Hq + Hkv)*D): the fused projection's gradient is written in place, no concatenation afterwards.
 std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal,
                               c10::optional<Tensor> kv_lens, double scale, c10::optional<Tensor> dqkv,
-                              c10::optional<Tensor> dbias) {
+                              c10::optional<Tensor> dbias, c10::optional<Tensor> drop_state, int64_t drop_thr,
+                              double drop_scale, int64_t drop_site) {
   const long D = q.size(-1);
   TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
   check_attn_operand(q, "q", D); check_attn_operand(k, "k", D); check_attn_operand(v, "v", D);
@@ -1511,6 +1580,11 @@ std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o,
     cpart = torch::empty({B, W}, q.options().dtype(at::kFloat));
     a.cpart = f32(cpart);
     a.cpart_ld = (int)W;
+  }
+  if (drop_state) {
+    TORCH_CHECK(k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, a.dkv_split),
+                "attention dropout needs a one-block shape (flash_bwd_one_block)");
+    a.drop = drop_args(*drop_state, drop_thr, drop_scale, drop_site);
   }
   k8s_amd::launch_flash_bwd(a, (int)D, cbf(o), o.stride(0), o.stride(1), o.stride(2), cur_stream());
   if (dbias) k8s_amd::launch_colsum_fold(a.cpart, (int)B, a.cpart_ld, f32(*dbias), false, cur_stream());
@@ -1711,7 +1785,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_fwd_from_sums", &bn_fwd_from_sums, py::arg("x"), py::arg("res"), py::arg("gamma"), py::arg("beta"),
         py::arg("sums"), py::arg("run_mean"), py::arg("run_var"), py::arg("momentum"), py::arg("eps"),
         py::arg("relu"), py::arg("want_mask") = false, py::arg("want_sub2") = false);
-  m.def("norm_fwd", &norm_fwd);
+  m.def("dropout", &dropout, py::arg("x"), py::arg("state"), py::arg("thr"), py::arg("scale"), py::arg("site"));
+  m.def("dropout_mask", &dropout_mask, py::arg("state"), py::arg("thr"), py::arg("site"), py::arg("row0"),
+        py::arg("rows"), py::arg("cols"));
+  m.def("norm_fwd", &norm_fwd, py::arg("x"), py::arg("res"), py::arg("gamma"), py::arg("beta"), py::arg("eps"),
+        py::arg("rms"), py::arg("drop_state") = py::none(), py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0, py::arg("drop_site") = 0);
+  m.def("norm_bwd_dropout", &norm_bwd_dropout, py::arg("dy"), py::arg("x"), py::arg("gamma"), py::arg("mean"),
+        py::arg("rstd"), py::arg("dres"), py::arg("dgamma"), py::arg("dbeta"), py::arg("dsum"), py::arg("drop_state"),
+        py::arg("drop_thr"), py::arg("drop_scale"), py::arg("drop_site"));
   m.def("norm_bwd", &norm_bwd, py::arg("dy"), py::arg("x"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
         py::arg("dres"), py::arg("dgamma"), py::arg("dbeta"), py::arg("rms"), py::arg("dsum") = py::none());
   m.def("xent_fwd", &xent_fwd);
@@ -1791,7 +1873,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bn_invstd") = py::none());
   m.def("conv_dgrad_wtrans", &conv_dgrad_wtrans);
   m.def("conv_dgrad_wsub", &conv_dgrad_wsub);
-  m.def("flash_fwd", &flash_fwd);
+  m.def("flash_fwd", &flash_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"), py::arg("kv_lens"),
+        py::arg("scale"), py::arg("drop_state") = py::none(), py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0, py::arg("drop_site") = 0);
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("bn_relu_maxpool", &bn_relu_maxpool, py::arg("x"), py::arg("sums"), py::arg("gamma"), py::arg("beta"),
         py::arg("run_mean"), py::arg("run_var"), py::arg("momentum"), py::arg("eps"), py::arg("want_link") = false);
@@ -1815,7 +1899,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool_bwd", &maxpool_bwd);
   m.def("flash_bwd", &flash_bwd, py::arg("dO"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),
         py::arg("lse"), py::arg("causal"), py::arg("kv_lens"), py::arg("scale"), py::arg("dqkv") = py::none(),
-        py::arg("dbias") = py::none());
+        py::arg("dbias") = py::none(), py::arg("drop_state") = py::none(), py::arg("drop_thr") = 0,
+        py::arg("drop_scale") = 1.0, py::arg("drop_site") = 0);
   m.def("flash_bwd_one_block", [](int64_t D, int64_t Sq, int64_t Sk, int64_t Hq, int64_t Hkv, bool causal, int64_t B) {
           return k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv,
                                               k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal));

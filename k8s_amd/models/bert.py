@@ -11,6 +11,13 @@ counts the two uses, ``Param.uses = 2``).
 Per layer the hot path is: fused QKV GEMM -> flash attention (key-padding
 mask) -> O GEMM (+bias) -> add & LayerNorm fused kernel -> FFN1 GEMM with
 bias+GELU epilogue -> FFN2 GEMM (+bias) -> add & LayerNorm.
+
+Dropout (``hidden_dropout`` after the embeddings' LayerNorm, the attention
+output projection and FFN2; ``attention_dropout`` on the softmax
+probabilities; both 0.1 in the original recipe, off by default here) runs
+inside those kernels on a counter generator (``ops.nn.DropoutState``): no mask
+is stored. Sites: 0 the embeddings; layer i uses 1 + 3i (attention
+probabilities), 2 + 3i (after O) and 3 + 3i (after FFN2).
 """
 from __future__ import annotations
 
@@ -45,6 +52,10 @@ class BertConfig:
     # (the loss masks the padded logits: cross_entropy(valid=vocab_size))
     vocab_pad: int = 256
 
+    # dropout probabilities of the training-mode forward (the original recipe uses 0.1 for both)
+    hidden_dropout: float = 0.0
+    attention_dropout: float = 0.0
+
     @property
     def padded_vocab(self) -> int:
         return (self.vocab_size + self.vocab_pad - 1) // self.vocab_pad * self.vocab_pad
@@ -56,8 +67,9 @@ BERT_TINY = BertConfig(vocab_size=1000, hidden=128, layers=2, heads=2, intermedi
 
 
 class BertLayer(nn.Module):
-    def __init__(self, store: ParamStore, name: str, c: BertConfig):
+    def __init__(self, store: ParamStore, name: str, c: BertConfig, index: int = 0):
         super().__init__()
+        self.site0 = 1 + 3 * index  # dropout sites: site0 probabilities, site0 + 1 after O, site0 + 2 after FFN2
         h, f = c.hidden, c.intermediate
         std = init_normal(c.init_std)
         self.c = c
@@ -76,8 +88,12 @@ class BertLayer(nn.Module):
         self.ln2_g = store.new(name + ".output.LayerNorm.weight", (h,), init_const(1), decay=False, lowp=False)
         self.ln2_b = store.new(name + ".output.LayerNorm.bias", (h,), init_const(0), decay=False, lowp=False)
 
-    def forward(self, x, B, S, kv_lens):
+    def forward(self, x, B, S, kv_lens, drop=None):
+        """``drop``: the model's DropoutState when this forward applies dropout (training mode), else None."""
         c = self.c
+        pa = (c.attention_dropout, drop, self.site0) if drop is not None and c.attention_dropout else None
+        p1 = (c.hidden_dropout, drop, self.site0 + 1) if drop is not None and c.hidden_dropout else None
+        p2 = (c.hidden_dropout, drop, self.site0 + 2) if drop is not None and c.hidden_dropout else None
         h, nh = c.hidden, c.heads
         d = h // nh
         # x is read by the QKV GEMM and, as the residual, by LN1 (likewise LN1's output by FFN1 and LN2): each
@@ -88,14 +104,14 @@ class BertLayer(nn.Module):
         b0, b1, b2 = K.BiasLink(), K.BiasLink(), K.BiasLink()
         qkv = K.linear(x, self.qkv_w, self.qkv_b, grad_link=l1, bias_link=b0)  # [T, 3h]
         o = attention_qkv(qkv, B, S, nh, nh, d, causal=False, kv_lens=kv_lens,
-                          bias_link=b0)  # packed QKV gradient in place
+                          bias_link=b0, dropout=pa)  # packed QKV gradient in place
         a = K.linear(o.reshape(B * S, h), self.o_w, self.o_b, bias_link=b1)
-        x, _ = K.layer_norm(a, self.ln1_g, self.ln1_b, c.eps, residual=x, res_link=l1, bias_link=b1)
+        x, _ = K.layer_norm(a, self.ln1_g, self.ln1_b, c.eps, residual=x, res_link=l1, bias_link=b1, dropout=p1)
         # FFN1's GELU backward and bias gradient inside FFN2's data-gradient epilogue (ActLink)
         al = K.ActLink()
         f = K.linear(x, self.f1_w, self.f1_b, act="gelu", grad_link=l2, act_link=al)
         f = K.linear(f, self.f2_w, self.f2_b, bias_link=b2, act_in=al)
-        x, _ = K.layer_norm(f, self.ln2_g, self.ln2_b, c.eps, residual=x, res_link=l2, bias_link=b2)
+        x, _ = K.layer_norm(f, self.ln2_g, self.ln2_b, c.eps, residual=x, res_link=l2, bias_link=b2, dropout=p2)
         return x
 
 
@@ -111,7 +127,9 @@ class BertForPreTraining(nn.Module):
         self.typ = store.new("bert.embeddings.token_type_embeddings.weight", (c.type_vocab, h), std)
         self.emb_ln_g = store.new("bert.embeddings.LayerNorm.weight", (h,), init_const(1), decay=False, lowp=False)
         self.emb_ln_b = store.new("bert.embeddings.LayerNorm.bias", (h,), init_const(0), decay=False, lowp=False)
-        self.layers = nn.ModuleList([BertLayer(store, "bert.encoder.layer.%d" % i, c) for i in range(c.layers)])
+        self.layers = nn.ModuleList([BertLayer(store, "bert.encoder.layer.%d" % i, c, i) for i in range(c.layers)])
+        # [seed, step] of every dropout site; the trainer seeds it per rank and sets the step after a restore
+        self.drop_state = K.DropoutState(0)
         self.pool_w = store.new("bert.pooler.dense.weight", (h, h), std)
         self.pool_b = store.new("bert.pooler.dense.bias", (h,), init_const(0), decay=False, lowp=False)
         self.mlm_w = store.new("cls.predictions.transform.dense.weight", (h, h), std)
@@ -126,6 +144,7 @@ class BertForPreTraining(nn.Module):
 
     def finalize(self, device, **kw):
         self.store.finalize(device, **kw)
+        self.drop_state.to(device)
         return self.to(device)
 
     def forward(self, input_ids, token_type_ids, mlm_labels, nsp_labels, mlm_positions=None, kv_lens=None,
@@ -136,11 +155,17 @@ class BertForPreTraining(nn.Module):
         B, S = input_ids.shape
         c = self.c
         h = c.hidden
+        drop = None
+        if self.training and (c.hidden_dropout or c.attention_dropout):
+            drop = self.drop_state
+            drop.advance()  # once per training forward, first: part of a captured step, so graph replays advance too
         # word + position + token-type lookups summed in one gather pass (scatter-add backward)
         e = K.embedding_sum([(input_ids, self.word), (None, self.pos), (token_type_ids, self.typ)], S, dtype)
         x = K.layer_norm(e.reshape(B * S, h), self.emb_ln_g, self.emb_ln_b, c.eps)
+        if drop is not None and c.hidden_dropout:
+            x = K.dropout(x, c.hidden_dropout, drop, 0)
         for layer in self.layers:
-            x = layer(x, B, S, kv_lens)
+            x = layer(x, B, S, kv_lens, drop)
         if mlm_positions is not None:
             rows = (mlm_positions + torch.arange(B, device=x.device).unsqueeze(1) * S).reshape(-1)
             xm = x.index_select(0, rows)  # [B * P, h]; backward scatters into the encoder output gradient

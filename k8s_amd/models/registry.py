@@ -61,9 +61,14 @@ def _plain_eval_forward(model, x):
 
 def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optional[int] = None,
           seed: int = 0, grad_dtype=torch.float32, fixed_batch: bool = True, pad_to: int = 64,
-          data_seed: Optional[int] = None, mlm_every_token: bool = False) -> Workload:
+          data_seed: Optional[int] = None, mlm_every_token: bool = False, dropout: Optional[float] = None,
+          dropout_seed: Optional[int] = None) -> Workload:
     """Construct ``name`` on ``device`` with per-rank ``batch``. ``fixed_batch`` reuses one synthetic batch
-    (what a throughput benchmark wants); otherwise every step draws a new one."""
+    (what a throughput benchmark wants); otherwise every step draws a new one. ``dropout`` (BERT only): the hidden
+    and attention-probability dropout of the training forward, seeded by ``dropout_seed`` (default ``seed``);
+    evaluation runs without it."""
+    if dropout and name not in ("bert_base", "bert_tiny"):
+        raise ValueError("dropout is implemented for the BERT models only, not %r" % name)
     device = torch.device(device)
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
     store = ParamStore()
@@ -81,12 +86,20 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
 
         return get
 
-    def token_eval(loss_of, labels_of):
-        """Evaluation of a model without mode-dependent layers: its own forward under no_grad."""
+    def token_eval(loss_of, labels_of, model=None):
+        """Evaluation of a token model: its own forward under no_grad -- in eval mode when ``model`` is given (BERT:
+        no dropout), the training flag restored afterwards as ``_plain_eval_forward`` does."""
         def evaluate(b, folded=None):
-            with torch.no_grad():
-                count = (labels_of(b) != -100).sum()
-                return {"loss_sum": loss_of(b).double() * count.double(), "count": count}
+            was = model.training if model is not None else None
+            if model is not None:
+                model.eval()
+            try:
+                with torch.no_grad():
+                    count = (labels_of(b) != -100).sum()
+                    return {"loss_sum": loss_of(b).double() * count.double(), "count": count}
+            finally:
+                if model is not None:
+                    model.train(was)
 
         return evaluate
 
@@ -128,20 +141,23 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
     if name in ("bert_base", "bert_tiny"):
         from k8s_amd.models import bert as M
 
+        import dataclasses
+
         cfg = M.BERT_BASE if name == "bert_base" else M.BERT_TINY
         if mlm_every_token:  # the MLM head on every token (dense labels), like HF BertForPreTraining
-            import dataclasses
-
             cfg = dataclasses.replace(cfg, max_predictions=0)
+        if dropout:
+            cfg = dataclasses.replace(cfg, hidden_dropout=float(dropout), attention_dropout=float(dropout))
         seq = seq or (128 if name == "bert_base" else 32)
         model = M.BertForPreTraining(store, cfg).finalize(device, grad_dtype=grad_dtype, seed=seed, pad_to=pad_to)
+        model.drop_state = K.DropoutState(seed if dropout_seed is None else dropout_seed, device)
 
         def make(n=batch, g=gen):
             return M.synthetic_batch(cfg, n, seq, device, generator=g)
 
         return Workload(name, model, store, cached(make), lambda b: model(*b, dtype=dtype)[0], batch * seq,
                         "tokens", "adam", 1e-4, {"seq": seq},
-                        evaluate=token_eval(lambda b: model(*b, dtype=dtype)[0], lambda b: b[2]),
+                        evaluate=token_eval(lambda b: model(*b, dtype=dtype)[0], lambda b: b[2], model),
                         eval_batch=heldout(make))
 
     if name in ("llama3_8b", "llama_1b", "llama_tiny"):

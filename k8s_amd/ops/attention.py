@@ -9,15 +9,48 @@ dK/dV in registers and atomically accumulated dQ). q/k/v may be strided
 views (e.g. column slices of the fused QKV projection) -- no copies. Head
 dims other than 64/128 and CPU tensors use an explicit matmul/softmax
 reference (no SDPA dispatch, so no Triton-built kernels run).
+
+``dropout=(p, DropoutState, site)`` drops attention probabilities with the counter generator of
+``csrc/kernels/rng.h`` (row = (b * Hq + h) * Sq + q, col = key): fused into the forward and the one-block backward
+for the shapes that backward takes (head_dim 64, Sq, Sk <= 128, Hq == Hkv); any other GPU shape runs the reference
+composition with the same mask, counted in ``DROPOUT_FALLBACKS`` and warned about once.
 """
 from __future__ import annotations
 
 import math
+import warnings
 from typing import Optional
 
 import torch
 
+from k8s_amd.ops import reference as ref
 from k8s_amd.ops._ext import load as _load
+
+# GPU attention calls with dropout that ran the reference composition instead of the fused kernels
+DROPOUT_FALLBACKS = 0
+
+
+def _dropout_fallback(q, k):
+    global DROPOUT_FALLBACKS
+    if DROPOUT_FALLBACKS == 0:
+        warnings.warn("k8s_amd attention: dropout on q %s / k %s is outside the one-block kernels' shape contract "
+                      "(head_dim 64, Sq, Sk <= 128, Hq == Hkv); using the reference composition"
+                      % (tuple(q.shape), tuple(k.shape)))
+    DROPOUT_FALLBACKS += 1
+
+
+def _drop_spec(dropout):
+    from k8s_amd.ops import nn as _nn
+
+    return _nn._drop_spec(dropout, "attention")
+
+
+def _drop_fused(q, k, v, causal) -> bool:
+    """The fused dropout path takes this call: the flash kernels' operand contract and a one-block backward shape."""
+    if not (_flash_ok(q, k, v) and q.shape[-1] == 64):
+        return False
+    B, Sq, Hq, D = q.shape
+    return bool(_load().flash_bwd_one_block(D, Sq, k.shape[1], Hq, k.shape[2], causal, B))
 
 
 def _flash_ok(q, k, v) -> bool:
@@ -28,7 +61,9 @@ def _flash_ok(q, k, v) -> bool:
     return ok and hasattr(_load(), "flash_fwd")  # _load() raises if the extension is missing on a GPU box
 
 
-def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None):
+def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+                        keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0):
+    """``keep`` (bool [B, Hq, Sq, Sk], ``ref.attention_keep``) with ``keep_scale``: dropout on the probabilities."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     rep = Hq // Hkv
@@ -45,17 +80,35 @@ def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] =
         keymask = torch.arange(Sk, device=q.device)[None, :] >= kv_lens[:, None].to(q.device)
         s = s.masked_fill(keymask[:, None, None, :], float("-inf"))
     p = torch.softmax(s, -1)
+    if keep is not None:
+        p = torch.where(keep, p * keep_scale, torch.zeros((), device=p.device))
     o = torch.matmul(p, vh)
     return o.permute(0, 2, 1, 3).to(q.dtype)
 
 
+def _drop_kw(drop) -> dict:
+    """flash_fwd / flash_bwd keyword arguments of a dropout spec (p, thr, scale, state, site); none when off."""
+    if drop is None:
+        return {}
+    return {"drop_state": drop[3].tensor, "drop_thr": drop[1], "drop_scale": drop[2], "drop_site": drop[4]}
+
+
+def _ref_keep(drop, q, k):
+    if drop is None:
+        return None, 1.0
+    p, _, scale, state, site = drop
+    B, Sq, Hq, _ = q.shape
+    return ref.attention_keep(state.tensor.to(q.device), site, B, Hq, Sq, k.shape[1], p), scale
+
+
 class _Flash(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, kv_lens, scale):
+    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None):
         C = _load()
         if kv_lens is not None:
             kv_lens = kv_lens.to(device=q.device, dtype=torch.int32).contiguous()
-        o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale)
+        ctx.drop = _drop_kw(drop)
+        o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.drop)
         ctx.save_for_backward(q, k, v, o, lse, kv_lens if kv_lens is not None else torch.empty(0))
         ctx.causal, ctx.scale, ctx.has_lens = causal, scale, kv_lens is not None
         return o
@@ -65,30 +118,40 @@ class _Flash(torch.autograd.Function):
         q, k, v, o, lse, lens = ctx.saved_tensors
         C = _load()
         dq, dk, dv = C.flash_bwd(do.contiguous(), q, k, v, o, lse, ctx.causal, lens if ctx.has_lens else None,
-                                 ctx.scale)
-        return dq, dk, dv, None, None, None
+                                 ctx.scale, **ctx.drop)
+        return dq, dk, dv, None, None, None, None
 
 
 class _Reference(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, kv_lens, scale):
+    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None):
         ctx.save_for_backward(q, k, v)
-        ctx.causal, ctx.kv_lens, ctx.scale = causal, kv_lens, scale
+        ctx.causal, ctx.kv_lens, ctx.scale, ctx.drop = causal, kv_lens, scale, drop
         with torch.no_grad():
-            return attention_reference(q, k, v, causal, kv_lens, scale)
+            keep, ks = _ref_keep(drop, q, k)
+            return attention_reference(q, k, v, causal, kv_lens, scale, keep, ks)
 
     @staticmethod
     def backward(ctx, do):
         q, k, v = ctx.saved_tensors
         with torch.enable_grad():
             qq, kk, vv = (t.detach().float().requires_grad_(True) for t in (q, k, v))
-            o = attention_reference(qq, kk, vv, ctx.causal, ctx.kv_lens, ctx.scale)
+            keep, ks = _ref_keep(ctx.drop, q, k)  # the forward's mask again (same seed, step and site)
+            o = attention_reference(qq, kk, vv, ctx.causal, ctx.kv_lens, ctx.scale, keep, ks)
             dq, dk, dv = torch.autograd.grad(o, (qq, kk, vv), do.float())
-        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None
+        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None, None
 
 
-def attention(q, k, v, causal: bool = False, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None):
+def attention(q, k, v, causal: bool = False, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None,
+              dropout: Optional[tuple] = None):
     scale = scale or 1.0 / math.sqrt(q.shape[-1])
+    drop = _drop_spec(dropout)
+    if drop is not None:
+        if _drop_fused(q, k, v, causal):
+            return _Flash.apply(q, k, v, causal, kv_lens, scale, drop)
+        if q.is_cuda:
+            _dropout_fallback(q, k)
+        return _Reference.apply(q, k, v, causal, kv_lens, scale, drop)
     if _flash_ok(q, k, v):
         return _Flash.apply(q, k, v, causal, kv_lens, scale)
     return _Reference.apply(q, k, v, causal, kv_lens, scale)
@@ -102,7 +165,7 @@ class _FlashQKV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, B, S, H, Hkv, D, causal, kv_lens, scale, pos, table, bias_link=None, rope_in_place=False,
-                rope_applied=False):
+                rope_applied=False, drop=None):
         C = _load()
         if kv_lens is not None:
             kv_lens = kv_lens.to(device=qkv.device, dtype=torch.int32).contiguous()
@@ -116,7 +179,8 @@ class _FlashQKV(torch.autograd.Function):
             C.rope_(x[:, : (H + Hkv) * D], pos, table, False)
         g = x.view(B, S, H + 2 * Hkv, D)
         q, k, v = g.narrow(2, 0, H), g.narrow(2, H, Hkv), g.narrow(2, H + Hkv, Hkv)
-        o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale)
+        ctx.drop = _drop_kw(drop)
+        o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.drop)
         ctx.save_for_backward(x, o, lse, kv_lens if kv_lens is not None else torch.empty(0),
                               pos if pos is not None else torch.empty(0), table if table is not None else torch.empty(0))
         ctx.meta = (B, S, H, Hkv, D, causal, scale, kv_lens is not None, pos is not None)
@@ -140,19 +204,20 @@ class _FlashQKV(torch.autograd.Function):
             ss = lpb.store.slot_for_write(lpb)
             dsum = ss.view(lpb.shape) if ss is not None else torch.empty(lpb.shape, device=x.device,
                                                                          dtype=torch.float32)
-        C.flash_bwd(do.contiguous(), q, k, v, o, lse, causal, lens if has_lens else None, scale, dqkv, dsum)
+        C.flash_bwd(do.contiguous(), q, k, v, o, lse, causal, lens if has_lens else None, scale, dqkv, dsum,
+                    **ctx.drop)
         if dsum is not None:
             lpb.store.mark_written(lpb) if ss is not None else lpb.store.deposit(lpb, dsum)
             bl.done = True
         if has_rope:
             C.rope_(dqkv[:, : (H + Hkv) * D], pos, table, True)
-        return (dqkv,) + (None,) * 13
+        return (dqkv,) + (None,) * 14
 
 
 def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int, causal: bool = False,
                   kv_lens: Optional[torch.Tensor] = None, rope: Optional[tuple] = None,
                   scale: Optional[float] = None, bias_link=None, rope_in_place: bool = False,
-                  rope_applied: bool = False):
+                  rope_applied: bool = False, dropout: Optional[tuple] = None):
     """Self-attention of a packed QKV projection ``qkv`` [B*S, (heads + 2*kv_heads) * head_dim] (q heads, then k,
     then v); ``rope`` = (pos [B*S] int32, table) applies rotary embeddings to q and k. Returns o [B, S, heads, D].
     GPU bf16: one fused path (``_FlashQKV``); otherwise the split + ``attention`` reference composition.
@@ -164,15 +229,20 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
     since those would see the rotated values; ``tests/test_attention_gpu.py`` pins in place == copy bitwise.
     ``rope_applied``: q / k already rotated by the projection's epilogue (``ops.nn.linear_rope``); the backward still
     returns the gradient of the UN-rotated projection output (dqkv rotated back), which is what that linear's backward
-    takes."""
+    takes. ``dropout`` = (p, DropoutState, site): dropout on the probabilities, fused on the one-block shapes (see the
+    module docstring); other shapes take the split + ``attention`` composition, which counts the fallback."""
     D = head_dim
     scale = scale or 1.0 / math.sqrt(D)
     W = (heads + 2 * kv_heads) * D
-    if qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128) and qkv.shape[-1] == W and \
-            W % 8 == 0 and qkv.is_contiguous():
+    drop = _drop_spec(dropout)
+    fused = qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128) and qkv.shape[-1] == W and \
+        W % 8 == 0 and qkv.is_contiguous()
+    if fused and drop is not None:
+        fused = D == 64 and bool(_load().flash_bwd_one_block(D, S, S, heads, kv_heads, causal, B))
+    if fused:
         pos, table = rope if rope is not None else (None, None)
         return _FlashQKV.apply(qkv, B, S, heads, kv_heads, D, causal, kv_lens, scale, pos, table, bias_link,
-                               rope_in_place, rope_applied)
+                               rope_in_place, rope_applied, drop)
     if rope_applied:
         raise RuntimeError("attention_qkv: q / k rotated by the projection epilogue need the fused GPU path")
     q, k, v = qkv.split([heads * D, kv_heads * D, kv_heads * D], dim=-1)
@@ -181,4 +251,4 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
 
         q, k = _nn.rope(q, rope[0], rope[1]), _nn.rope(k, rope[0], rope[1])
     return attention(q.reshape(B, S, heads, D), k.reshape(B, S, kv_heads, D), v.reshape(B, S, kv_heads, D),
-                     causal=causal, kv_lens=kv_lens, scale=scale)
+                     causal=causal, kv_lens=kv_lens, scale=scale, dropout=dropout)

@@ -529,17 +529,100 @@ def batch_norm_act(x, pg, pb, run_mean, run_var, residual=None, relu=True, train
     return y
 
 
+# =========================================================================== dropout
+class DropoutState:
+    """The device int64 ``[seed, step]`` pair every dropout site of one model reads (``csrc/kernels/rng.h``): a mask
+    bit is a pure function of (seed, step, site, row, col, p), so nothing is stored and the backward regenerates the
+    forward's bits. The kernels read the pair themselves and ``advance`` is a device-side increment on the current
+    stream, so a captured graph draws new masks on every replay."""
+
+    def __init__(self, seed: int = 0, device="cpu"):
+        v = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.tensor = torch.tensor([v - (1 << 64) if v >= (1 << 63) else v, 0], dtype=torch.int64, device=device)
+
+    def to(self, device):
+        self.tensor = self.tensor.to(device)
+        return self
+
+    def advance(self):
+        self.tensor[1:2].add_(1)
+
+    def set_step(self, n: int):
+        self.tensor[1:2].fill_(int(n))
+
+    @property
+    def seed(self) -> int:
+        return int(self.tensor[0]) & 0xFFFFFFFFFFFFFFFF
+
+    @property
+    def step(self) -> int:
+        return int(self.tensor[1])
+
+
+def _drop_spec(dropout, what):
+    """None (off: p == 0 is the plain path, same launches and bits) or (p, thr, scale, state, site)."""
+    if dropout is None:
+        return None
+    p, state, site = dropout
+    if not p:
+        return None
+    if not isinstance(state, DropoutState):
+        raise TypeError("%s: dropout = (p, DropoutState, site)" % what)
+    thr, scale = ref.drop_params(float(p))
+    return float(p), thr, scale, state, int(site)
+
+
+def _drop_fused(x) -> bool:
+    return _gpu(x) and x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0
+
+
+class _Dropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, spec):
+        ctx.spec = spec
+        return _Dropout._map(x.contiguous(), spec)
+
+    @staticmethod
+    def _map(x, spec):
+        p, thr, scale, state, site = spec
+        if _drop_fused(x):
+            return _C().dropout(x, state.tensor, thr, scale, site)
+        D = x.shape[-1]
+        keep = ref.dropout_keep(state.tensor.to(x.device), site, x.numel() // D, D, p)
+        return ref.dropout(x, keep, scale)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _Dropout._map(dy.contiguous(), ctx.spec), None
+
+
+def dropout(x, p: float, state: DropoutState, site: int):
+    """y = keep ? x * scale : 0 with x viewed as rows of its last dim (row-major [R, D]); ``p`` = 0 returns x. The
+    backward is the same map with the same mask, so it must run before ``state`` advances."""
+    spec = _drop_spec((p, state, site), "dropout")
+    return x if spec is None else _Dropout.apply(x, spec)
+
+
 # =========================================================================== layernorm / rmsnorm
 class _Norm(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, res, anchor, pg, pb, eps, rms, res_link=None, bias_link=None):
+    def forward(ctx, x, res, anchor, pg, pb, eps, rms, res_link=None, bias_link=None, drop=None):
         # an unused second output (x + res) must not get a materialised zero gradient (one [T, D] fill per norm)
         ctx.set_materialize_grads(False)
         x = x.contiguous()
         if res is not None:
             res = res.contiguous()
         beta = pb.master if pb is not None else None
-        if _gpu(x):
+        ctx.drop = drop
+        if drop is not None:  # (p, thr, scale, state, site): x passes through dropout on its way into the add
+            p, thr, scale, state, site = drop
+            if _gpu(x):
+                y, mean, rstd, xsum = _C().norm_fwd(x, res, pg.master, beta, eps, rms, state.tensor, thr, scale, site)
+            else:
+                D = x.shape[-1]
+                keep = ref.dropout_keep(state.tensor, site, x.numel() // D, D, p)
+                y, mean, rstd, xsum = ref.dropout_add_norm_fwd(x, res, pg.master, beta, eps, keep, scale)
+        elif _gpu(x):
             y, mean, rstd, xsum = _C().norm_fwd(x, res, pg.master, beta, eps, rms)
         else:
             y, mean, rstd, xsum = ref.norm_fwd(x, res, pg.master, beta, eps, rms)
@@ -561,6 +644,7 @@ class _Norm(torch.autograd.Function):
             dy = torch.zeros(xin.shape, device=xin.device, dtype=xin.dtype)
         dy = dy.contiguous()
         dres = dxsum.contiguous() if (dxsum is not None and ctx.has_res) else None
+        drop, da = ctx.drop, None
         if _gpu(xin):
             # gamma / beta gradients straight into their flat fp32 slots on first use (no temporary + copy)
             sg = store.slot_for_write(pg)
@@ -578,7 +662,11 @@ class _Norm(torch.autograd.Function):
                 ss = store.slot_for_write(lpb) if lpb.store is store else None
                 dsum = ss.view(lpb.shape) if ss is not None else torch.empty(lpb.shape, device=xin.device,
                                                                              dtype=torch.float32)
-            dx = _C().norm_bwd(dy, xin, pg.master, mean, rstd, dres, dg, db, ctx.rms, dsum=dsum)
+            if drop is not None:
+                dx, da = _C().norm_bwd_dropout(dy, xin, pg.master, mean, rstd, dres, dg, db, dsum, drop[3].tensor,
+                                               drop[1], drop[2], drop[4])
+            else:
+                dx = _C().norm_bwd(dy, xin, pg.master, mean, rstd, dres, dg, db, ctx.rms, dsum=dsum)
             store.mark_written(pg) if sg is not None else store.deposit(pg, dg)
             if pb is not None:
                 store.mark_written(pb) if sb is not None else store.deposit(pb, db)
@@ -586,7 +674,12 @@ class _Norm(torch.autograd.Function):
                 lpb.store.mark_written(lpb) if ss is not None else lpb.store.deposit(lpb, dsum)
                 bl.done = True
         else:
-            dx, dg, db = ref.norm_bwd(dy, xin, pg.master, mean, rstd, dres, ctx.rms)
+            if drop is not None:
+                D = xin.shape[-1]
+                keep = ref.dropout_keep(drop[3].tensor, drop[4], xin.numel() // D, D, drop[0])
+                dx, da, dg, db, _ = ref.dropout_add_norm_bwd(dy, xin, pg.master, mean, rstd, dres, keep, drop[2])
+            else:
+                dx, dg, db = ref.norm_bwd(dy, xin, pg.master, mean, rstd, dres, ctx.rms)
             store.deposit(pg, dg)
             if pb is not None:
                 store.deposit(pb, db)
@@ -601,14 +694,22 @@ class _Norm(torch.autograd.Function):
                 else:  # that linear already ran and handed its dgrad over: form the sum here
                     dres_out = dx + link.grad
                     link.grad = None
-        return dx, dres_out, None, None, None, None, None, None, None
+        # (with dropout, x's gradient is the masked da; dx itself is the gradient of the sum, i.e. the residual's)
+        return (da if drop is not None else dx), dres_out, None, None, None, None, None, None, None, None
 
 
-def layer_norm(x, pg, pb, eps=1e-12, residual=None, res_link=None, bias_link=None):
+def layer_norm(x, pg, pb, eps=1e-12, residual=None, res_link=None, bias_link=None, dropout=None):
     """LayerNorm over the last dim; with ``residual`` returns (norm(x+res), x+res). ``res_link`` (a GradLink
     shared with the linear that also reads ``residual``): the two gradient contributions of ``residual`` are
-    summed in that linear's dgrad epilogue instead of by a separate add. ``bias_link``: see ``BiasLink``."""
-    y, xsum = _Norm.apply(x, residual, pg.store.anchor, pg, pb, eps, False, res_link, bias_link)
+    summed in that linear's dgrad epilogue instead of by a separate add. ``bias_link``: see ``BiasLink``.
+    ``dropout`` = (p, DropoutState, site), with ``residual`` only: norm(dropout(x) + res) in the same kernels (the mask
+    applied in registers; the backward writes x's masked gradient beside the sum's and the ``bias_link`` column sums
+    are the masked gradient's)."""
+    drop = _drop_spec(dropout, "layer_norm")
+    if drop is not None and residual is None:
+        raise ValueError("layer_norm: dropout is applied to x on its way into the residual add; without a residual "
+                         "use nn.dropout")
+    y, xsum = _Norm.apply(x, residual, pg.store.anchor, pg, pb, eps, False, res_link, bias_link, drop)
     return (y, xsum) if residual is not None else y
 
 

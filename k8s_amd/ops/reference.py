@@ -83,6 +83,135 @@ def norm_bwd(dy, x, gamma, mean, rstd, dres, rms):
     return dx.reshape(x.shape).to(x.dtype), dgamma, dbeta
 
 
+# --------------------------------------------------------------------------- dropout (counter generator)
+# The definition the kernels implement (csrc/kernels/rng.h), in torch integer ops: int64 values masked to 32 bits, on
+# whatever device the state / rows live on, with no host read of a device tensor -- so it is both the CPU oracle and the
+# on-GPU fallback under graph capture.
+#   rowkey = Philox4x32-10(counter = (row lo, row hi, site, step lo), key = (seed lo, seed hi))[0]
+#   keep   = mix32(rowkey ^ (col * 0x9E3779B1)) >= thr
+_M32 = 0xFFFFFFFF
+
+
+def drop_params(p: float):
+    """(thr, scale) of a drop probability in [0, 1): thr = min(floor(p 2^32 + 0.5), 2^32 - 1), scale = the fp32 value
+    of 1 / (1 - thr / 2^32) -- the quantised probability, so E[keep * scale] = 1."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout probability must be in [0, 1), got %r" % (p,))
+    thr = min(int(math.floor(p * 4294967296.0 + 0.5)), _M32)
+    scale = torch.tensor(1.0 / (1.0 - thr / 4294967296.0), dtype=torch.float32).item()
+    return thr, scale
+
+
+def _mulhilo32(a: int, b):
+    """(hi, lo) 32-bit halves of a * b for a constant a < 2^32 and an int64 tensor b of values < 2^32."""
+    t1 = (b & 0xFFFF) * a   # < 2^48
+    t2 = (b >> 16) * a      # < 2^48, weight 2^16
+    low = ((t2 & 0xFFFF) << 16) + t1
+    return (t2 >> 16) + (low >> 32), low & _M32
+
+
+def _mul32(x, c: int):
+    """x * c mod 2^32 for an int64 tensor x of values < 2^32 and a constant c < 2^32."""
+    return (x * (c & 0xFFFF) + (((x * (c >> 16)) & 0xFFFF) << 16)) & _M32
+
+
+def philox4x32(counter, key):
+    """Random123 Philox4x32-10 on int64 tensors holding 32-bit words: counter (c0, c1, c2, c3), key (k0, k1)."""
+    c0, c1, c2, c3 = counter
+    k0, k1 = key
+    for _ in range(10):
+        hi0, lo0 = _mulhilo32(0xD2511F53, c0)
+        hi1, lo1 = _mulhilo32(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def _drop_state(state, device):
+    """int64 [seed, step] on ``device`` from a DropoutState, a tensor or a (seed, step) pair of ints."""
+    t = getattr(state, "tensor", state)
+    if isinstance(t, torch.Tensor):
+        return t if device is None else t.to(device)
+
+    def wrap(v):  # any 64-bit seed as the int64 with the same bits
+        v = int(v) & 0xFFFFFFFFFFFFFFFF
+        return v - (1 << 64) if v >= (1 << 63) else v
+
+    return torch.tensor([wrap(t[0]), wrap(t[1])], dtype=torch.int64, device=device)
+
+
+def dropout_rowkey(state, site: int, rows):
+    """Philox rowkeys (int64 tensor of 32-bit values, ``rows``' shape) of the int64 row indices ``rows``."""
+    rows = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(rows, dtype=torch.int64)
+    st = _drop_state(state, rows.device)
+    rows = rows.to(torch.int64)
+    seed, step = st[0], st[1]
+    z = torch.zeros_like(rows)
+    counter = (rows & _M32, (rows >> 32) & _M32, z + int(site), z + (step & _M32))
+    key = (z + (seed & _M32), z + ((seed >> 32) & _M32))
+    return philox4x32(counter, key)[0]
+
+
+def dropout_keep(state, site: int, rows, cols, p: float):
+    """Keep mask (bool, ``rows``' shape + [len(cols)]) of the dropout site ``site``: ``rows`` int64 row indices (a
+    tensor, or a count meaning 0 .. n - 1), ``cols`` likewise the columns; ``state`` a DropoutState, its int64
+    [seed, step] tensor, or a (seed, step) pair."""
+    t = getattr(state, "tensor", state)
+    dev = t.device if isinstance(t, torch.Tensor) else None
+    if not isinstance(rows, torch.Tensor):
+        rows = torch.arange(int(rows), dtype=torch.int64, device=dev)
+    if not isinstance(cols, torch.Tensor):
+        cols = torch.arange(int(cols), dtype=torch.int64, device=rows.device)
+    thr, _ = drop_params(p)
+    rk = dropout_rowkey(state, site, rows).unsqueeze(-1)
+    x = rk ^ _mul32(cols.to(device=rows.device, dtype=torch.int64) & _M32, 0x9E3779B1)
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    x = x ^ (x >> 16)
+    return x >= thr
+
+
+def attention_keep(state, site: int, B: int, H: int, Sq: int, Sk: int, p: float, device=None):
+    """Keep mask [B, H, Sq, Sk] of attention probabilities: row = (b H + h) Sq + q, col = key."""
+    t = getattr(state, "tensor", state)
+    dev = t.device if isinstance(t, torch.Tensor) else device
+    rows = torch.arange(B * H * Sq, dtype=torch.int64, device=dev)
+    return dropout_keep(state, site, rows, torch.arange(Sk, dtype=torch.int64, device=dev), p).view(B, H, Sq, Sk)
+
+
+def dropout(x, keep, scale: float):
+    """y = keep ? x * scale : 0, rounded once to x's dtype (forward and backward are the same map)."""
+    return torch.where(keep.reshape(x.shape), x.float() * scale, torch.zeros((), device=x.device)).to(x.dtype)
+
+
+def dropout_add_norm_fwd(x, res, gamma, beta, eps, keep, scale: float):
+    """LayerNorm(keep * scale * x + res): (y, mean, rstd, xsum) like ``norm_fwd`` with a residual."""
+    xs = torch.where(keep.reshape(x.shape), x.float() * scale, torch.zeros((), device=x.device)) + res.float()
+    mean = xs.mean(-1)
+    var = (xs - mean.unsqueeze(-1)).pow(2).mean(-1)
+    rstd = torch.rsqrt(var + eps)
+    y = (xs - mean.unsqueeze(-1)) * rstd.unsqueeze(-1) * gamma.float() + beta.float()
+    return y.to(x.dtype), mean.reshape(-1), rstd.reshape(-1), xs.to(x.dtype)
+
+
+def dropout_add_norm_bwd(dy, xsum, gamma, mean, rstd, dres, keep, scale: float):
+    """(dx, da, dgamma, dbeta, dsum): dx the gradient of the sum (the residual's), da = keep * scale * dx the dropped
+    summand's, dsum the fp32 column sums of da."""
+    D = xsum.shape[-1]
+    g = dy.float().reshape(-1, D)
+    r = rstd.reshape(-1, 1)
+    xh = (xsum.float().reshape(-1, D) - mean.reshape(-1, 1)) * r
+    gg = g * gamma.float()
+    dx = r * (gg - gg.mean(-1, keepdim=True) - xh * (gg * xh).mean(-1, keepdim=True))
+    if dres is not None:
+        dx = dx + dres.float().reshape(-1, D)
+    da = torch.where(keep.reshape(-1, D), dx * scale, torch.zeros((), device=dx.device))
+    return (dx.reshape(xsum.shape).to(xsum.dtype), da.reshape(xsum.shape).to(xsum.dtype), (g * xh).sum(0), g.sum(0),
+            da.sum(0))
+
+
 # --------------------------------------------------------------------------- cross entropy
 def xent_fwd(logits, labels, ignore_index=-100, smoothing=0.0):
     lf = logits.float()

@@ -100,6 +100,10 @@ def parse(argv=None):
                          "has PS tasks, 0: never")
     ap.add_argument("--log-every", type=int, default=10)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="BERT: hidden and attention-probability dropout of the training forward (the original "
+                         "recipe uses 0.1); masks are a function of (--seed, rank, step), so a resumed or graphed run "
+                         "draws the same ones")
     ap.add_argument("--fresh-batches", action="store_true", help="draw a new synthetic batch every step")
     ap.add_argument("--graph", action="store_true", default=os.environ.get("K8S_AMD_GRAPH", "0") == "1",
                     help="capture the whole step in a hipGraph after warmup (single rank, all-reduce strategy)")
@@ -329,6 +333,10 @@ def train(a) -> int:
         config_error = "--eval-batches and --eval-batch must be positive"
     elif a.eval_every < 0:
         config_error = "--eval-every must be >= 0"
+    elif not 0.0 <= a.dropout < 1.0:
+        config_error = "--dropout must be in [0, 1)"
+    elif a.dropout > 0 and not a.model.startswith("bert"):
+        config_error = "--dropout is implemented for the BERT models only, not %s" % a.model
     if config_error:
         print("error: %s" % config_error, file=sys.stderr, flush=True)
         return EXIT_PERMANENT
@@ -360,12 +368,13 @@ def train(a) -> int:
     metrics = _Metrics(a.logdir, chief)
     metrics.event(event="start", rank=rank, world=world, role=info.role, model=a.model, strategy=a.strategy,
                   device=str(dev), start_time=t_start, process_start_time=t_proc, zero1=bool(sharded and world > 1), grad_comm=comm,
-                  optimizer=opt_name, lr_schedule=a.lr_schedule, batch=batch)
+                  optimizer=opt_name, lr_schedule=a.lr_schedule, batch=batch, dropout=a.dropout)
 
     # the sharded parameter service needs the flat buffers divisible into world equal 64-aligned shards
     w = build(a.model, dev, batch, seq=a.seq, image=a.image, seed=a.seed, fixed_batch=not a.fresh_batches,
               pad_to=world * ALIGN if sharded else ALIGN, data_seed=a.seed * 7919 + rank,
-              mlm_every_token=a.mlm_head == "every-token")
+              mlm_every_token=a.mlm_head == "every-token", dropout=a.dropout or None,
+              dropout_seed=a.seed * 7919 + rank)
     lr = a.lr if a.lr is not None else w.lr
     if opt_name in ("sgd", "lars"):
         wd = 5e-5 if a.weight_decay is None else a.weight_decay
@@ -404,6 +413,8 @@ def train(a) -> int:
 
         psv = PsVariables(ps_addrs)
     start_step = _restore(a, w, opt, dev, chief, world, metrics, psv, svc)
+    if a.dropout > 0:  # step t draws the same masks whether or not the run was resumed
+        w.model.drop_state.set_step(start_step)
     t_ready = time.time()  # model, optimizer and data built, checkpoint restored
     if a.eval_only and start_step == 0:  # (start_step is broadcast: every rank leaves together)
         metrics.event(event="error", error="--eval-only: no checkpoint in --ckpt-dir and no PS variable snapshot "
@@ -602,10 +613,12 @@ def train(a) -> int:
     if svc is not None:
         svc.sync_master()
     kdist.barrier()
+    from k8s_amd.ops import attention as kattn
     from k8s_amd.ops import gemm as kgemm
 
     metrics.event(event="done", steps=a.steps, loss=loss_v, elapsed=time.time() - t_start, rank=rank,
                   weights_sum=float(w.store.master.double().sum().item()), gemm_fallbacks=dict(kgemm.FALLBACKS),
+                  dropout_fallbacks=kattn.DROPOUT_FALLBACKS,
                   peak_mem_gb=(round(torch.cuda.max_memory_allocated(w.store.master.device) / 2**30, 1)
                                if w.store.master.is_cuda else None))
     metrics.close()
