@@ -5,8 +5,9 @@ snapshot to the GPU box:
 
 * ``k8s_amd/_C*.so``      -- gfx950 HIP kernels + PyTorch bindings. Each
   ``csrc/kernels/*.hip`` file is compiled by ``hipcc --offload-arch=gfx950``
-  WITHOUT torch headers (seconds per file, in parallel); only
-  ``csrc/ops_binding.cpp`` sees the torch headers. Linked against torch's own
+  WITHOUT torch headers (seconds per file, in parallel); only the binding
+  files ``csrc/binding/*.cpp`` (one per kernel family, each its own job in
+  the same pool) see the torch headers. Linked against torch's own
   ``libamdhip64`` so the extension shares PyTorch's HIP runtime and streams.
 * ``k8s_amd/_operator*.so`` + ``bin/tf_operator`` + ``bin/e2e`` -- the C++17
   control plane (see csrc/operator), built with g++.
@@ -102,6 +103,10 @@ def kernel_sources():
     return sorted(glob.glob(os.path.join(CSRC, "kernels", "*.hip")))
 
 
+def binding_sources():
+    return sorted(glob.glob(os.path.join(CSRC, "binding", "*.cpp")))
+
+
 def build_kernels(force=False, jobs=None) -> str:
     inc, tlib = _torch_dirs()
     os.makedirs(os.path.join(BUILD, "obj"), exist_ok=True)
@@ -113,20 +118,21 @@ def build_kernels(force=False, jobs=None) -> str:
         if force or _newer(obj, [src] + headers):
             jobs_list.append([HIPCC, *HIP_FLAGS, RESOURCE_FLAG, "-I", os.path.join(CSRC, "kernels"), "-c", src,
                               "-o", obj])
-    bind_src = os.path.join(CSRC, "ops_binding.cpp")
-    bind_obj = os.path.join(BUILD, "obj", "ops_binding.o")
-    objs.append(bind_obj)
-    if force or _newer(bind_obj, [bind_src] + headers):
-        flags = [
-            "-DUSE_ROCM=1",
-            "-D__HIP_PLATFORM_AMD__=1",
-            "-DTORCH_EXTENSION_NAME=_C",
-            "-DTORCH_API_INCLUDE_EXTENSION_H",
-            "-D_GLIBCXX_USE_CXX11_ABI=1",
-            "-Wno-deprecated-declarations",
-        ]
-        incs = sum([["-I", d] for d in inc + [sysconfig.get_paths()["include"], CSRC]], [])
-        jobs_list.append([HIPCC, *HIP_FLAGS, *flags, *incs, "-c", bind_src, "-o", bind_obj])
+    bind_flags = [
+        "-DUSE_ROCM=1",
+        "-D__HIP_PLATFORM_AMD__=1",
+        "-DTORCH_EXTENSION_NAME=_C",
+        "-DTORCH_API_INCLUDE_EXTENSION_H",
+        "-D_GLIBCXX_USE_CXX11_ABI=1",
+        "-Wno-deprecated-declarations",
+    ]
+    bind_incs = sum([["-I", d] for d in inc + [sysconfig.get_paths()["include"], CSRC]], [])
+    bind_headers = headers + glob.glob(os.path.join(CSRC, "binding", "*.h"))
+    for src in binding_sources():
+        obj = os.path.join(BUILD, "obj", "binding_" + os.path.basename(src) + ".o")
+        objs.append(obj)
+        if force or _newer(obj, [src] + bind_headers):
+            jobs_list.append([HIPCC, *HIP_FLAGS, *bind_flags, *bind_incs, "-c", src, "-o", obj])
     n = jobs or min(8, os.cpu_count() or 4)
     with cf.ThreadPoolExecutor(max_workers=n) as ex:
         logs = [(j, fut.result()) for j, fut in [(j, ex.submit(_run, j)) for j in jobs_list]]

@@ -1,0 +1,143 @@
+// Flash attention forward / backward (attention.hip), with optional dropout on the probabilities.
+#include "binding/common.h"
+
+namespace k8s_amd::binding {
+namespace {
+
+void check_attn_operand(const Tensor& t, const char* name, long D) {
+  TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
+  check_dtype(t, at::kBFloat16, name);
+  TORCH_CHECK(t.dim() == 4, name, " must be [B, S, H, D]");
+  TORCH_CHECK(t.size(3) == D && t.stride(3) == 1, name, " must have a contiguous head dim of ", D);
+  for (int i = 0; i < 3; ++i) TORCH_CHECK(t.stride(i) % 8 == 0, name, " strides must be multiples of 8 elements");
+  check_aligned(t, name);
+}
+const int* kv_lens_ptr(const OptTensor& kv_lens, long B) {
+  if (!kv_lens) return nullptr;
+  TORCH_CHECK(kv_lens->is_cuda() && kv_lens->scalar_type() == at::kInt && kv_lens->is_contiguous() &&
+                  kv_lens->numel() == B, "kv_lens must be an int32 GPU tensor of length B");
+  return kv_lens->data_ptr<int>();
+}
+
+// what AttnFwdArgs and AttnBwdArgs share: q / k / v [B, S, H, D] with their strides, the shape, the softmax scale and
+// kv_lens. Returns the head dim D.
+template <class Args>
+long fill_qkv(Args& a, const Tensor& q, const Tensor& k, const Tensor& v, bool causal, const OptTensor& kv_lens,
+              double scale) {
+  TORCH_CHECK(q.dim() == 4 && (q.size(3) == 64 || q.size(3) == 128), "head dim must be 64 or 128");
+  const long D = q.size(3);
+  check_attn_operand(q, "q", D); check_attn_operand(k, "k", D); check_attn_operand(v, "v", D);
+  a.B = q.size(0); a.Sq = q.size(1); a.Hq = q.size(2); a.Sk = k.size(1); a.Hkv = k.size(2); a.causal = causal;
+  TORCH_CHECK(k.size(0) == a.B && v.size(0) == a.B && v.size(1) == a.Sk && v.size(2) == a.Hkv, "k/v shape mismatch");
+  TORCH_CHECK(a.Hkv > 0 && a.Hq % a.Hkv == 0, "Hq must be a multiple of Hkv");
+  TORCH_CHECK(a.Sq > 0 && a.Sk > 0, "empty sequence");
+  a.kv_lens = kv_lens_ptr(kv_lens, a.B);
+  a.q = cbf(q); a.k = cbf(k); a.v = cbf(v);
+  a.sqb = q.stride(0); a.sqs = q.stride(1); a.sqh = q.stride(2);
+  a.skb = k.stride(0); a.sks = k.stride(1); a.skh = k.stride(2);
+  a.svb = v.stride(0); a.svs = v.stride(1); a.svh = v.stride(2);
+  a.scale_log2 = (float)(scale * 1.4426950408889634);
+  return D;
+}
+
+// drop_state (optional): dropout on the probabilities, one-block shapes only (flash_bwd_one_block, D = 64)
+std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, bool causal, OptTensor kv_lens, double scale,
+                              OptTensor drop_state, int64_t drop_thr, double drop_scale, int64_t drop_site) {
+  AttnFwdArgs a;
+  const long D = fill_qkv(a, q, k, v, causal, kv_lens, scale);
+  const long B = a.B, Sq = a.Sq, Hq = a.Hq, Sk = a.Sk, Hkv = a.Hkv;
+  if (drop_state) {
+    TORCH_CHECK(k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, 1),
+                "attention dropout needs a one-block shape (flash_bwd_one_block)");
+    a.drop = drop_args(*drop_state, drop_thr, drop_scale, drop_site);
+  }
+  auto o = torch::empty({B, Sq, Hq, D}, q.options());
+  const long ld = (Sq + 127) / 128 * 128;  // padded rows: the backward stages 64/128-query slices with 16-B copies
+  auto lse = torch::empty({B, Hq, ld}, q.options().dtype(at::kFloat));
+  a.o = bf(o); a.lse = f32(lse); a.lse_ld = ld;
+  a.sob = o.stride(0); a.sos = o.stride(1); a.soh = o.stride(2);
+  launch_flash_fwd(a, (int)D, cur_stream());
+  return {o, lse};
+}
+
+// dq / dk / dv are new contiguous tensors, or -- with `dqkv` given -- views into that [B*S, (Hq + 2*Hkv) * D]
+// buffer laid out like the packed QKV projection q / k / v were sliced from (q at column 0, k at Hq*D, v at
+// (Hq + Hkv)*D): the fused projection's gradient is written in place, no concatenation afterwards.
+std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal,
+                              OptTensor kv_lens, double scale, OptTensor dqkv, OptTensor dbias, OptTensor drop_state,
+                              int64_t drop_thr, double drop_scale, int64_t drop_site) {
+  AttnBwdArgs a;
+  const long D = fill_qkv(a, q, k, v, causal, kv_lens, scale);
+  const long B = a.B, Sq = a.Sq, Hq = a.Hq, Sk = a.Sk, Hkv = a.Hkv;
+  check_attn_operand(o, "o", D); check_attn_operand(dO, "dO", D);
+  TORCH_CHECK(dO.sizes() == q.sizes() && o.sizes() == q.sizes(), "dO / o must match q");
+  check_cuda(lse, "lse"); check_dtype(lse, at::kFloat, "lse");
+  const long ld = (Sq + 127) / 128 * 128;
+  TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == Hq && lse.size(2) == ld,
+              "lse must be the [B, Hq, round_up(Sq, 128)] tensor flash_fwd returned");
+  const long Wp = (Hq + 2 * Hkv) * D;  // the packed QKV projection's width
+  a.dkv_split = k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal);
+  const bool one_block = k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, a.dkv_split);
+  if (dqkv) {
+    TORCH_CHECK(Sq == Sk, "packed QKV gradient needs self-attention (Sq == Sk)");
+    check_cuda(*dqkv, "dqkv"); check_dtype(*dqkv, at::kBFloat16, "dqkv");
+    TORCH_CHECK(dqkv->numel() == B * Sq * Wp, "dqkv must be contiguous [B*S, (Hq+2*Hkv)*D]");
+  }
+  if (dbias) {  // the packed projection's bias gradient from the one-block kernel's column partials
+    TORCH_CHECK(dqkv && one_block, "dbias needs the packed gradient and a one-block shape (flash_bwd_one_block)");
+    check_channel_f32(*dbias, Wp, "dbias");
+  }
+  if (drop_state) {
+    TORCH_CHECK(one_block, "attention dropout needs a one-block shape (flash_bwd_one_block)");
+    a.drop = drop_args(*drop_state, drop_thr, drop_scale, drop_site);
+  }
+  auto delta = torch::empty({B, Hq, ld}, q.options().dtype(at::kFloat));
+  Tensor dq, dk, dv;
+  if (dqkv) {
+    auto g = dqkv->view({B, Sq, Hq + 2 * Hkv, D});
+    dq = g.narrow(2, 0, Hq);
+    dk = g.narrow(2, Hq, Hkv);
+    dv = g.narrow(2, Hq + Hkv, Hkv);
+  } else {
+    dq = torch::empty({B, Sq, Hq, D}, q.options());
+    dk = torch::empty({B, Sk, Hkv, D}, q.options());
+    dv = torch::empty({B, Sk, Hkv, D}, q.options());
+  }
+  a.dO = cbf(dO); a.lse = f32(lse); a.lse_ld = ld; a.delta = f32(delta);
+  a.dq = bf(dq); a.dk = bf(dk); a.dv = bf(dv);
+  a.sdb = dO.stride(0); a.sds = dO.stride(1); a.sdh = dO.stride(2);
+  a.sgqb = dq.stride(0); a.sgqs = dq.stride(1); a.sgqh = dq.stride(2);
+  a.sgkb = dk.stride(0); a.sgks = dk.stride(1); a.sgkh = dk.stride(2);
+  a.sgvb = dv.stride(0); a.sgvs = dv.stride(1); a.sgvh = dv.stride(2);
+  a.scale = (float)scale;
+  Tensor dkv_ws;
+  if (a.dkv_split > 1) {
+    dkv_ws = torch::empty({a.dkv_split, 2, B, Hkv, Sk, D}, q.options().dtype(at::kFloat));
+    a.dkv_ws = f32(dkv_ws);
+  }
+  Tensor cpart;
+  if (dbias) {
+    cpart = torch::empty({B, Wp}, q.options().dtype(at::kFloat));
+    a.cpart = f32(cpart);
+    a.cpart_ld = (int)Wp;
+  }
+  launch_flash_bwd(a, (int)D, cbf(o), o.stride(0), o.stride(1), o.stride(2), cur_stream());
+  if (dbias) launch_colsum_fold(a.cpart, (int)B, a.cpart_ld, f32(*dbias), false, cur_stream());
+  return {dq, dk, dv};
+}
+
+}  // namespace
+
+void bind_attention(pybind11::module_& m) {
+  m.def("flash_fwd", &flash_fwd, "q"_a, "k"_a, "v"_a, "causal"_a, "kv_lens"_a, "scale"_a, "drop_state"_a = py::none(),
+        "drop_thr"_a = 0, "drop_scale"_a = 1.0, "drop_site"_a = 0);
+  m.def("flash_bwd", &flash_bwd, "dO"_a, "q"_a, "k"_a, "v"_a, "o"_a, "lse"_a, "causal"_a, "kv_lens"_a, "scale"_a,
+        "dqkv"_a = py::none(), "dbias"_a = py::none(), "drop_state"_a = py::none(), "drop_thr"_a = 0,
+        "drop_scale"_a = 1.0, "drop_site"_a = 0);
+  m.def("flash_bwd_one_block", [](int64_t D, int64_t Sq, int64_t Sk, int64_t Hq, int64_t Hkv, bool causal, int64_t B) {
+          return k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv,
+                                              k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal));
+        }, "whether flash_bwd runs as the one-block short-sequence kernel (which can also emit the packed bias gradient)");
+}
+
+}  // namespace k8s_amd::binding

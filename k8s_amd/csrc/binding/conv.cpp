@@ -1,0 +1,205 @@
+// Convolution (NHWC x, KRSC w): forward, inference with a folded BatchNorm, the data gradients' parity sub-grid
+// products and weight transforms, the 3x3 staged-window data gradient with BatchNorm-backward sums, weight gradients.
+#include "binding/common.h"
+
+namespace k8s_amd::binding {
+namespace {
+
+int conv_out(int in, int k, int st, int pad, int dil) { return (in + 2 * pad - dil * (k - 1) - 1) / st + 1; }
+
+struct ConvGeom {
+  int N, H, W, C, K, R, S;
+};
+// x [N, H, W, C] against a weight-shaped [K, R, S, C] tensor (w, or a weight gradient); C % 8 == 0 and K % 8 == 0
+ConvGeom conv_geom(const Tensor& x, const Tensor& w) {
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "x [N,H,W,C], w [K,R,S,C]");
+  ConvGeom g{(int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3),
+             (int)w.size(0), (int)w.size(1), (int)w.size(2)};
+  TORCH_CHECK(w.size(3) == g.C, "channel mismatch");
+  TORCH_CHECK(g.C % 8 == 0 && g.K % 8 == 0, "implicit-GEMM conv needs C % 8 == 0 and K % 8 == 0");
+  return g;
+}
+Tensor conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad, int64_t dil, bool out_f32, OptTensor bias, int64_t act,
+                OptTensor stats, OptTensor xform) {
+  check_bf16(x, "x"); check_bf16(w, "w");
+  const auto [N, H, W, C, K, R, S] = conv_geom(x, w);
+  TORCH_CHECK(stride >= 1 && dil >= 1, "conv_fwd: stride >= 1, dilation >= 1");
+  const int Ho = conv_out(H, R, stride, pad, dil), Wo = conv_out(W, S, stride, pad, dil);
+  if (bias) check_channel_f32(*bias, K, "bias");
+  if (stats) check_stat_sums(*stats, K, "stats", true);
+  const float* xf = xform_ptr(xform, C);
+  if (xf) TORCH_CHECK(C % 64 == 0 && !out_f32 && !bias && act == 0,
+                      "normalize-on-load convolution: C % 64 == 0, bf16 output, no bias / activation");
+  auto y = torch::empty({N, Ho, Wo, K}, x.options().dtype(out_f32 ? at::kFloat : at::kBFloat16));
+  launch_conv_fwd(cbf(x), cbf(w), y.data_ptr(), out_f32, N, H, W, C, K, R, S, (int)stride, (int)pad, (int)dil, Ho, Wo,
+                  optf(bias), (int)act, 0, stats ? f32(*stats) : nullptr, cur_stream(), nullptr, xf);
+  return y;
+}
+
+// Inference convolution with the following BatchNorm folded into the epilogue (gemm.hip IEPI):
+//   y = act(bf16(conv(x, w) * scale + shift) + res); scale / shift fp32 [K], res bf16 [N, Ho, Wo, K] or None.
+// Always the tile kernel; a shape outside its contract raises. `out`: write into this bf16 [N, Ho, Wo, K] tensor.
+Tensor conv_infer(Tensor x, Tensor w, int64_t stride, int64_t pad, Tensor scale, Tensor shift, OptTensor res,
+                  bool relu, OptTensor out) {
+  check_bf16_dense(x, 4, "x"); check_bf16_dense(w, 4, "w");
+  const auto [N, H, W, C, K, R, S] = conv_geom(x, w);
+  TORCH_CHECK(stride >= 1 && pad >= 0, "conv_infer: stride >= 1, pad >= 0");
+  check_channel_f32(scale, K, "scale"); check_channel_f32(shift, K, "shift");
+  TORCH_CHECK(H + 2 * pad >= R && W + 2 * pad >= S, "conv_infer: the filter does not fit the padded image");
+  const int Ho = conv_out(H, R, stride, pad, 1), Wo = conv_out(W, S, stride, pad, 1);
+  TORCH_CHECK((long)N * Ho * Wo < (1L << 31), "conv_infer: fewer than 2^31 output pixels");
+  const std::vector<int64_t> oshape{N, Ho, Wo, K};
+  if (out) {
+    check_bf16_dense(*out, 4, "out");
+    TORCH_CHECK(out->sizes().vec() == oshape, "out must be [N, Ho, Wo, K]");
+  }
+  if (res) {
+    check_bf16_dense(*res, 4, "res");
+    TORCH_CHECK(res->sizes().vec() == oshape, "res must have the output's shape [N, Ho, Wo, K]");
+  }
+  Tensor y = out ? *out : torch::empty(oshape, x.options());
+  launch_conv_infer(cbf(x), cbf(w), bf(y), N, H, W, C, K, R, S, (int)stride, (int)pad, Ho, Wo, f32(scale), f32(shift),
+                    res ? cbf(*res) : nullptr, relu, cur_stream());
+  return y;
+}
+
+// out[n, i*stride + a, j*stride + b, :] (+)= conv(x, w, stride 1, pad)[n, i, j, :] over an Hs x Ws grid (i < Hs,
+// j < Ws): one output parity of a stride-s data gradient. x is dy, w [C, Tr, Ts, K] holds the taps of that parity
+// (ops/conv.py _dgrad_strided_hip builds it) and out is the full bf16 dx [N, H, W, C]; `accumulate` adds onto out in
+// the epilogue (out already holds the residual branch's gradient).
+void conv_fwd_subgrid(Tensor x, Tensor w, int64_t pad, int64_t Hs, int64_t Ws, Tensor out, int64_t stride, int64_t a,
+                      int64_t b, bool accumulate, OptTensor bn_x, OptTensor bn_mask, OptTensor bn_mean,
+                      OptTensor bn_sums, OptTensor bn_gamma, OptTensor bn_beta, OptTensor bn_invstd) {
+  check_bf16(x, "x"); check_bf16(w, "w"); check_bf16(out, "out");
+  const auto [N, H, W, C, K, R, S] = conv_geom(x, w);
+  TORCH_CHECK(out.dim() == 4 && out.size(0) == N && out.size(3) == K, "out shape");
+  const int OH = out.size(1), OW = out.size(2);
+  TORCH_CHECK(stride >= 1 && a >= 0 && a < stride && b >= 0 && b < stride, "parity out of range");
+  TORCH_CHECK(Hs >= 1 && Ws >= 1 && (Hs - 1) * stride + a < OH && (Ws - 1) * stride + b < OW,
+              "sub-grid exceeds the output image");
+  k8s_amd::SubGrid sg{OH, OW, (int)stride, (int)a, (int)b};
+  // bn_*: a BatchNorm's backward sums over `out` (gemm.hip BST sub-grid path). mask kind (bn_mask, accumulate): the
+  // correction of a residual BatchNorm's sums for the elements this accumulating product changes (the first data
+  // gradient into `out` took the sums over its values). relu kind (bn_gamma / bn_beta / bn_invstd, a plain store):
+  // the sums of a BatchNorm + ReLU over this parity's stored pixels (the parities partition the output).
+  k8s_amd::BnBwdSums bb;
+  if (bn_sums) {
+    TORCH_CHECK(bn_x && bn_mean, "bn sums: bn_x and bn_mean");
+    TORCH_CHECK(bn_mask ? accumulate : !accumulate,
+                "bn sums: bn_mask + accumulate (a correction) or bn_gamma / bn_beta / bn_invstd + a plain store");
+    TORCH_CHECK(bn_x->sizes() == out.sizes(), "bn_x: the shape of out");
+    bb = bn_bwd_sums(*bn_x, *bn_mean, *bn_sums, bn_mask, bn_gamma, bn_beta, bn_invstd, {}, {}, {});
+  }
+  launch_conv_fwd(cbf(x), cbf(w), out.data_ptr(), false, N, H, W, C, K, R, S, 1, (int)pad, 1, (int)Hs, (int)Ws, nullptr,
+                  0, accumulate ? 1 : 0, nullptr, cur_stream(), &sg, nullptr, bn_sums ? &bb : nullptr);
+}
+
+// 3x3 / stride-1 / pad-1 data gradient dx = conv(gy, wt) on the staged-window kernel (wt = conv_dgrad_wtrans(w))
+// that also accumulates the BatchNorm-backward sums of dx for the non-residual BatchNorm + ReLU relu(BN(x)) that
+// produced the convolution's input (conv3x3.hip epilogue): sums[r][0][c] += sum g, sums[r][1][c] += sum g (x - mean),
+// g = relu_on(x) ? dx : 0. sums: zeroed fp32 [conv_stat_replicas, 2, C].
+Tensor conv3x3_dgrad_bnstats(Tensor gy, Tensor wt, Tensor x, Tensor gamma, Tensor beta, Tensor mean, Tensor invstd,
+                             Tensor sums) {
+  check_bf16_dense(gy, 4, "gy"); check_bf16_dense(wt, 4, "wt"); check_bf16_dense(x, 4, "x");
+  const int N = (int)gy.size(0), H = (int)gy.size(1), W = (int)gy.size(2), Kc = (int)gy.size(3);
+  const int C = (int)wt.size(0);
+  TORCH_CHECK(wt.size(1) == 3 && wt.size(2) == 3 && wt.size(3) == Kc, "wt: [C, 3, 3, K]");
+  TORCH_CHECK(x.size(0) == N && x.size(1) == H && x.size(2) == W && x.size(3) == C, "x: the shape of dx");
+  TORCH_CHECK(k8s_amd::conv3x3_eligible(H, W, Kc, C, 3, 3, 1, 1, 1), "conv3x3_dgrad_bnstats: outside the kernel");
+  const k8s_amd::BnBwdSums bb = bn_bwd_sums(x, mean, sums, {}, gamma, beta, invstd, {}, {}, {});
+  Tensor dx = torch::empty({N, H, W, C}, gy.options());
+  launch_conv3x3(cbf(gy), cbf(wt), bf(dx), nullptr, nullptr, N, H, W, Kc, C, cur_stream(), &bb);
+  return dx;
+}
+
+// dw[K,R,S,C] fp32 (+)= dy^T . im2col(x)
+void conv_wgrad(Tensor x, Tensor dy, Tensor dw, int64_t stride, int64_t pad, int64_t dil, int64_t splits,
+                bool accumulate, OptTensor xform) {
+  check_bf16(x, "x"); check_bf16(dy, "dy");
+  check_cuda(dw, "dw"); check_dtype(dw, at::kFloat, "dw");
+  const auto [N, H, W, C, K, R, S] = conv_geom(x, dw);
+  TORCH_CHECK(stride >= 1 && dil >= 1, "conv_wgrad: stride >= 1, dilation >= 1");
+  const int Ho = conv_out(H, R, stride, pad, dil), Wo = conv_out(W, S, stride, pad, dil);
+  TORCH_CHECK(dy.dim() == 4 && dy.size(0) == N && dy.size(1) == Ho && dy.size(2) == Wo && dy.size(3) == K,
+              "dy shape mismatch");
+  const float* xf = xform_ptr(xform, C);
+  if (dil == 1 && Ho == H && Wo == W && H == W && k8s_amd::wgrad3x3_tiled_ok(C, K, R, S, (int)stride, (int)pad, W)) {
+    auto wsp = torch::empty({k8s_amd::wgrad3x3_tiled_workspace(N, H, W, C)}, dw.options());
+    launch_wgrad3x3_tiled(cbf(x), cbf(dy), f32(wsp), f32(dw), N, H, W, C, accumulate, cur_stream(), xf);
+    return;
+  }
+  if (!xf && dil == 1 && k8s_amd::wgrad_stream_eligible(N, Ho, Wo, C, K, R, S)) {
+    launch_wgrad_stream(cbf(x), cbf(dy), f32(dw), N, H, W, C, K, R, S, (int)stride, (int)pad, Ho, Wo, accumulate,
+                        cur_stream());
+    return;
+  }
+  if (xf) TORCH_CHECK(C % 64 == 0, "normalize-on-load weight gradient needs C % 64 == 0");
+  int sp = splits <= 0 ? k8s_amd::gemm_choose_splits(K, R * S * C, N * Ho * Wo) : (int)splits;
+  Tensor ws;
+  if (sp > 1) ws = torch::empty({k8s_amd::gemm_splitk_workspace(K, R * S * C, sp)}, dw.options());
+  launch_conv_wgrad(cbf(x), cbf(dy), f32(dw), N, H, W, C, K, R, S, (int)stride, (int)pad, (int)dil, Ho, Wo, sp,
+                    accumulate, sp > 1 ? f32(ws) : nullptr, cur_stream(), xf);
+}
+
+// taps: per parity, the list of r*S + s tap indices (row-major over its [Tr][Ts] grid); returns one packed bf16
+// buffer with parity p's [C, T_p, K] sub-weight at the element offset offsets[p]
+std::vector<Tensor> conv_dgrad_wsub(Tensor w, std::vector<std::vector<int64_t>> taps) {
+  check_bf16(w, "w");
+  TORCH_CHECK(w.dim() == 4, "w [K,R,S,C]");
+  const int K = w.size(0), R = w.size(1), S = w.size(2), C = w.size(3);
+  TORCH_CHECK(!taps.empty() && taps.size() <= 16, "1-16 parities");
+  k8s_amd::DgradTaps t{};
+  long off = 0;
+  std::vector<int64_t> offs;
+  for (size_t p = 0; p < taps.size(); ++p) {
+    TORCH_CHECK(!taps[p].empty() && taps[p].size() <= 16, "1-16 taps per parity");
+    t.n[p] = (int)taps[p].size();
+    t.off[p] = off;
+    offs.push_back(off);
+    for (size_t i = 0; i < taps[p].size(); ++i) {
+      TORCH_CHECK(taps[p][i] >= 0 && taps[p][i] < R * S, "tap index out of range");
+      t.rs[p][i] = (int)taps[p][i];
+    }
+    off += (long)C * t.n[p] * K;
+    off = (off + 7) / 8 * 8;  // keep every parity's sub-weight 16-B aligned
+  }
+  auto out = torch::empty({off}, w.options());
+  launch_conv_dgrad_wsub(cbf(w), bf(out), K, R * S, C, t, (int)taps.size(), cur_stream());
+  return {out, torch::tensor(offs)};
+}
+Tensor conv_dgrad_wtrans(Tensor w) {
+  check_bf16(w, "w");
+  TORCH_CHECK(w.dim() == 4, "w [K,R,S,C]");
+  const int K = w.size(0), R = w.size(1), S = w.size(2), C = w.size(3);
+  auto w2 = torch::empty({C, R, S, K}, w.options());
+  launch_conv_dgrad_wtrans(cbf(w), bf(w2), K, R, S, C, cur_stream());
+  return w2;
+}
+
+}  // namespace
+
+void bind_conv(pybind11::module_& m) {
+  m.def("conv_fwd", &conv_fwd, "x"_a, "w"_a, "stride"_a, "pad"_a, "dil"_a, "out_f32"_a, "bias"_a, "act"_a, "stats"_a,
+        "xform"_a = py::none());
+  m.def("conv_infer", &conv_infer, "x"_a, "w"_a, "stride"_a, "pad"_a, "scale"_a, "shift"_a, "res"_a = py::none(),
+        "relu"_a = true, "out"_a = py::none());
+  m.def("conv3x3_staged_ok", [](int H, int W, int C, int K, int R, int S, int stride, int pad) {
+    // the staged-window forward / data gradient (conv3x3.hip) and the tiled weight gradient (wgrad_tile.hip) both
+    // take this layer: BatchNorm + ReLU can be normalised on load in all three products
+    return k8s_amd::conv3x3_eligible(H, W, C, K, R, S, stride, pad, 1) &&
+           k8s_amd::conv3x3_eligible(H, W, K, C, R, S, stride, pad, 1) &&
+           k8s_amd::wgrad3x3_tiled_ok(C, K, R, S, stride, pad, W);
+  });
+  m.def("conv3x3_dgrad_bnstats", &conv3x3_dgrad_bnstats,
+        "3x3 stride-1 data gradient with the BatchNorm-backward sums of a relu(BN(x)) input (conv3x3.hip)");
+  m.def("conv_fwd_subgrid", &conv_fwd_subgrid, "x"_a, "w"_a, "pad"_a, "Hs"_a, "Ws"_a, "out"_a, "stride"_a, "a"_a, "b"_a,
+        "accumulate"_a = false, "bn_x"_a = py::none(), "bn_mask"_a = py::none(), "bn_mean"_a = py::none(),
+        "bn_sums"_a = py::none(), "bn_gamma"_a = py::none(), "bn_beta"_a = py::none(), "bn_invstd"_a = py::none());
+  m.def("conv_wgrad", &conv_wgrad, "x"_a, "dy"_a, "dw"_a, "stride"_a, "pad"_a, "dil"_a, "splits"_a, "accumulate"_a,
+        "xform"_a = py::none());
+  m.def("wgrad_stream_eligible", &k8s_amd::wgrad_stream_eligible, "tall-K weight-gradient kernel takes this shape");
+  m.def("conv_dgrad_wtrans", &conv_dgrad_wtrans);
+  m.def("conv_dgrad_wsub", &conv_dgrad_wsub);
+}
+
+}  // namespace k8s_amd::binding

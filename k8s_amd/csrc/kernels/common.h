@@ -145,7 +145,7 @@ inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // MI355X), queried once per device. An override (set_planner_cus, or $K8S_AMD_PLANNER_CUS read on first use)
 // replaces it for every device: a rank whose CUs are partly taken by concurrently running RCCL kernels can plan
 // for fewer, and the GPU tests force odd budgets to check that every planner stays correct off the 256 grid.
-// Defined in ops_binding.cpp's translation unit set (planner.cpp) so all kernels share one value.
+// Defined once (planner.hip) and linked with every kernel and binding object, so all of them share one value.
 int planner_cus();
 void set_planner_cus(int n);  // n <= 0: back to the device's count
 

@@ -1,6 +1,6 @@
 // Host-side launcher declarations for every gfx950 kernel translation unit.
 // The kernels themselves are compiled without any PyTorch headers (fast,
-// parallel builds); only ops_binding.cpp sees torch.
+// parallel builds); only the files of csrc/binding see torch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

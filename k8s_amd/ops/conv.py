@@ -187,8 +187,7 @@ def _dgrad_hip(C_, gy, w, padding, addend=None, bn_link=None):
         sums = _bn_sums(C_, bn_link, C, gy.device)
         dx = C_.conv3x3_dgrad_bnstats(gy, C_.conv_dgrad_wtrans(w), bn_link.x, bn_link.gamma, bn_link.beta,
                                       bn_link.mean, bn_link.invstd, sums)
-        bn_link.sums, bn_link.sums2, bn_link.dy_key = sums, None, (dx.data_ptr(), tuple(dx.shape))
-        STATS["bn_bstats"] += 1
+        bn_link.deposit(sums, None, dx)
         return dx
     if R == 1 and S == 1 and padding == 0:
         N, H, W_, _ = gy.shape
@@ -201,8 +200,7 @@ def _dgrad_hip(C_, gy, w, padding, addend=None, bn_link=None):
                 gy.reshape(-1, K), w.reshape(K, C), addend.dy.view(-1, C), addend.mask, bn_link.x.view(-1, C),
                 bn_link.mask, bn_link.mean, sums, None if sums2 is None else bn_link.x2.view(-1, C), bn_link.mean2,
                 sums2).view(N, H, W_, C)
-            bn_link.sums, bn_link.sums2, bn_link.dy_key = sums, sums2, (out.data_ptr(), tuple(out.shape))
-            STATS["bn_bstats"] += 1
+            bn_link.deposit(sums, sums2, out)
             return out
         if (masked and BSTATS_TILE_MASK and bn_link is not None and not bn_link.relu and bn_link.x is not None
                 and bn_link.mask is not None and bn_link.x.shape == (N, H, W_, C) and N * H * W_ < 2 ** 31
@@ -217,16 +215,14 @@ def _dgrad_hip(C_, gy, w, padding, addend=None, bn_link=None):
                                        bn_link.mask, bn_link.mean, sums, addend.dy.view(-1, C), addend.mask,
                                        bn_link.x2.view(-1, C) if dual else None, bn_link.mean2 if dual else None,
                                        sums2)
-            bn_link.sums, bn_link.sums2, bn_link.dy_key = sums, sums2, (out.data_ptr(), tuple(out.shape))
-            STATS["bn_bstats"] += 1
+            bn_link.deposit(sums, sums2, out)
             return out
         if (BSTATS_GEMM and bn_link is not None and bn_link.relu and bn_link.x is not None and addend is None
                 and bn_link.x.shape == (N, H, W_, C) and C_.gemm_dgrad_bnstats_ok(N * H * W_, C, K)):
             sums = _bn_sums(C_, bn_link, C, gy.device)
             out = C_.gemm_dgrad_bnstats(gy.reshape(-1, K), w.reshape(K, C), bn_link.x.view(-1, C), bn_link.gamma,
                                         bn_link.beta, bn_link.mean, bn_link.invstd, sums).view(N, H, W_, C)
-            bn_link.sums, bn_link.sums2, bn_link.dy_key = sums, None, (out.data_ptr(), tuple(out.shape))
-            STATS["bn_bstats"] += 1
+            bn_link.deposit(sums, None, out)
             return out
         if (BSTATS_ENTRY and addend is None and bn_link is not None and not bn_link.relu and not bn_link.last_full and bn_link.mask is not None
                 and bn_link.x2 is None and bn_link.x is not None and bn_link.x.shape == (N, H, W_, C)
@@ -236,8 +232,7 @@ def _dgrad_hip(C_, gy, w, padding, addend=None, bn_link=None):
             sums = _bn_sums(C_, bn_link, C, gy.device)
             out = C_.dgrad_short_bnstats(gy.reshape(-1, K), w.reshape(K, C), None, None, bn_link.x.view(-1, C),
                                          bn_link.mask, bn_link.mean, sums).view(N, H, W_, C)
-            bn_link.sums, bn_link.sums2, bn_link.dy_key, bn_link.pending = sums, None, None, True
-            STATS["bn_bstats"] += 1
+            bn_link.deposit_pending(sums)
             return out
         if masked:  # the epilogue reads dy and the mask bits itself: no materialised residual gradient
             out = torch.empty(N, H, W_, C, device=gy.device, dtype=gy.dtype)
@@ -252,8 +247,7 @@ def _dgrad_hip(C_, gy, w, padding, addend=None, bn_link=None):
             sums = _bn_sums(C_, bn_link, C, gy.device)
             C_.gemm_dgrad_bnstats_mask(gy.reshape(-1, K), w.reshape(K, C), addend.view(-1, C), bn_link.x.view(-1, C),
                                        bn_link.mask, bn_link.mean, sums)
-            bn_link.sums, bn_link.sums2, bn_link.dy_key = sums, None, (addend.data_ptr(), tuple(addend.shape))
-            STATS["bn_bstats"] += 1
+            bn_link.deposit(sums, None, addend)
             return addend
         if addend is not None:
             C_.gemm(gy.reshape(-1, K), True, w.reshape(K, C), False, addend.view(-1, C), False, None, 0, None, True,
@@ -338,10 +332,9 @@ def _dgrad_strided_hip(C_, gy, w, stride, padding, H, W, addend=None, bn_link=No
         else:
             C_.conv_fwd_subgrid(gy, wsub, -tr[0][0], Hs, Ws, dx, stride, a, b, addend is not None)
     if fix:
-        bn_link.dy_key, bn_link.pending = (dx.data_ptr(), tuple(dx.shape)), False
+        bn_link.complete(dx)
     if relu_sums:
-        bn_link.sums, bn_link.sums2, bn_link.dy_key = rsums, None, (dx.data_ptr(), tuple(dx.shape))
-        STATS["bn_bstats"] += 1
+        bn_link.deposit(rsums, None, dx)
     return dx
 
 

@@ -116,8 +116,9 @@ class BnStatLink:
     (``relu``: ResNet's bn1) read by a stride-1 3x3 convolution on the staged-window kernel (conv3x3.hip epilogue,
     g = relu_on(x) ? dy : 0 from the BatchNorm's affine). The BatchNorm's forward fills (x, mask, mean[, x2,
     mean2]) and tags y with the link (``y._k8s_bnstat``); the convolution's backward deposits the sums and the
-    identity of the dy they were taken over; the BatchNorm's backward uses them only when it receives exactly that dy
-    (so a second consumer of y, whose gradient autograd would add, falls back to the reduction)."""
+    identity of the dy they were taken over (``deposit``); the BatchNorm's backward uses them only when it receives
+    exactly that dy (``take``: so a second consumer of y, whose gradient autograd would add, falls back to the
+    reduction)."""
     __slots__ = ("x", "mask", "mean", "x2", "mean2", "invstd", "gamma", "beta", "relu", "sums", "sums2", "dy_key",
                  "store", "pending", "last_full")
 
@@ -127,12 +128,33 @@ class BnStatLink:
         self.invstd = self.gamma = self.beta = None
         self.relu = False  # a non-residual BatchNorm + ReLU (mask None: g = relu_on(x) ? dy : 0, from the affine)
         self.sums = self.sums2 = self.dy_key = None
-        # sums over the first of two data gradients into y (a stage-entry block's conv1), awaiting the second's
-        # correction (its downsample convolution, ops.conv._dgrad_strided_hip); dy_key is set only once complete
+        # sums over the first of two data gradients into y (a stage-entry block's conv1: deposit_pending), awaiting
+        # the second's correction (its downsample convolution, ops.conv._dgrad_strided_hip: complete); dy_key is set
+        # only once complete
         self.pending = False
         # two stride-1 data gradients into y (the stem pool's output, read by layer 1's conv1 and downsample): the
         # first takes no sums, the second -- accumulating onto the first -- takes them over the final tensor
         self.last_full = False
+
+    @staticmethod
+    def _key(t):
+        """The identity of the tensor a deposit's sums were taken over."""
+        return t.data_ptr(), tuple(t.shape)
+
+    def deposit(self, sums, sums2, over):
+        """The convolution's backward hands over the sums (``sums2``: the second BatchNorm's, or None) taken over the
+        data gradient ``over``."""
+        self.sums, self.sums2, self.dy_key = sums, sums2, self._key(over)
+        _conv_impl().STATS["bn_bstats"] += 1
+
+    def deposit_pending(self, sums):
+        """The sums over the first of two data gradients into y; no key until ``complete``."""
+        self.sums, self.sums2, self.dy_key, self.pending = sums, None, None, True
+        _conv_impl().STATS["bn_bstats"] += 1
+
+    def complete(self, over):
+        """The second data gradient corrected the pending sums: they now hold for the final tensor ``over``."""
+        self.dy_key, self.pending = self._key(over), False
 
     def take(self, dy):
         """(sums, sums2) if they were taken over ``dy``, else None; clears the deposit either way."""
@@ -140,7 +162,7 @@ class BnStatLink:
         self.sums = self.sums2 = self.dy_key = None
         self.x = self.mask = self.mean = self.x2 = self.mean2 = None  # the BatchNorm's backward is the last reader
         self.invstd = self.gamma = self.beta = None
-        if sums is None or key != (dy.data_ptr(), tuple(dy.shape)):
+        if sums is None or key != self._key(dy):
             return None
         return sums, sums2
 
