@@ -223,6 +223,36 @@ Tensor cast_bf16(Tensor x, OptTensor out) {
   return o;
 }
 
+// ------------------------------------------------------------------ gradient accumulation (kernels/accum.hip)
+// Two flat fp32 buffers of one layout and the 64-aligned range [lo, hi) of them a pass works on. Returns hi - lo.
+long check_accum_range(const Tensor& a, const char* a_name, const Tensor& b, const char* b_name, int64_t lo,
+                       int64_t hi) {
+  check_cuda(a, a_name); check_dtype(a, at::kFloat, a_name); check_aligned(a, a_name);
+  check_channel_f32(b, a.numel(), b_name); check_aligned(b, b_name);
+  TORCH_CHECK(a.device() == b.device(), a_name, " and ", b_name, " are on different devices");
+  TORCH_CHECK(a.data_ptr() != b.data_ptr() || a.numel() == 0, a_name, " and ", b_name, " must be different buffers");
+  TORCH_CHECK(a.numel() % 64 == 0, "flat buffer length must be a multiple of 64");
+  TORCH_CHECK(lo % 64 == 0 && hi % 64 == 0, "range [", lo, ", ", hi, ") must be 64-aligned");
+  TORCH_CHECK(0 <= lo && lo <= hi && hi <= a.numel(), "range [", lo, ", ", hi, ") is outside the ", a.numel(),
+              " elements");
+  return hi - lo;
+}
+void grad_accumulate(Tensor acc, Tensor g, int64_t lo, int64_t hi, bool first) {
+  const long n = check_accum_range(acc, "acc", g, "grad", lo, hi);
+  launch_grad_accumulate(f32(acc) + lo, f32(g) + lo, n, first, cur_stream());
+}
+void grad_fold(Tensor g, Tensor acc, int64_t lo, int64_t hi, OptTensor out_bf) {
+  const long n = check_accum_range(g, "grad", acc, "acc", lo, hi);
+  uint16_t* ob = nullptr;
+  if (out_bf && out_bf->defined()) {
+    check_bf16_dense(*out_bf, -1, "out_bf");
+    TORCH_CHECK(out_bf->device() == g.device(), "out_bf is not on the gradient's device");
+    TORCH_CHECK(out_bf->numel() >= n, "out_bf has ", out_bf->numel(), " elements, the range has ", n);
+    ob = bf(*out_bf);
+  }
+  launch_grad_fold(f32(g) + lo, f32(acc) + lo, ob, n, cur_stream());
+}
+
 }  // namespace
 
 void bind_optim(pybind11::module_& m) {
@@ -247,6 +277,10 @@ void bind_optim(pybind11::module_& m) {
   m.def("slice_sum", &slice_sum, "recv"_a, "world"_a, "out"_a = py::none(), "out_bf"_a = py::none(),
         "fp32 rank-order sum of an all-to-all's bf16 chunks");
   m.def("cast_bf16", &cast_bf16, "x"_a, "out"_a = py::none());
+  m.def("grad_accumulate", &grad_accumulate, "acc"_a, "g"_a, "lo"_a, "hi"_a, "first"_a,
+        "acc[lo:hi] = g[lo:hi] if first else acc[lo:hi] + g[lo:hi]");
+  m.def("grad_fold", &grad_fold, "g"_a, "acc"_a, "lo"_a, "hi"_a, "out_bf"_a = py::none(),
+        "g[lo:hi] += acc[lo:hi]; out_bf[:hi - lo] = bf16(g[lo:hi]) when given");
 }
 
 }  // namespace k8s_amd::binding

@@ -25,6 +25,11 @@ void launch_clip_factor(const float* stats, float max_norm, float* factor, hipSt
 void launch_slice_sum(const uint16_t* in, long n, int world, float* out, uint16_t* out_bf, hipStream_t st);
 void launch_cast_bf16(const float* in, uint16_t* out, long n, hipStream_t st);
 
+// accum.hip: gradient accumulation over n elements (a multiple of 64) of two flat fp32 buffers.
+// accumulate: acc = first ? g : acc + g. fold: g = g + acc, and out_bf = bf16(g) when given.
+void launch_grad_accumulate(float* acc, const float* g, long n, bool first, hipStream_t st);
+void launch_grad_fold(float* g, const float* acc, uint16_t* out_bf, long n, hipStream_t st);
+
 // layerwise.hip: LARS / LAMB over a work-item table, items = long[n_items][4] {flat offset, state offset, length,
 // segment}; flags = per-segment bits (1 decay, 2 low-precision copy); partial [n_items][2], sums [n_seg][2]
 constexpr int kLayerItemMax = 16384;  // elements per work item, at most

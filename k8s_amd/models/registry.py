@@ -111,6 +111,12 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
                 if "b" not in box:
                     box["b"] = make()
                 return box["b"]
+            # fresh batches are consecutive draws of one generator, so batch i is the (i + 1)-th draw: a run resumed
+            # at batch i first discards the draws an uninterrupted run made before it and then sees the same data
+            done = box.get("next", 0)
+            for _ in range(done, int(step)):
+                make()
+            box["next"] = max(done, int(step)) + 1
             return make()
 
         return get

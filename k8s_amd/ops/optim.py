@@ -388,3 +388,21 @@ class FusedLAMB(_LayerwiseOptimizer):
         self.step_count += 1
         self.set_hyper(lr, self.step_count)
 
+
+# --------------------------------------------------------------------------- gradient accumulation
+def grad_accumulate(acc: torch.Tensor, g: torch.Tensor, lo: int, hi: int, first: bool) -> None:
+    """``acc[lo:hi] = g[lo:hi] if first else acc[lo:hi] + g[lo:hi]`` on two flat fp32 buffers of one layout
+    (``csrc/kernels/accum.hip``); ``lo`` / ``hi`` are multiples of 64."""
+    if acc.is_cuda or g.is_cuda:
+        _load_ext().grad_accumulate(acc, g, lo, hi, bool(first))
+    else:
+        ref.grad_accumulate(acc, g, lo, hi, first)
+
+
+def grad_fold(g: torch.Tensor, acc: torch.Tensor, lo: int, hi: int, out_bf: Optional[torch.Tensor] = None) -> None:
+    """``g[lo:hi] = g[lo:hi] + acc[lo:hi]`` and, with ``out_bf`` (bf16, at least ``hi - lo`` elements), the same
+    pass stores ``bf16(g[lo:hi])`` at its start (round to nearest even)."""
+    if g.is_cuda or acc.is_cuda:
+        _load_ext().grad_fold(g, acc, lo, hi, out_bf)
+    else:
+        ref.grad_fold(g, acc, lo, hi, out_bf)

@@ -318,6 +318,33 @@ def grad_sumsq(g):
     return torch.stack([(gf * gf).sum(), (~torch.isfinite(gf)).sum().float()])
 
 
+# --------------------------------------------------------------------------- gradient accumulation
+def _accum_range(a, b, lo, hi):
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError("gradient accumulation works on fp32 buffers")
+    if a.numel() != b.numel() or lo % 64 or hi % 64 or not 0 <= lo <= hi <= a.numel():
+        raise ValueError("range [%d, %d) must be 64-aligned and inside two buffers of one size" % (lo, hi))
+
+
+def grad_accumulate(acc, g, lo, hi, first):
+    """acc[lo:hi] = g[lo:hi] if first else acc[lo:hi] + g[lo:hi] (whatever acc held is overwritten when first)."""
+    _accum_range(acc, g, lo, hi)
+    if first:
+        acc[lo:hi].copy_(g[lo:hi])
+    else:
+        torch.add(acc[lo:hi], g[lo:hi], out=acc[lo:hi])
+
+
+def grad_fold(g, acc, lo, hi, out_bf=None):
+    """g[lo:hi] = g[lo:hi] + acc[lo:hi]; with out_bf also out_bf[:hi - lo] = bf16(g[lo:hi]), round to nearest even."""
+    _accum_range(g, acc, lo, hi)
+    if out_bf is not None and (out_bf.dtype != torch.bfloat16 or out_bf.numel() < hi - lo):
+        raise ValueError("out_bf must be bf16 with at least hi - lo elements")
+    torch.add(g[lo:hi], acc[lo:hi], out=g[lo:hi])
+    if out_bf is not None:
+        out_bf[:hi - lo].copy_(g[lo:hi])
+
+
 # --------------------------------------------------------------------------- layer-wise optimizers (LARS / LAMB)
 # These work on one PIECE of one parameter slot at a time (a slot, or the part of it inside one owned range of a
 # sharded update); ``ops/optim.py`` walks the pieces. ``s`` is grad_scale times the clip factor, ``w`` the slot's

@@ -58,8 +58,14 @@ class _Bucket:
 
 class GradReducer:
     def __init__(self, store: ParamStore, group=None, bucket_mb: float = 64.0, enabled: Optional[bool] = None,
-                 comm_dtype: torch.dtype = torch.float32):
+                 comm_dtype: torch.dtype = torch.float32, accumulator=None):
         self.store = store
+        # gradient accumulation (parallel/accum.py): None unless it spans more than one micro-batch, and then every
+        # path below is today's
+        self.acc = accumulator if (accumulator is not None and accumulator.active) else None
+        if self.acc is not None and self.acc.store is not store:
+            raise ValueError("the accumulator belongs to another ParamStore")
+        self.sync = True  # this micro-batch ends in finish() (begin_step)
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.enabled = (self.world > 1) if enabled is None else enabled
@@ -130,7 +136,12 @@ class GradReducer:
                                "allreduce-" + ("bf16" if self.comm_dtype == torch.bfloat16 else "fp32"))
 
     # ------------------------------------------------------------------ step protocol
-    def begin_step(self):
+    def begin_step(self, sync: bool = True):
+        """``sync=False`` opens a non-final micro-batch of an accumulated step: deposits are counted, no bucket is
+        launched and nothing is reduced; the caller closes it with ``accumulator.accumulate(first)``."""
+        if not sync and self.acc is None:
+            raise ValueError("begin_step(sync=False) needs an accumulator with steps > 1")
+        self.sync = sync
         self.store.begin_step()
         for b in self.buckets:
             b.pending = sum(p.uses for p in b.params)
@@ -143,7 +154,7 @@ class GradReducer:
         if b is None:
             return
         b.pending -= 1
-        if self.enabled:
+        if self.enabled and self.sync:
             self._launch_ready()
 
     def _launch_ready(self):
@@ -151,10 +162,12 @@ class GradReducer:
             b = self.buckets[self.next_launch]
             if b.pending > 0:
                 return
-            self._launch(b)
+            self._launch(b, fold=self.acc is not None)
             self.next_launch += 1
 
-    def _launch(self, b: _Bucket):
+    def _launch(self, b: _Bucket, fold: bool = False):
+        """``fold``: an accumulated step's last micro-batch -- the running sum of the earlier ones is added to the
+        bucket right before its collective (the bf16 transport's cast is part of that pass)."""
         if b.launched:
             return
         b.launched = True
@@ -167,7 +180,10 @@ class GradReducer:
             send, recv = self.pool.acquire(b.index, total, t.device)
             if total != length:
                 send[length:].zero_()
-            cast_bf16(t, send[:length])
+            if fold:
+                self.acc.fold(b.lo, b.hi, send[:length])
+            else:
+                cast_bf16(t, send[:length])
             w = dist.all_to_all_single(recv, send, group=self.group, async_op=True)
             if self.side is None:
                 self.works.append((b, send, recv, w))
@@ -185,11 +201,16 @@ class GradReducer:
             self.pool.release(b.index, self.side)  # the next step's cast waits for this on the device
             self.side_busy = True
         else:
+            if fold:
+                self.acc.fold(b.lo, b.hi)
             op = dist.ReduceOp.MAX if self.fault else dist.ReduceOp.SUM
             self.works.append((b, None, None, dist.all_reduce(t, op=op, group=self.group, async_op=True)))
 
     def finish(self):
-        """Zero never-used gradients, flush remaining buckets, order the current stream after RCCL."""
+        """Zero never-used gradients, flush remaining buckets, order the current stream after RCCL. With an
+        accumulator every bucket that no launch folded (all of them when the reducer is disabled) is folded here."""
+        if not self.sync:
+            raise RuntimeError("finish() closes a begin_step(sync=True) micro-batch")
         for b in self.buckets:
             if b.pending > 0:
                 for p in b.params:
@@ -199,6 +220,12 @@ class GradReducer:
                 b.pending = 0
         if self.enabled:
             self._launch_ready()
+        if self.acc is not None:
+            for b in self.buckets:
+                if not b.launched:
+                    self.acc.fold(b.lo, b.hi)
+            self.acc.end_step((b.lo, b.hi) for b in self.buckets)
+        if self.enabled:
             self._drain()
         self.works = []
 
@@ -223,7 +250,8 @@ class GradReducer:
 
     @property
     def grad_scale(self) -> float:
-        return 1.0 / self.world if self.enabled else 1.0
+        s = 1.0 / self.world if self.enabled else 1.0
+        return s * self.acc.scale if self.acc is not None else s
 
 
 def transport_check(grad: torch.Tensor, lo: int, hi: int, cmp: Tuple[int, int], run: Callable[[], None],

@@ -82,8 +82,13 @@ class _Range:
 class ShardedParameterService:
     def __init__(self, store: ParamStore, optimizer, group=None, bucket_mb: float = 64.0,
                  comm_dtype: torch.dtype = torch.float32, zero1: bool = True, pull: str = "auto",
-                 enabled: Optional[bool] = None):
+                 enabled: Optional[bool] = None, accumulator=None):
         self.store, self.opt, self.group = store, optimizer, group
+        # gradient accumulation (parallel/accum.py): None unless it spans more than one micro-batch
+        self.acc = accumulator if (accumulator is not None and accumulator.active) else None
+        if self.acc is not None and self.acc.store is not store:
+            raise ValueError("the accumulator belongs to another ParamStore")
+        self.sync = True  # this micro-batch ends in step() (begin_step)
         init = dist.is_available() and dist.is_initialized()
         self.world = dist.get_world_size(group) if init else 1
         self.rank = dist.get_rank(group) if init else 0
@@ -148,7 +153,12 @@ class ShardedParameterService:
         return [self.shard(b) for b in self.buckets]
 
     # ---------------------------------------------------------------- step protocol
-    def begin_step(self):
+    def begin_step(self, sync: bool = True):
+        """``sync=False`` opens a non-final micro-batch of an accumulated step: deposits are counted, nothing is
+        pushed; the caller closes it with ``accumulator.accumulate(first)``."""
+        if not sync and self.acc is None:
+            raise ValueError("begin_step(sync=False) needs an accumulator with steps > 1")
+        self.sync = sync
         # (no wait for the last pull here: each bucket is waited by the first forward layer that reads it,
         # ``Param.weight``, and the rest by ``step`` before the optimizer rewrites the working copy)
         self.store.begin_step()
@@ -161,20 +171,29 @@ class ShardedParameterService:
     def _on_deposit(self, p):
         for b in self.buckets_of.get(p.index, ()):
             b.pending -= 1
-        self._launch_ready()
+        if self.sync:
+            self._launch_ready()
 
     def _launch_ready(self):
         while self.next_launch < len(self.buckets) and self.buckets[self.next_launch].pending <= 0:
-            self._push(self.buckets[self.next_launch])
+            self._push(self.buckets[self.next_launch], fold=self.acc is not None)
             self.next_launch += 1
 
-    def _push(self, b: _Range):
+    def _push(self, b: _Range, fold: bool = False):
+        """``fold``: an accumulated step's last micro-batch -- the running sum of the earlier ones is added to the
+        range right before its push (the bf16 transport's cast is part of that pass). ``step`` pushes every range
+        that backward left, so each is folded exactly once, with or without collectives."""
         if not self.active:
+            if fold:
+                self.acc.fold(b.lo, b.hi)
             return
         g = self.store.grad[b.lo:b.hi]
         if self.comm_dtype == torch.bfloat16:
             send, recv = self.pool.acquire(b.index, b.hi - b.lo, g.device)
-            cast_bf16(g, send)
+            if fold:
+                self.acc.fold(b.lo, b.hi, send)
+            else:
+                cast_bf16(g, send)
             w = dist.all_to_all_single(recv, send, group=self.group, async_op=True)
             if self.side is not None:
                 lo, hi = self.shard(b)
@@ -187,6 +206,8 @@ class ShardedParameterService:
             else:
                 self.a2a.append((b, send, recv, w))
         else:
+            if fold:
+                self.acc.fold(b.lo, b.hi)
             lo, hi = self.shard(b)  # in place: the output is this rank's slice of the input
             op = dist.ReduceOp.MAX if self.fault else dist.ReduceOp.SUM
             self.works.append(dist.reduce_scatter_tensor(self.store.grad[lo:hi], g, op=op, group=self.group,
@@ -337,6 +358,8 @@ class ShardedParameterService:
 
     def step(self, lr: Optional[float] = None):
         """Finish the pushes, update the owned shards, pull the new weights."""
+        if not self.sync:
+            raise RuntimeError("step() closes a begin_step(sync=True) micro-batch")
         s = self.store
         for b in self.buckets:  # parameters never used this step contribute zero gradient
             if b.pending > 0:
@@ -346,6 +369,8 @@ class ShardedParameterService:
                         p.written = True
                 b.pending = 0
         self._launch_ready()
+        if self.acc is not None:
+            self.acc.end_step((b.lo, b.hi) for b in self.buckets)
         self._finish_pushes()
         # buckets of the last pull that no forward layer read: the optimizer below rewrites their owned slices
         self.store.wait_pending()
@@ -353,7 +378,7 @@ class ShardedParameterService:
         if self.active:
             def reduce(stats):
                 dist.all_reduce(stats, group=self.group)
-        self.opt.step(grad_scale=1.0 / self.world, lr=lr, ranges=self.owned_ranges, stats_reduce=reduce)
+        self.opt.step(grad_scale=self.grad_scale, lr=lr, ranges=self.owned_ranges, stats_reduce=reduce)
         if self.active:
             if self.pull == "lowp":
                 self._pull_lowp()
@@ -361,6 +386,11 @@ class ShardedParameterService:
                 # fp32 master (the CPU's fp32 compute reads it) then the bf16 copy locally
                 self._pull(s.master)
                 s.refresh_lowp()
+
+    @property
+    def grad_scale(self) -> float:
+        s = 1.0 / self.world
+        return s * self.acc.scale if self.acc is not None else s
 
     def _pull(self, buf: torch.Tensor):
         works = []

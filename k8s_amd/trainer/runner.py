@@ -11,7 +11,7 @@ process exit code (`/root/reference/pkg/trainer/training.go:45-73`):
 * data-parallel strategies: ``allreduce`` (bucketed RCCL all-reduce
   overlapped with backward, ``parallel/ddp.py``) or ``ps`` (sharded parameter
   service: reduce-scatter push / owner update / all-gather pull,
-  ``parallel/ps.py``);
+  ``parallel/ps.py``); ``--accum-steps N`` runs N micro-batches per optimizer step (``parallel/accum.py``);
 * optimizers: fused SGD / Adam, or their layer-wise adaptive forms for large global batches (``--optimizer lars`` /
   ``lamb``); learning rate: linear warmup, then constant, polynomial or cosine decay (``trainer/schedule.py``);
 * exit codes: 0 success; 1 permanent (bad config, numerics, OOM -- the
@@ -105,6 +105,10 @@ def parse(argv=None):
                          "recipe uses 0.1); masks are a function of (--seed, rank, step), so a resumed or graphed run "
                          "draws the same ones")
     ap.add_argument("--fresh-batches", action="store_true", help="draw a new synthetic batch every step")
+    ap.add_argument("--accum-steps", type=int, default=1,
+                    help="gradient accumulation: micro-batches of --batch per optimizer step (global batch = batch x "
+                         "world x N). A step stays an optimizer step everywhere (--steps, warmup, logging, "
+                         "checkpoints); not with --graph")
     ap.add_argument("--graph", action="store_true", default=os.environ.get("K8S_AMD_GRAPH", "0") == "1",
                     help="capture the whole step in a hipGraph after warmup (single rank, all-reduce strategy)")
     ap.add_argument("--eval-every", type=int, default=0,
@@ -333,6 +337,11 @@ def train(a) -> int:
         config_error = "--eval-batches and --eval-batch must be positive"
     elif a.eval_every < 0:
         config_error = "--eval-every must be >= 0"
+    elif a.accum_steps < 1:
+        config_error = "--accum-steps must be >= 1"
+    elif a.accum_steps > 1 and a.graph:
+        config_error = "--accum-steps > 1 cannot be combined with --graph (capturing a step of several " \
+                       "micro-batches is not supported)"
     elif not 0.0 <= a.dropout < 1.0:
         config_error = "--dropout must be in [0, 1)"
     elif a.dropout > 0 and not a.model.startswith("bert"):
@@ -368,7 +377,8 @@ def train(a) -> int:
     metrics = _Metrics(a.logdir, chief)
     metrics.event(event="start", rank=rank, world=world, role=info.role, model=a.model, strategy=a.strategy,
                   device=str(dev), start_time=t_start, process_start_time=t_proc, zero1=bool(sharded and world > 1), grad_comm=comm,
-                  optimizer=opt_name, lr_schedule=a.lr_schedule, batch=batch, dropout=a.dropout)
+                  optimizer=opt_name, lr_schedule=a.lr_schedule, batch=batch, dropout=a.dropout,
+                  accum_steps=a.accum_steps, global_batch=batch * world * a.accum_steps)
 
     # the sharded parameter service needs the flat buffers divisible into world equal 64-aligned shards
     w = build(a.model, dev, batch, seq=a.seq, image=a.image, seed=a.seed, fixed_batch=not a.fresh_batches,
@@ -391,11 +401,17 @@ def train(a) -> int:
         torch.distributed.broadcast(w.store.master, 0)
         w.store.refresh_lowp()
     comm_dtype = torch.bfloat16 if comm == "bf16" else torch.float32
+    micro = a.accum_steps  # micro-batches per optimizer step
+    accum = None
+    if micro > 1:
+        from k8s_amd.parallel.accum import GradAccumulator
+
+        accum = GradAccumulator(w.store, micro)
     if sharded:
-        svc = ShardedParameterService(w.store, opt, bucket_mb=a.bucket_mb, comm_dtype=comm_dtype)
+        svc = ShardedParameterService(w.store, opt, bucket_mb=a.bucket_mb, comm_dtype=comm_dtype, accumulator=accum)
         begin, finish = svc.begin_step, (lambda lr_: svc.step(lr=lr_))
     else:
-        red = GradReducer(w.store, bucket_mb=a.bucket_mb, comm_dtype=comm_dtype)
+        red = GradReducer(w.store, bucket_mb=a.bucket_mb, comm_dtype=comm_dtype, accumulator=accum)
         begin = red.begin_step
 
         def finish(lr_):
@@ -413,8 +429,8 @@ def train(a) -> int:
 
         psv = PsVariables(ps_addrs)
     start_step = _restore(a, w, opt, dev, chief, world, metrics, psv, svc)
-    if a.dropout > 0:  # step t draws the same masks whether or not the run was resumed
-        w.model.drop_state.set_step(start_step)
+    if a.dropout > 0:  # step t draws the same masks whether or not the run was resumed (one draw per micro-batch)
+        w.model.drop_state.set_step(start_step * micro)
     t_ready = time.time()  # model, optimizer and data built, checkpoint restored
     if a.eval_only and start_step == 0:  # (start_step is broadcast: every rank leaves together)
         metrics.event(event="error", error="--eval-only: no checkpoint in --ckpt-dir and no PS variable snapshot "
@@ -547,7 +563,7 @@ def train(a) -> int:
             cur_lr = lr_at(step, lr, a.warmup_steps, a.steps, a.lr_schedule, a.lr_end, a.lr_power)
             if graph is not None:
                 loss = graph(w.batch(step), cur_lr)
-            else:
+            elif accum is None:
                 with tracer.phase("step"):
                     begin()
                     with tracer.phase("data"):
@@ -556,6 +572,29 @@ def train(a) -> int:
                         loss = w.loss(inputs)
                     with tracer.phase("backward"):
                         loss.backward()
+                    with tracer.phase("reduce+update"):
+                        finish(cur_lr)
+            else:
+                # an accumulated step: micro-batch k is batch step * N + k; only the last one is reduced (its buckets
+                # fold the running sum in as they become ready), the others are added to the accumulator
+                with tracer.phase("step"):
+                    loss = None
+                    for k in range(micro):
+                        last = k == micro - 1
+                        begin(sync=last)
+                        with tracer.phase("data"):
+                            inputs = w.batch(step * micro + k)
+                        with tracer.phase("forward"):
+                            loss_k = w.loss(inputs)
+                        with tracer.phase("backward"):
+                            loss_k.backward()
+                        loss = loss_k.detach().float() if loss is None else loss + loss_k.detach().float()
+                        if not last:
+                            with tracer.phase("accumulate"):
+                                accum.accumulate(first=(k == 0))
+                            if watchdog is not None:  # kicked per micro-batch (and below, per step)
+                                watchdog.kick()
+                    loss = loss / micro  # the step's loss: the mean of its micro-batches', summed on the device
                     with tracer.phase("reduce+update"):
                         finish(cur_lr)
             n_last += 1
@@ -576,7 +615,7 @@ def train(a) -> int:
                     return EXIT_PERMANENT
                 sync()
                 now = time.time()
-                rate = n_last * w.units_per_step * world / max(now - t_last, 1e-9)
+                rate = n_last * micro * w.units_per_step * world / max(now - t_last, 1e-9)
                 if step == start_step:
                     metrics.event(event="step0", step=step, loss=loss_v, since_start=now - t_start,
                                   setup_s=round(t_ready - t_start, 4), first_step_s=round(now - t_ready, 4))
