@@ -112,6 +112,27 @@ Tensor conv3x3_dgrad_bnstats(Tensor gy, Tensor wt, Tensor x, Tensor gamma, Tenso
   return dx;
 }
 
+// The fused backward of a 1x1 / stride-1 convolution whose input is relu(BN(x)) normalised on load (bwd1x1_fused.hip):
+// returns dz [M, C] = gy [M, K] . w [K, C]; writes (accumulate: adds) dw [K, C] fp32 = gy^T . relu(bf16(x scale +
+// shift)) with xform = fp32 [2, C] (scale | shift), and adds the BatchNorm-backward sums of dz (g = relu_on(x) ? dz : 0:
+// sum g, sum g (x - mean)) into sums, zeroed fp32 [conv_stat_replicas, 2, C].
+Tensor bwd1x1_fused(Tensor gy, Tensor x, Tensor w, Tensor xform, Tensor gamma, Tensor beta, Tensor mean, Tensor invstd,
+                    Tensor dw, Tensor sums, bool accumulate) {
+  check_bf16_dense(gy, 2, "gy"); check_bf16_dense(x, 2, "x"); check_bf16_dense(w, 2, "w");
+  const long M = gy.size(0), K = gy.size(1), C = x.size(1);
+  TORCH_CHECK(x.size(0) == M && w.size(0) == K && w.size(1) == C, "shapes: gy [M, K], x [M, C], w [K, C]");
+  TORCH_CHECK(k8s_amd::bwd1x1_fused_ok(M, (int)C, (int)K),
+              "bwd1x1_fused: (C, K) = (64, 256) or (128, 512), 1 <= M < 2^31");
+  check_cuda(dw, "dw"); check_dtype(dw, at::kFloat, "dw"); check_aligned(dw, "dw");
+  TORCH_CHECK(dw.numel() == K * C, "dw must have K * C fp32 elements");
+  check_channel_f32(xform, 2 * C, "xform (BatchNorm scale | shift)");
+  const k8s_amd::BnBwdSums bb = bn_bwd_sums(x, mean, sums, {}, gamma, beta, invstd, {}, {}, {});
+  Tensor dz = torch::empty({M, C}, gy.options());
+  launch_bwd1x1_fused(cbf(gy), cbf(x), cbf(w), f32(xform), bb.gamma, bb.beta, bb.mean, bb.invstd, bf(dz), f32(dw),
+                      bb.sums, M, (int)C, (int)K, accumulate, cur_stream());
+  return dz;
+}
+
 // dw[K,R,S,C] fp32 (+)= dy^T . im2col(x)
 void conv_wgrad(Tensor x, Tensor dy, Tensor dw, int64_t stride, int64_t pad, int64_t dil, int64_t splits,
                 bool accumulate, OptTensor xform) {
@@ -197,7 +218,13 @@ void bind_conv(pybind11::module_& m) {
         "bn_sums"_a = py::none(), "bn_gamma"_a = py::none(), "bn_beta"_a = py::none(), "bn_invstd"_a = py::none());
   m.def("conv_wgrad", &conv_wgrad, "x"_a, "dy"_a, "dw"_a, "stride"_a, "pad"_a, "dil"_a, "splits"_a, "accumulate"_a,
         "xform"_a = py::none());
-  m.def("wgrad_stream_eligible", &k8s_amd::wgrad_stream_eligible, "tall-K weight-gradient kernel takes this shape");
+  m.def("bwd1x1_fused", &bwd1x1_fused, "gy"_a, "x"_a, "w"_a, "xform"_a, "gamma"_a, "beta"_a, "mean"_a, "invstd"_a,
+        "dw"_a, "sums"_a, "accumulate"_a,
+        "1x1 data gradient, normalize-on-load weight gradient and BatchNorm-backward sums in one pass (bwd1x1_fused.hip)");
+  m.def("bwd1x1_fused_ok", [](int64_t M, int64_t C, int64_t K) {
+    return C <= 1024 && K <= 4096 && k8s_amd::bwd1x1_fused_ok(M, (int)C, (int)K);
+  }, "M"_a, "C"_a, "K"_a, "whether bwd1x1_fused takes this shape");
+  m.def("wgrad_stream_eligible",&k8s_amd::wgrad_stream_eligible, "tall-K weight-gradient kernel takes this shape");
   m.def("conv_dgrad_wtrans", &conv_dgrad_wtrans);
   m.def("conv_dgrad_wsub", &conv_dgrad_wsub);
 }

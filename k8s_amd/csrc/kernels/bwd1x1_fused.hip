@@ -1,0 +1,355 @@
+// K2 fused backward of a 1x1 convolution whose input BatchNorm + ReLU is normalised on load (ResNet-50's conv3 at
+// 56x56 and 28x28: C = 64 -> K = 256 and C = 128 -> K = 512). One pass over gy [M][K] and x [M][C] gives
+//
+//   dz[m][c]  = sum_k gy[m][k] w[k][c]                               bf16, rounded once
+//   dW[k][c] (+)= sum_m gy[m][k] z[m][c],  z = bf16(relu(fma(x, scale, shift)))   fp32 (gemm.hip XForm rounding)
+//   sums[.][0][c] += sum_m g,  sums[.][1][c] += sum_m g (x - mean),  g = relu_on(x) ? stored dz : 0
+//
+// where the weight gradient (gemm.hip, xform_b) followed by the data gradient with the BatchNorm-backward sums
+// (gemm_dgrad_bnstats) read gy and x twice: 13.6 GB against 7.4 GB at batch 3072 / 56x56, the wide tensor being gy.
+//
+//  * Persistent grid, one 512-thread workgroup per CU (planner_cus()), walking row tiles pair + i * npairs. A
+//    workgroup owns 64 channels: C = 128 runs as two workgroups per row tile (the products and the sums are
+//    independent per channel), placed on one XCD (bid % 8) and adjacent in dispatch order so that the gy tile they
+//    share comes from HBM once and from L2 after (wgrad_stream.hip places its tiles the same way).
+//  * A stage is RS rows of gy (K-major, 16-B units XOR-swizzled by swz_g(row)) and of x (128-B rows, swz128), filled by
+//    global_load_lds into a ring of NSLOT stages with counted vmcnt waits and raw barriers; rows past M are
+//    zero-filled from a zero line (the transposed reads need EXEC all ones, and a zero gy row makes its dz, its share
+//    of dW and of the sums zero whatever relu(shift) the x row becomes).
+//  * dz: w never enters LDS. Wave (rh, ct) keeps the fragments of w[:, 16 channels] in registers for the whole walk
+//    (K / 32 x 4 VGPRs) as the MFMA's A operand and reads its rows of the gy tile K-major with ds_read_b128; the
+//    result lands as 4 channels x 1 row per lane, goes to a bf16 staging tile, and leaves in full 128-B rows.
+//  * One element pass per stage (thread = one 16-B unit, fixed channels for the whole walk): reads the staged dz and
+//    the raw x unit, stores dz, adds the sums in registers, and overwrites the x unit in place with z.
+//  * dW: wave w owns K / 8 rows of dW x 64 channels in accumulators across the walk; both operands are read
+//    transposed (ds_read_b64_tr_b16) from the same gy image and the z image, as in wgrad_stream.hip. The partials
+//    leave once per workgroup through fp32 atomics (16 MB chip-wide at K = 256, 32 MB at K = 512).
+//  * swz_g serves both read patterns of the gy image: the 16 rows of a ds_read_b128 lane group get 16 distinct units
+//    of a 256-B bank row, and the 8 rows of a transposed read's 32-lane group (r..r+3, r+8..r+11) 8 distinct 32-B pairs.
+//    Measured (rocprofv3 --pmc, batch 3072): SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.39 at K = 256 and 0.37 at
+//    K = 512 over the whole kernel -- more than the fragment reads' layout predicts; the 8-B staging writes of dz and
+//    the element pass have not been looked at separately.
+#include <algorithm>
+#include <stdexcept>
+
+#include "common.h"
+#include "launchers.h"
+#include "mfma.h"
+
+namespace k8s_amd {
+namespace b1f {
+
+constexpr int THREADS = 512;
+constexpr int CT = 64;  // channels per workgroup
+
+__device__ __attribute__((aligned(64))) uint16_t g_zero16[64];
+
+typedef __attribute__((ext_vector_type(4))) int int4_t;
+
+__device__ __forceinline__ int swz128(int r) { return 2 * (((r >> 1) & 1) | (((r >> 3) & 1) << 1)); }
+__device__ __forceinline__ int swz_g(int r) { return (2 * ((r & 3) | (((r >> 3) & 1) << 2))) | ((r >> 2) & 1); }
+
+struct TrRaw {
+  short4_t lo, hi;
+};
+// Transposed fragment of an [rows (m)][RB bytes] image: lane l holds column rb + (l & 15), rows kk*32 + 8*(l >> 4) + j
+template <int RB, bool G>
+__device__ __forceinline__ void tr_load(TrRaw& r, const char* img, int rb, int kk, int lane) {
+  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
+  const int u = (rb >> 3) + (p >> 1);
+  const int r0 = kk * 32 + 8 * g + q, r1 = r0 + 4;
+  const int u0 = u ^ (G ? swz_g(r0) : swz128(r0)), u1 = u ^ (G ? swz_g(r1) : swz128(r1));
+  tr16_asm(r.lo, img + r0 * RB + (u0 << 4) + (p & 1) * 8);
+  tr16_asm(r.hi, img + r1 * RB + (u1 << 4) + (p & 1) * 8);
+}
+#define K8S_LDS_TIE4(w, a, b, c, d) asm volatile(w : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
+
+struct Args {
+  const uint16_t *gy, *x, *w;
+  const float *xform, *gamma, *beta, *mean, *invstd;
+  uint16_t* dz;
+  float* dw;
+  float* sums;
+  int M, C, ntiles, npairs;
+};
+
+__device__ __forceinline__ void lds_barrier() {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+
+//   <256, 64, 3, 1>: 3 x 40 KB ring + 8 KB staging;  <512, 32, 4, 2>: 4 x 36 KB ring + 4 KB staging
+template <int K, int RS, int NSLOT, int HALVES>
+__global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
+  constexpr int RB = K * 2, UG = K / 8;
+  constexpr int IMG_G = RS * RB, IMG_X = RS * 128, STAGE = IMG_G + IMG_X, RING = NSLOT * STAGE;
+  constexpr int LG = RS * UG / THREADS;  // gy LDS-DMA per thread per stage
+  constexpr int XT = RS * 8;             // 16-B units of an x tile: the threads of the element pass
+  constexpr int NKS = K / 32, KW = K / 8, KTW = KW / 16;
+  static_assert(LG * THREADS == RS * UG && XT % 64 == 0 && XT <= THREADS && (RS == 32 || RS == 64), "tile");
+  static_assert(XT * 64 <= RING, "sums partials reuse the ring");
+  // the element pass's per-channel constants (xform scale | shift, the BatchNorm's affine pair, mean): registers, or
+  // at K = 512 -- where w's fragments and the dW accumulators take 128 -- a 5 x 64 fp32 table behind the staging tile
+  constexpr bool PLDS = K > 256;
+  __shared__ __attribute__((aligned(1024))) char smem[RING + IMG_X + (PLDS ? 5 * CT * 4 : 0)];
+  char* stg = smem + RING;
+  float* ptab = reinterpret_cast<float*>(stg + IMG_X);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int bid = blockIdx.x;
+  int pair = bid, chalf = 0;
+  if constexpr (HALVES == 2) {  // the two halves of a pair: one XCD, adjacent in dispatch order
+    const int slot = bid >> 3;
+    chalf = slot & 1;
+    pair = (slot >> 1) * 8 + (bid & 7);
+  }
+  const int c0 = chalf * CT;
+  const int n = pair < a.ntiles ? (a.ntiles - pair + a.npairs - 1) / a.npairs : 0;
+  if (n == 0) return;
+  const long M = a.M;
+  const int C = a.C;
+
+  // ---- w fragments of this wave's 16 channels: A operand of dz^T = w^T gy^T (row = channel, k = 8 (l >> 4) + j)
+  const int ct = wid & 3, rh = wid >> 2;
+  int4_t wf[NKS];
+  {
+    const uint16_t* wp = a.w + (long)(8 * (lane >> 4)) * C + c0 + ct * 16 + (lane & 15);
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      bf16x8_t v;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = (short)wp[(long)(ks * 32 + j) * C];
+      wf[ks] = __builtin_bit_cast(int4_t, v);
+    }
+  }
+  // ---- the element pass's channels: unit (tid & 7) of row tid >> 3 holds logical unit u of the 64
+  const int erow = tid >> 3;
+  const int eu = (tid & 7) ^ swz128(erow);
+  const int ecol = c0 + eu * 8;
+  float xsc[8], xsh[8], gsc[8], gsh[8], mu[8], ps[8], pq[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    xsc[j] = a.xform[ecol + j];
+    xsh[j] = a.xform[C + ecol + j];
+    mu[j] = a.mean[ecol + j];
+    bn_affine_regs(a.gamma[ecol + j], a.beta[ecol + j], mu[j], a.invstd[ecol + j], gsc[j], gsh[j]);
+    ps[j] = pq[j] = 0.f;
+  }
+  if constexpr (PLDS) {
+    if (tid < 8) {  // row 0: swz128(0) = 0, unit tid
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        ptab[0 * CT + tid * 8 + j] = xsc[j];
+        ptab[1 * CT + tid * 8 + j] = xsh[j];
+        ptab[2 * CT + tid * 8 + j] = gsc[j];
+        ptab[3 * CT + tid * 8 + j] = gsh[j];
+        ptab[4 * CT + tid * 8 + j] = mu[j];
+      }
+    }
+  }
+  // every ordinary load is consumed here, before the first LDS-DMA is issued
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(wf[ks]));
+  if constexpr (!PLDS) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(xsc[j]), "+v"(xsh[j]), "+v"(gsc[j]), "+v"(gsh[j]), "+v"(mu[j]));
+  } else {
+    __syncthreads();  // (the table's global loads are consumed by its LDS stores)
+  }
+
+  auto issue = [&](int slot, int i) {
+    char* st = smem + slot * STAGE;
+    const long m0 = (long)(pair + i * a.npairs) * RS;
+#pragma unroll
+    for (int j = 0; j < LG; ++j) {
+      const int sl = j * THREADS + tid, row = sl / UG, up = sl % UG;
+      const int u = up ^ swz_g(row);
+      const long m = m0 + row;
+      const void* src = m < M ? (const void*)(a.gy + m * K + u * 8) : (const void*)g_zero16;
+      glds16(src, st + j * (THREADS * 16) + wid * 1024);
+    }
+    if (wid < XT / 64) {
+      const long m = m0 + erow;
+      const void* src = m < M ? (const void*)(a.x + m * C + ecol) : (const void*)g_zero16;
+      glds16(src, st + IMG_G + wid * 1024);
+    }
+  };
+
+  f32x4_t dwa[KTW][4];
+#pragma unroll
+  for (int i = 0; i < KTW; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dwa[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+  const int pre = min(n, NSLOT - 1);
+  for (int s = 0; s < pre; ++s) issue(s, s);
+  int slot = 0;
+  for (int s = 0; s < n; ++s) {
+    // stage s landed: of the younger stages in flight each wave counts its LG gy loads (the x load of the waves that
+    // have one, and the dz stores, only make the wait stricter)
+    const int younger = min(n - 1, s + NSLOT - 2) - s;
+    if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LG) : "memory");
+    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LG) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    lds_barrier();  // every wave's share of stage s is in LDS; stage s-1's reads are done
+    if (s + NSLOT - 1 < n) issue(slot == 0 ? NSLOT - 1 : slot - 1, s + NSLOT - 1);  // into the slot of stage s-1
+    char* G = smem + slot * STAGE;
+    char* X = G + IMG_G;
+
+    // ---- dz tile: rows rh * RS/2 .., channels ct * 16 ..; lane holds row (l & 15), channels 4 (l >> 4) + r
+    {
+      f32x4_t d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+      const int row0 = rh * (RS / 2) + (lane & 15);
+      const int kq = lane >> 4;
+      if constexpr (RS == 64) {
+        const int row1 = row0 + 16;
+        const char* p0 = G + row0 * RB;
+        const char* p1 = G + row1 * RB;
+        const int s0 = swz_g(row0), s1 = swz_g(row1);
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+          const bf16x8_t b0 = *reinterpret_cast<const bf16x8_t*>(p0 + (((ks * 4 + kq) ^ s0) << 4));
+          const bf16x8_t b1 = *reinterpret_cast<const bf16x8_t*>(p1 + (((ks * 4 + kq) ^ s1) << 4));
+          const mfma_bf16x8 wa = __builtin_bit_cast(mfma_bf16x8, wf[ks]);
+          d0 = mfma16(wa, __builtin_bit_cast(mfma_bf16x8, b0), d0);
+          d1 = mfma16(wa, __builtin_bit_cast(mfma_bf16x8, b1), d1);
+        }
+      } else {
+        const char* p0 = G + row0 * RB;
+        const int s0 = swz_g(row0);
+#pragma unroll
+        for (int ks = 0; ks < NKS; ks += 2) {
+          const bf16x8_t b0 = *reinterpret_cast<const bf16x8_t*>(p0 + (((ks * 4 + kq) ^ s0) << 4));
+          const bf16x8_t b1 = *reinterpret_cast<const bf16x8_t*>(p0 + (((ks * 4 + 4 + kq) ^ s0) << 4));
+          d0 = mfma16(__builtin_bit_cast(mfma_bf16x8, wf[ks]), __builtin_bit_cast(mfma_bf16x8, b0), d0);
+          d1 = mfma16(__builtin_bit_cast(mfma_bf16x8, wf[ks + 1]), __builtin_bit_cast(mfma_bf16x8, b1), d1);
+        }
+        d0 += d1;
+      }
+      const int unit = ct * 2 + (lane >> 5), half = (lane >> 4) & 1;
+      auto put = [&](int row, const f32x4_t& d) {
+        bf16x4_t o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (short)f2bf(d[r]);
+        *reinterpret_cast<bf16x4_t*>(stg + row * 128 + ((unit ^ swz128(row)) << 4) + half * 8) = o;
+      };
+      put(row0, d0);
+      if constexpr (RS == 64) put(row0 + 16, d1);
+    }
+    lds_barrier();  // the staged dz tile is complete
+
+    // ---- element pass: store dz, add the sums, z over x in place
+    if (wid < XT / 64) {
+      const bf16x8_t dzv = *reinterpret_cast<const bf16x8_t*>(stg + tid * 16);
+      const bf16x8_t xv = *reinterpret_cast<const bf16x8_t*>(X + tid * 16);
+      if constexpr (PLDS) {
+        const float* t = ptab + (ecol - c0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          xsc[j] = t[j];
+          xsh[j] = t[CT + j];
+          gsc[j] = t[2 * CT + j];
+          gsh[j] = t[3 * CT + j];
+          mu[j] = t[4 * CT + j];
+        }
+      }
+      float o[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float xf = bf2f((uint16_t)xv[j]);
+        o[j] = fmaxf(__builtin_fmaf(xf, xsc[j], xsh[j]), 0.f);
+        const float g = relu_on(xf, gsc[j], gsh[j]) ? bf2f((uint16_t)dzv[j]) : 0.f;
+        ps[j] += g;
+        pq[j] = __builtin_fmaf(g, xf - mu[j], pq[j]);
+      }
+      *reinterpret_cast<bf16x8_t*>(X + tid * 16) = pack_bf16x8(o);
+      const long m = (long)(pair + s * a.npairs) * RS + erow;
+      if (m < M) *reinterpret_cast<bf16x8_t*>(a.dz + m * C + ecol) = dzv;
+    }
+    lds_barrier();  // the z tile is complete, the staging tile free
+
+    // ---- dW: rows wid * KW .. of dW (gy columns) x 64 channels
+#pragma unroll
+    for (int kk = 0; kk < RS / 32; ++kk) {
+      TrRaw ar[KTW], br[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) tr_load<128, false>(br[j], X, j * 16, kk, lane);
+#pragma unroll
+      for (int i = 0; i < KTW; ++i) tr_load<RB, true>(ar[i], G, wid * KW + i * 16, kk, lane);
+      K8S_LDS_TIE8("s_waitcnt lgkmcnt(0)", br[0].lo, br[0].hi, br[1].lo, br[1].hi, br[2].lo, br[2].hi, br[3].lo,
+                   br[3].hi);
+#pragma unroll
+      for (int i = 0; i < KTW; i += 2)
+        K8S_LDS_TIE4("s_waitcnt lgkmcnt(0)", ar[i].lo, ar[i].hi, ar[i + 1].lo, ar[i + 1].hi);
+#pragma unroll
+      for (int i = 0; i < KTW; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          dwa[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(join8(br[j].lo, br[j].hi), join8(ar[i].lo, ar[i].hi),
+                                                              dwa[i][j], 0, 0, 0);
+    }
+    slot = slot + 1 == NSLOT ? 0 : slot + 1;
+  }
+
+  // ---- dW partials: lane holds dW[k = wid * KW + i * 16 + (lane & 15)][c0 + j * 16 + 4 (lane >> 4) + r]
+#pragma unroll
+  for (int i = 0; i < KTW; ++i) {
+    const int k = wid * KW + i * 16 + (lane & 15);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float* d = a.dw + (long)k * C + c0 + j * 16 + 4 * (lane >> 4);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) atomicAdd(d + r, dwa[i][j][r]);
+    }
+  }
+  // ---- sums: the RS threads of a channel unit fold through LDS, one atomic per (channel, sum) per workgroup
+  __syncthreads();
+  float* part = reinterpret_cast<float*>(smem);
+  if (tid < XT) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      part[tid * 16 + j] = ps[j];
+      part[tid * 16 + 8 + j] = pq[j];
+    }
+  }
+  __syncthreads();
+  if (tid < 2 * CT) {
+    const int col = tid & (CT - 1), which = tid / CT;
+    const int u = col >> 3, r = col & 7;
+    float v = 0.f;
+#pragma unroll 4
+    for (int row = 0; row < RS; ++row) v += part[(row * 8 + (u ^ swz128(row))) * 16 + which * 8 + r];
+    atomicAdd(a.sums + (long)(bid % kConvStatReplicas) * 2 * C + (long)which * C + c0 + col, v);
+  }
+}
+
+}  // namespace b1f
+
+// The contract: (C, K) = (64, 256) or (128, 512), 1 <= M < 2^31.
+bool bwd1x1_fused_ok(long M, int C, int K) {
+  return M >= 1 && M < (1L << 31) && ((C == 64 && K == 256) || (C == 128 && K == 512));
+}
+
+void launch_bwd1x1_fused(const uint16_t* gy, const uint16_t* x, const uint16_t* w, const float* xform,
+                         const float* gamma, const float* beta, const float* mean, const float* invstd, uint16_t* dz,
+                         float* dw, float* sums, long M, int C, int K, bool accumulate, hipStream_t st) {
+  using namespace b1f;
+  if (!bwd1x1_fused_ok(M, C, K)) throw std::runtime_error("bwd1x1_fused: (C, K) = (64, 256) or (128, 512), M < 2^31");
+  if (!accumulate) (void)hipMemsetAsync(dw, 0, (size_t)K * C * sizeof(float), st);
+  Args a{gy, x, w, xform, gamma, beta, mean, invstd, dz, dw, sums, (int)M, C, 0, 0};
+  const int cus = std::max(1, planner_cus());
+  if (C == 64) {
+    a.ntiles = (int)((M + 63) / 64);
+    a.npairs = cus;
+    hipLaunchKernelGGL((bwd1x1_fused_kernel<256, 64, 3, 1>), dim3(cus), dim3(THREADS), 0, st, a);
+  } else {
+    const int grid = std::max(16, cus / 16 * 16);  // pairs of workgroups, 8 pairs (one per XCD) at a time
+    a.ntiles = (int)((M + 31) / 32);
+    a.npairs = grid / 2;
+    hipLaunchKernelGGL((bwd1x1_fused_kernel<512, 32, 4, 2>), dim3(grid), dim3(THREADS), 0, st, a);
+  }
+}
+
+}  // namespace k8s_amd

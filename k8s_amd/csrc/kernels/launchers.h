@@ -247,6 +247,14 @@ void launch_conv_wgrad(const uint16_t* x, const uint16_t* dy, float* dw, int N, 
 bool wgrad_stream_eligible(int N, int Ho, int Wo, int C, int K, int R, int S);
 void launch_wgrad_stream(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, int C, int K, int R,
                          int S, int stride, int pad, int Ho, int Wo, bool accumulate, hipStream_t st);
+// bwd1x1_fused.hip: the whole backward of a 1x1 / stride-1 convolution whose input is relu(BN(x)) normalised on load,
+// in one pass over gy [M][K] and x [M][C]: dz = gy . w (bf16), dw [K][C] fp32 (+)= gy^T . relu(bf16(x scale + shift))
+// (xform = fp32 [2][C] scale | shift), and the BatchNorm-backward sums of dz (as BnBwdSums, relu kind) into the zeroed
+// sums [kConvStatReplicas][2][C]. (C, K) = (64, 256) or (128, 512), M < 2^31; dw is zeroed first unless accumulating.
+bool bwd1x1_fused_ok(long M, int C, int K);
+void launch_bwd1x1_fused(const uint16_t* gy, const uint16_t* x, const uint16_t* w, const float* xform,
+                         const float* gamma, const float* beta, const float* mean, const float* invstd, uint16_t* dz,
+                         float* dw, float* sums, long M, int C, int K, bool accumulate, hipStream_t st);
 void launch_conv_dgrad_wtrans(const uint16_t* w, uint16_t* w2, int K, int R, int S, int C, hipStream_t st);
 // per-output-parity sub-weights of a stride-s dgrad (up to 16 parities x 16 taps), packed at off[p]
 struct DgradTaps {

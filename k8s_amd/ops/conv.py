@@ -338,6 +338,19 @@ def _dgrad_strided_hip(C_, gy, w, stride, padding, H, W, addend=None, bn_link=No
     return dx
 
 
+def _bwd1x1_fused_on() -> bool:
+    """K8S_AMD_BWD1X1_FUSED=0 keeps the weight gradient and the data gradient of a normalize-on-load 1x1 convolution
+    on their two kernels (A/B, tests); read per call."""
+    return os.environ.get("K8S_AMD_BWD1X1_FUSED", "1") != "0"
+
+
+def _fused_link_ok(bn_link, x) -> bool:
+    """A relu-kind BnStatLink (the convolution's input BatchNorm + ReLU) filled for x."""
+    return (bn_link is not None and bn_link.relu and bn_link.x is not None and bn_link.x.shape == x.shape
+            and bn_link.x.data_ptr() == x.data_ptr()
+            and all(t is not None for t in (bn_link.gamma, bn_link.beta, bn_link.mean, bn_link.invstd)))
+
+
 def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None, x_sub=None, bn_link=None):
     """Returns dx (+ ``addend``, e.g. the residual branch's gradient of the same tensor, fused into the
     dgrad epilogue where our kernel runs) or None; deposits dw into ``p``'s flat gradient slot. ``xform``: the
@@ -358,6 +371,22 @@ def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None
     if addend is not None and not torch.is_tensor(addend) and not (
             hip and stride == 1 and K % 8 == 0 and C % 8 == 0):
         addend = addend.materialize()  # only the stride-1 dgrad on our kernels takes the (dy, mask) pair
+    # ---- both gradients and the BatchNorm-backward sums in one pass over gy and x (bwd1x1_fused.hip)
+    if (xform is not None and need_dx and addend is None and R == 1 and S == 1 and stride == 1 and padding == 0
+            and _bwd1x1_fused_on() and _fused_link_ok(bn_link, x) and gy.is_contiguous() and x.is_contiguous()
+            and C_.bwd1x1_fused_ok(gy.numel() // K, C, K)):
+        STATS["hip_wgrad"] += 1
+        STATS["hip_dgrad"] += 1
+        acc = p.written
+        sums = _bn_sums(C_, bn_link, C, gy.device)
+        dz = C_.bwd1x1_fused(gy.view(-1, K), x.view(-1, C), w.view(K, C), xform, bn_link.gamma, bn_link.beta,
+                             bn_link.mean, bn_link.invstd, p.grad.view(K, C), sums, acc).view(x.shape)
+        if acc:
+            p.store._notify(p)
+        else:
+            p.store.mark_written(p)
+        bn_link.deposit(sums, None, dz)
+        return dz
     # ---- weight gradient
     dw_done = False
     if hip and C % 8 == 0 and K % 8 == 0 and p is not None and p.grad.dtype == torch.float32:
