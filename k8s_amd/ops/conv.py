@@ -24,6 +24,7 @@ view; on the GPU they are counted in ``STATS`` and warned about once.
 """
 from __future__ import annotations
 
+import collections
 import os
 import warnings
 
@@ -33,12 +34,12 @@ import torch.nn.functional as F
 from k8s_amd.ops._ext import load as _load
 
 
-# (Round 2 built a BatchNorm-backward statistics epilogue for the data gradients -- the BN backward's reduction
-# pass computed in the dgrad that produces its input; it measured a net loss twice, 10.61k vs 11.00k img/s in round 2
-# and 12.02k vs 12.20k with only the long-K dgrads in round 3 (scripts/gpurun/env_ab.sh), and was removed.)
+# The data gradients also take BatchNorm-backward sums in their epilogues: nn.BnStatLink lists the link kinds and the
+# routes serving each; _plan_dgrad / _plan_dgrad_strided / _plan_bwd choose the route, ROUTES counts the ones that ran.
 
 STATS = {"hip_fwd": 0, "aten_fwd": 0, "hip_wgrad": 0, "aten_wgrad": 0, "hip_dgrad": 0, "aten_dgrad": 0,
          "bn_bstats": 0, "hip_infer": 0, "aten_infer": 0}
+ROUTES = collections.Counter()  # data-gradient route name -> times executed
 
 # (Round 5 built weight gradients on a second HIP stream -- each conv's dW kernel forked off the compute stream to
 # overlap the data gradient and BatchNorm passes after it. The streams co-ran, but the HBM-bound kernels stretched:
@@ -174,91 +175,106 @@ def _bn_sums(C_, bn_link, C, device):
     return torch.zeros(R, 2, C, device=device, dtype=torch.float32)
 
 
-def _dgrad_hip(C_, gy, w, padding, addend=None, bn_link=None):
-    """dx on our kernels; with ``addend`` (bf16, shape of dx) a 1x1 dgrad accumulates onto it in the GEMM
-    epilogue and returns it (the fused residual-gradient add). ``bn_link`` (nn.BnStatLink, with a masked addend):
-    the epilogue also accumulates the BatchNorm-backward sums of dx for the BatchNorm(s) that produced x."""
+def _link_kind(bn_link, shape):
+    """The kind of a BnStatLink that is filled, and filled for a data gradient of ``shape`` -- what every sum-taking
+    route needs first -- else None. (The fill methods of the link give each kind its fields.)"""
+    filled = bn_link is not None and bn_link.kind is not None and bn_link.x.shape == shape
+    return bn_link.kind if filled else None
+
+
+def _plan_dgrad(C_, gy, w, padding, addend, bn_link):
+    """The route of a stride-1 data gradient, by name (``_dgrad_hip`` executes it). Launches and allocates nothing:
+    reads shapes, contiguity, the addend's kind, the link's kind, the BSTATS_* switches and ``C_``'s predicates."""
     K, R, S, C = w.shape
+    N, Ho, Wo = gy.shape[:3]
     masked = addend is not None and not torch.is_tensor(addend)  # nn.MaskedGrad: (dy, packed ReLU mask)
-    if (BSTATS_3X3 and bn_link is not None and bn_link.relu and bn_link.x is not None and addend is None and R == 3
-            and S == 3
-            and padding == 1 and gy.shape[1] == gy.shape[2] and bn_link.x.shape[:3] == gy.shape[:3]
-            and C_.conv3x3_staged_ok(gy.shape[1], gy.shape[2], C, K, 3, 3, 1, 1)):
-        sums = _bn_sums(C_, bn_link, C, gy.device)
-        dx = C_.conv3x3_dgrad_bnstats(gy, C_.conv_dgrad_wtrans(w), bn_link.x, bn_link.gamma, bn_link.beta,
-                                      bn_link.mean, bn_link.invstd, sums)
-        bn_link.deposit(sums, None, dx)
-        return dx
-    if R == 1 and S == 1 and padding == 0:
-        N, H, W_, _ = gy.shape
-        if masked and bn_link is not None and not bn_link.relu and bn_link.x is not None and \
-                bn_link.x.shape == (N, H, W_, C) and \
-                C_.gemm_short_bnstats_ok(N * H * W_, C, K, bn_link.x2 is not None):
-            sums = _bn_sums(C_, bn_link, C, gy.device)
-            sums2 = _bn_sums(C_, bn_link, C, gy.device) if bn_link.x2 is not None else None
-            out = C_.dgrad_short_bnstats(
-                gy.reshape(-1, K), w.reshape(K, C), addend.dy.view(-1, C), addend.mask, bn_link.x.view(-1, C),
-                bn_link.mask, bn_link.mean, sums, None if sums2 is None else bn_link.x2.view(-1, C), bn_link.mean2,
-                sums2).view(N, H, W_, C)
-            bn_link.deposit(sums, sums2, out)
-            return out
-        if (masked and BSTATS_TILE_MASK and bn_link is not None and not bn_link.relu and bn_link.x is not None
-                and bn_link.mask is not None and bn_link.x.shape == (N, H, W_, C) and N * H * W_ < 2 ** 31
-                and (BSTATS_TILE_SHORT or bn_link.x2 is None or not C_.gemm_short_bnstats_ok(N * H * W_, C, K, False))):
-            # the same on the tile kernel: K = 512 (the stage-4 identity blocks) and the two-BatchNorm form past
-            # gemm_short's K = 128 (a downsample block's output read by the next block's conv1 at stages 3-4)
-            out = torch.empty(N, H, W_, C, device=gy.device, dtype=gy.dtype)
-            sums = _bn_sums(C_, bn_link, C, gy.device)
-            dual = bn_link.x2 is not None
-            sums2 = _bn_sums(C_, bn_link, C, gy.device) if dual else None
-            C_.gemm_dgrad_bnstats_mask(gy.reshape(-1, K), w.reshape(K, C), out.view(-1, C), bn_link.x.view(-1, C),
-                                       bn_link.mask, bn_link.mean, sums, addend.dy.view(-1, C), addend.mask,
-                                       bn_link.x2.view(-1, C) if dual else None, bn_link.mean2 if dual else None,
-                                       sums2)
-            bn_link.deposit(sums, sums2, out)
-            return out
-        if (BSTATS_GEMM and bn_link is not None and bn_link.relu and bn_link.x is not None and addend is None
-                and bn_link.x.shape == (N, H, W_, C) and C_.gemm_dgrad_bnstats_ok(N * H * W_, C, K)):
-            sums = _bn_sums(C_, bn_link, C, gy.device)
-            out = C_.gemm_dgrad_bnstats(gy.reshape(-1, K), w.reshape(K, C), bn_link.x.view(-1, C), bn_link.gamma,
-                                        bn_link.beta, bn_link.mean, bn_link.invstd, sums).view(N, H, W_, C)
-            bn_link.deposit(sums, None, out)
-            return out
-        if (BSTATS_ENTRY and addend is None and bn_link is not None and not bn_link.relu and not bn_link.last_full and bn_link.mask is not None
-                and bn_link.x2 is None and bn_link.x is not None and bn_link.x.shape == (N, H, W_, C)
-                and C_.gemm_short_bnstats_ok(N * H * W_, C, K, False)):
-            # the first of two data gradients into a residual BN's output (a stage-entry block's conv1): the sums
-            # over its values, completed by the downsample's strided dgrad (_dgrad_strided_hip)
-            sums = _bn_sums(C_, bn_link, C, gy.device)
-            out = C_.dgrad_short_bnstats(gy.reshape(-1, K), w.reshape(K, C), None, None, bn_link.x.view(-1, C),
-                                         bn_link.mask, bn_link.mean, sums).view(N, H, W_, C)
-            bn_link.deposit_pending(sums)
-            return out
-        if masked:  # the epilogue reads dy and the mask bits itself: no materialised residual gradient
-            out = torch.empty(N, H, W_, C, device=gy.device, dtype=gy.dtype)
-            C_.gemm(gy.reshape(-1, K), True, w.reshape(K, C), False, out.view(-1, C), False, None, 0, None, True,
-                    1.0, 1, add_src=addend.dy.view(-1, C), add_mask=addend.mask)
-            return out
-        if (addend is not None and bn_link is not None and bn_link.last_full and bn_link.x is not None
-                and bn_link.mask is not None and bn_link.x.shape == (N, H, W_, C) and addend.is_contiguous()
-                and C % 8 == 0 and N * H * W_ < 2 ** 31):
-            # the second of two data gradients into a BatchNorm's output (nn.BnStatLink.last_full: the stem pool's,
-            # 64 channels, the tile kernel): accumulated onto the first's, the sums taken over the final tensor
-            sums = _bn_sums(C_, bn_link, C, gy.device)
-            C_.gemm_dgrad_bnstats_mask(gy.reshape(-1, K), w.reshape(K, C), addend.view(-1, C), bn_link.x.view(-1, C),
-                                       bn_link.mask, bn_link.mean, sums)
-            bn_link.deposit(sums, None, addend)
-            return addend
-        if addend is not None:
-            C_.gemm(gy.reshape(-1, K), True, w.reshape(K, C), False, addend.view(-1, C), False, None, 0, None, True,
-                    1.0, 1)
-            return addend
-        return C_.gemm(gy.reshape(-1, K), True, w.reshape(K, C), False, None, False, None, 0, None, False, 1.0,
-                       1).reshape(N, H, W_, C)
+    kind = _link_kind(bn_link, (N, Ho + R - 1 - 2 * padding, Wo + S - 1 - 2 * padding, C))
+    if (BSTATS_3X3 and kind == "relu" and addend is None and R == 3 and S == 3 and padding == 1 and Ho == Wo
+            and C_.conv3x3_staged_ok(Ho, Wo, C, K, 3, 3, 1, 1)):
+        return "conv3x3_relu_sums"
+    if not (R == 1 and S == 1 and padding == 0):
+        return "implicit_flipped"
+    M = N * Ho * Wo
     if masked:
-        addend = addend.materialize()
-    dx = C_.conv_fwd(gy, C_.conv_dgrad_wtrans(w), 1, R - 1 - padding, 1, False, None, 0, None)
-    return dx if addend is None else dx.add_(addend)
+        residual = kind in ("mask", "dual", "pool")  # a packed ReLU mask: g = bit ? dx : 0
+        if residual and C_.gemm_short_bnstats_ok(M, C, K, kind == "dual"):
+            return "short_mask_sums"
+        # the same on the tile kernel: K = 512 (the stage-4 identity blocks) and the two-BatchNorm form past
+        # gemm_short's K = 128 (a downsample block's output read by the next block's conv1 at stages 3-4)
+        if (residual and BSTATS_TILE_MASK and M < 2 ** 31
+                and (BSTATS_TILE_SHORT or kind != "dual" or not C_.gemm_short_bnstats_ok(M, C, K, False))):
+            return "tile_mask_sums"
+        return "gemm_masked_add"
+    if addend is None:
+        if BSTATS_GEMM and kind == "relu" and C_.gemm_dgrad_bnstats_ok(M, C, K):
+            return "tile_relu_sums"
+        # the first of two data gradients into a residual BN's output (a stage-entry block's conv1): the sums over
+        # its values, completed by the downsample's strided dgrad (parity_complete_sums)
+        if BSTATS_ENTRY and kind == "mask" and C_.gemm_short_bnstats_ok(M, C, K, False):
+            return "short_entry_pending"
+        return "gemm_plain"
+    # the second of two data gradients into the stem pool's output (64 channels, the tile kernel): accumulated onto the
+    # first's, the sums taken over the final tensor
+    if kind == "pool" and addend.is_contiguous() and C % 8 == 0 and M < 2 ** 31:
+        return "tile_final_sums"
+    return "gemm_add"
+
+
+def _dgrad_hip(C_, gy, w, padding, addend=None, bn_link=None):
+    """dx on our kernels; with ``addend`` (bf16, shape of dx, or an nn.MaskedGrad) a 1x1 dgrad accumulates onto it in
+    the GEMM epilogue (the fused residual-gradient add; a tensor addend is overwritten and returned). ``bn_link``
+    (nn.BnStatLink): on the ``*_sums`` / ``*_pending`` routes the epilogue also accumulates the BatchNorm-backward sums
+    of dx for the BatchNorm(s) that produced x, and deposits them in the link."""
+    route = _plan_dgrad(C_, gy, w, padding, addend, bn_link)
+    ROUTES[route] += 1
+    K, R, S, C = w.shape
+    ln = bn_link
+    if route == "implicit_flipped":
+        if addend is not None and not torch.is_tensor(addend):
+            addend = addend.materialize()
+        dx = C_.conv_fwd(gy, C_.conv_dgrad_wtrans(w), 1, R - 1 - padding, 1, False, None, 0, None)
+        return dx if addend is None else dx.add_(addend)
+    if route == "conv3x3_relu_sums":
+        sums = _bn_sums(C_, ln, C, gy.device)
+        dx = C_.conv3x3_dgrad_bnstats(gy, C_.conv_dgrad_wtrans(w), ln.x, ln.gamma, ln.beta, ln.mean, ln.invstd, sums)
+        ln.deposit(sums, None, dx)
+        return dx
+    shape = gy.shape[:3] + (C,)
+    gy, w = gy.reshape(-1, K), w.reshape(K, C)
+    if route == "gemm_plain":
+        return C_.gemm(gy, True, w, False, None, False, None, 0, None, False, 1.0, 1).reshape(shape)
+    if route == "gemm_add":
+        C_.gemm(gy, True, w, False, addend.view(-1, C), False, None, 0, None, True, 1.0, 1)
+        return addend
+    if route == "gemm_masked_add":  # the epilogue reads dy and the mask bits itself: no materialised residual gradient
+        out = torch.empty(shape, device=gy.device, dtype=gy.dtype)
+        C_.gemm(gy, True, w, False, out.view(-1, C), False, None, 0, None, True, 1.0, 1,
+                add_src=addend.dy.view(-1, C), add_mask=addend.mask)
+        return out
+    sums, sums2, x = _bn_sums(C_, ln, C, gy.device), None, ln.x.view(-1, C)
+    if route == "tile_relu_sums":
+        out = C_.gemm_dgrad_bnstats(gy, w, x, ln.gamma, ln.beta, ln.mean, ln.invstd, sums).view(shape)
+    elif route == "short_entry_pending":
+        out = C_.dgrad_short_bnstats(gy, w, None, None, x, ln.mask, ln.mean, sums).view(shape)
+        ln.deposit_pending(sums)
+        return out
+    elif route == "tile_final_sums":
+        out = addend
+        C_.gemm_dgrad_bnstats_mask(gy, w, out.view(-1, C), x, ln.mask, ln.mean, sums)
+    else:  # short_mask_sums / tile_mask_sums: a masked addend, one or two BatchNorms' sums
+        x2 = None
+        if ln.kind == "dual":
+            sums2, x2 = _bn_sums(C_, ln, C, gy.device), ln.x2.view(-1, C)
+        add = addend.dy.view(-1, C)
+        if route == "short_mask_sums":
+            out = C_.dgrad_short_bnstats(gy, w, add, addend.mask, x, ln.mask, ln.mean, sums, x2, ln.mean2,
+                                         sums2).view(shape)
+        else:
+            out = torch.empty(shape, device=gy.device, dtype=gy.dtype)
+            C_.gemm_dgrad_bnstats_mask(gy, w, out.view(-1, C), x, ln.mask, ln.mean, sums, add, addend.mask, x2,
+                                       ln.mean2, sums2)
+    ln.deposit(sums, sums2, out)
+    return out
 
 
 def _parity_taps(R, a, pad, stride):
@@ -284,38 +300,51 @@ def strided_dgrad_ok(gy, w, stride, padding):
     return True
 
 
+def _plan_dgrad_strided(gy, w, stride, padding, H, W, addend, bn_link):
+    """The route of a strided data gradient, by name (``_dgrad_strided_hip`` executes it); launches and allocates
+    nothing. A pending link this data gradient cannot complete is cleared: its BatchNorm takes its own reduction."""
+    K, R, S, C = w.shape
+    kind = _link_kind(bn_link, (gy.shape[0], H, W, C))
+    if bn_link is not None and bn_link.pending:
+        # completing a residual BN's backward sums started by the first data gradient into `addend`
+        # (short_entry_pending): the live parity's epilogue adds the changes it makes (gemm.hip BST sub-grid path)
+        if (kind is not None and R == 1 and S == 1 and padding == 0 and torch.is_tensor(addend)
+                and addend.is_contiguous() and addend.shape == bn_link.x.shape):
+            return "parity_complete_sums"
+        bn_link.drop_pending()
+    # a BatchNorm + ReLU's sums (ResNet's bn1 before a stride-2 3x3 conv2): every parity stores its own pixels and adds
+    # the sums over them (gemm.hip BST sub-grid path, relu kind)
+    if BSTATS_STRIDED and kind == "relu" and addend is None and C > 64 and K % 64 == 0:
+        return "parity_relu_sums"
+    return "parity"
+
+
 def _dgrad_strided_hip(C_, gy, w, stride, padding, H, W, addend=None, bn_link=None):
     """dx [N, H, W, C] of a stride-s conv on our implicit-GEMM kernel, one launch per output parity.
 
     With ``addend`` (bf16 [N, H, W, C], e.g. the gradient the block input already got from the other branch)
     every parity accumulates onto it in the GEMM epilogue and it is returned: no memset for the parities no
     tap reaches (they keep the addend) and no separate add pass."""
+    route = _plan_dgrad_strided(gy, w, stride, padding, H, W, addend, bn_link)
+    ROUTES[route] += 1
     K, R, S, C = w.shape
-    N = gy.shape[0]
-    # completing a residual BN's backward sums started by the first data gradient into `addend` (nn.BnStatLink
-    # pending): the live parity's epilogue adds the changes it makes (gemm.hip BST sub-grid path)
-    fix = (bn_link is not None and bn_link.pending and R == 1 and S == 1 and padding == 0 and addend is not None
-           and torch.is_tensor(addend) and addend.is_contiguous() and bn_link.x is not None
-           and bn_link.x.shape == addend.shape)
-    if bn_link is not None and bn_link.pending and not fix:
-        bn_link.sums, bn_link.pending = None, False  # cannot complete: the BN takes its own reduction
-    # a BatchNorm + ReLU's sums (nn.BnStatLink relu kind: ResNet's bn1 before a stride-2 3x3 conv2): every parity
-    # stores its own pixels and adds the sums over them (gemm.hip BST sub-grid path, relu kind)
-    relu_sums = (BSTATS_STRIDED and bn_link is not None and bn_link.relu and bn_link.x is not None and addend is None
-                 and not bn_link.pending and bn_link.x.shape == (N, H, W, C) and C > 64 and K % 64 == 0)
-    rsums = _bn_sums(C_, bn_link, C, gy.device) if relu_sums else None
-    parities = [(a, b) for a in range(stride) for b in range(stride)]
-    empty = [(a, b) for a, b in parities
-             if not _parity_taps(R, a, padding, stride) or not _parity_taps(S, b, padding, stride)]
+    ln = bn_link
+    tail = (addend is not None,)  # conv_fwd_subgrid's last arguments: accumulate onto dx[, what the sums need]
+    if route == "parity_complete_sums":
+        tail = (True, ln.x, ln.mask, ln.mean, ln.sums)
+    elif route == "parity_relu_sums":
+        rsums = _bn_sums(C_, ln, C, gy.device)
+        tail = (False, ln.x, None, ln.mean, rsums, ln.gamma, ln.beta, ln.invstd)
+    live = [(a, b, _parity_taps(R, a, padding, stride), _parity_taps(S, b, padding, stride))
+            for a in range(stride) for b in range(stride)]
+    live = [(a, b, tr, ts) for a, b, tr, ts in live if tr and ts]
     if addend is not None:
         dx = addend
     else:
         # parities no tap reaches are zero: one contiguous memset beats strided fills of the sub-grids
         # (1x1 stride-2: 3 of 4 parities; strided fills made that path 1.8x slower than MIOpen)
-        dx = (torch.zeros if empty else torch.empty)(N, H, W, C, device=gy.device, dtype=gy.dtype)
-    live = [(a, b, _parity_taps(R, a, padding, stride), _parity_taps(S, b, padding, stride))
-            for a in range(stride) for b in range(stride)]
-    live = [(a, b, tr, ts) for a, b, tr, ts in live if tr and ts]
+        alloc = torch.zeros if len(live) < stride * stride else torch.empty
+        dx = alloc(gy.shape[0], H, W, C, device=gy.device, dtype=gy.dtype)
     # every parity's [C, Tr, Ts, K] sub-weight gathered by one kernel (taps r*S + s, row-major over Tr x Ts)
     packed, offs = C_.conv_dgrad_wsub(w, [[r * S + s_ for _, r in tr for _, s_ in ts] for _, _, tr, ts in live])
     offs = offs.tolist()
@@ -323,32 +352,43 @@ def _dgrad_strided_hip(C_, gy, w, stride, padding, H, W, addend=None, bn_link=No
         n = C * len(tr) * len(ts) * K
         wsub = packed[offs[i]:offs[i] + n].view(C, len(tr), len(ts), K)
         Hs, Ws = (H - a + stride - 1) // stride, (W - b + stride - 1) // stride
-        if fix:
-            C_.conv_fwd_subgrid(gy, wsub, -tr[0][0], Hs, Ws, dx, stride, a, b, True, bn_link.x, bn_link.mask,
-                                bn_link.mean, bn_link.sums)
-        elif relu_sums:
-            C_.conv_fwd_subgrid(gy, wsub, -tr[0][0], Hs, Ws, dx, stride, a, b, False, bn_link.x, None, bn_link.mean,
-                                rsums, bn_link.gamma, bn_link.beta, bn_link.invstd)
-        else:
-            C_.conv_fwd_subgrid(gy, wsub, -tr[0][0], Hs, Ws, dx, stride, a, b, addend is not None)
-    if fix:
-        bn_link.complete(dx)
-    if relu_sums:
-        bn_link.deposit(rsums, None, dx)
+        C_.conv_fwd_subgrid(gy, wsub, -tr[0][0], Hs, Ws, dx, stride, a, b, *tail)
+    if route == "parity_complete_sums":
+        ln.complete(dx)
+    elif route == "parity_relu_sums":
+        ln.deposit(rsums, None, dx)
     return dx
 
 
-def _bwd1x1_fused_on() -> bool:
-    """K8S_AMD_BWD1X1_FUSED=0 keeps the weight gradient and the data gradient of a normalize-on-load 1x1 convolution
-    on their two kernels (A/B, tests); read per call."""
-    return os.environ.get("K8S_AMD_BWD1X1_FUSED", "1") != "0"
+def _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link):
+    """Which family forms a convolution backward's data gradient: "fused_1x1" (both gradients and the input
+    BatchNorm + ReLU's backward sums in one pass over gy and x, bwd1x1_fused.hip), "stride1" (``_plan_dgrad``),
+    "strided" (``_plan_dgrad_strided``) or "aten". Launches and allocates nothing. K8S_AMD_BWD1X1_FUSED=0 (read per
+    call: A/B, tests) keeps a normalize-on-load 1x1 convolution's two gradients on their two kernels."""
+    K, R, S, C = w.shape
+    if (xform is not None and addend is None and R == 1 and S == 1 and stride == 1 and padding == 0
+            and os.environ.get("K8S_AMD_BWD1X1_FUSED", "1") != "0" and _link_kind(bn_link, x.shape) == "relu"
+            and bn_link.x.data_ptr() == x.data_ptr() and gy.is_contiguous() and x.is_contiguous()
+            and C_.bwd1x1_fused_ok(gy.numel() // K, C, K)):
+        return "fused_1x1"
+    if _hip(gy, x, w) and stride == 1 and K % 8 == 0 and C % 8 == 0:
+        return "stride1"
+    if _hip(gy, x, w) and strided_dgrad_ok(gy, w, stride, padding):
+        return "strided"
+    return "aten"
 
 
-def _fused_link_ok(bn_link, x) -> bool:
-    """A relu-kind BnStatLink (the convolution's input BatchNorm + ReLU) filled for x."""
-    return (bn_link is not None and bn_link.relu and bn_link.x is not None and bn_link.x.shape == x.shape
-            and bn_link.x.data_ptr() == x.data_ptr()
-            and all(t is not None for t in (bn_link.gamma, bn_link.beta, bn_link.mean, bn_link.invstd)))
+def _slot_written(p):
+    """A kernel wrote (``p.written`` was False when it was launched) or accumulated into ``p``'s flat gradient slot."""
+    p.store._notify(p) if p.written else p.store.mark_written(p)
+
+
+def _finish_dw(p, gy, x, w, stride, padding):
+    """The weight gradient our kernels did not take (``p`` still set): ATen's, deposited."""
+    if p is not None:
+        _vendor("wgrad", x, w, stride, padding)
+        _, dw = _aten_bwd(gy, x, w, stride, padding, False, True)
+        p.store.deposit(p, dw)
 
 
 def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None, x_sub=None, bn_link=None):
@@ -362,7 +402,7 @@ def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None
     if x_sub is not None:
         _wgrad_hip(C_, gy, x_sub, p.grad.view(p.shape), 1, 0, p.written)
         STATS["hip_wgrad"] += 1
-        p.store._notify(p) if p.written else p.store.mark_written(p)
+        _slot_written(p)
         p = None  # done
     hip = _hip(gy, x, w)
     if xform is not None and not (hip and C % 64 == 0 and K % 8 == 0 and p is not None
@@ -371,48 +411,39 @@ def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None
     if addend is not None and not torch.is_tensor(addend) and not (
             hip and stride == 1 and K % 8 == 0 and C % 8 == 0):
         addend = addend.materialize()  # only the stride-1 dgrad on our kernels takes the (dy, mask) pair
-    # ---- both gradients and the BatchNorm-backward sums in one pass over gy and x (bwd1x1_fused.hip)
-    if (xform is not None and need_dx and addend is None and R == 1 and S == 1 and stride == 1 and padding == 0
-            and _bwd1x1_fused_on() and _fused_link_ok(bn_link, x) and gy.is_contiguous() and x.is_contiguous()
-            and C_.bwd1x1_fused_ok(gy.numel() // K, C, K)):
+    family = _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link) if need_dx else None
+    if family == "fused_1x1":
+        ROUTES[family] += 1
         STATS["hip_wgrad"] += 1
         STATS["hip_dgrad"] += 1
-        acc = p.written
         sums = _bn_sums(C_, bn_link, C, gy.device)
         dz = C_.bwd1x1_fused(gy.view(-1, K), x.view(-1, C), w.view(K, C), xform, bn_link.gamma, bn_link.beta,
-                             bn_link.mean, bn_link.invstd, p.grad.view(K, C), sums, acc).view(x.shape)
-        if acc:
-            p.store._notify(p)
-        else:
-            p.store.mark_written(p)
+                             bn_link.mean, bn_link.invstd, p.grad.view(K, C), sums, p.written).view(x.shape)
+        _slot_written(p)
         bn_link.deposit(sums, None, dz)
         return dz
     # ---- weight gradient
-    dw_done = False
     if hip and C % 8 == 0 and K % 8 == 0 and p is not None and p.grad.dtype == torch.float32:
         STATS["hip_wgrad"] += 1
-        acc = p.written
-        _wgrad_hip(C_, gy, x, p.grad.view(p.shape), stride, padding, acc, xform)
-        if acc:
-            p.store._notify(p)
-        else:
-            p.store.mark_written(p)
-        dw_done = True
+        _wgrad_hip(C_, gy, x, p.grad.view(p.shape), stride, padding, p.written, xform)
+        _slot_written(p)
+        p = None  # done
     # ---- data gradient
     dx = None
-    if need_dx:
-        if hip and stride == 1 and K % 8 == 0 and C % 8 == 0:
-            STATS["hip_dgrad"] += 1
+    if family in ("stride1", "strided"):
+        STATS["hip_dgrad"] += 1
+        if family == "stride1":
             dx = _dgrad_hip(C_, gy, w, padding, addend, bn_link)
-        elif hip and strided_dgrad_ok(gy, w, stride, padding):
-            STATS["hip_dgrad"] += 1
-            dx = _dgrad_strided_hip(C_, gy, w, stride, padding, x.shape[1], x.shape[2], addend, bn_link)
         else:
-            _vendor("dgrad", x, w, stride, padding)
-            dx, _ = _aten_bwd(gy, x, w, stride, padding, True, False)
-            if addend is not None:
-                dx = dx + addend
-    return _finish_dw(dx, dw_done, p, gy, x, w, stride, padding)
+            dx = _dgrad_strided_hip(C_, gy, w, stride, padding, x.shape[1], x.shape[2], addend, bn_link)
+    elif family == "aten":
+        ROUTES[family] += 1
+        _vendor("dgrad", x, w, stride, padding)
+        dx, _ = _aten_bwd(gy, x, w, stride, padding, True, False)
+        if addend is not None:
+            dx = dx + addend
+    _finish_dw(p, gy, x, w, stride, padding)
+    return dx
 
 
 # 1x1 / stride-2 / pad-0 convolutions (ResNet's downsample branch) as stride-1 GEMMs on the subsampled input: one
@@ -426,11 +457,3 @@ def subsample_ok(x, w, stride, padding) -> bool:
     K, R, S, C = w.shape
     return (SUB1X1 and stride > 1 and R == 1 and S == 1 and padding == 0 and _hip(x, w) and C % 64 == 0
             and K % 8 == 0 and x.is_contiguous())
-
-
-def _finish_dw(dx, dw_done, p, gy, x, w, stride, padding):
-    if not dw_done and p is not None:
-        _vendor("wgrad", x, w, stride, padding)
-        _, dw = _aten_bwd(gy, x, w, stride, padding, False, True)
-        p.store.deposit(p, dw)
-    return dx

@@ -108,38 +108,57 @@ class MaskedGrad:
 
 
 class BnStatLink:
-    """Joins a residual BatchNorm (``y = relu(BN(x) + r)``, packed ReLU mask; or the two-BatchNorm form of a ResNet
-    downsample block) to the 1x1 convolution that reads y with a masked residual addend (a ResNet identity block's
-    conv1): that convolution's data gradient -- the whole gradient of y -- also accumulates the BatchNorm-backward
-    sums (sum g, sum g (x - mean) for g = mask ? dy : 0) in its epilogue (gemm_short.hip EPI 3 / 4), so the
-    BatchNorm's backward skips its reduction sweep over dy and x. The same for a non-residual BatchNorm + ReLU
-    (``relu``: ResNet's bn1) read by a stride-1 3x3 convolution on the staged-window kernel (conv3x3.hip epilogue,
-    g = relu_on(x) ? dy : 0 from the BatchNorm's affine). The BatchNorm's forward fills (x, mask, mean[, x2,
-    mean2]) and tags y with the link (``y._k8s_bnstat``); the convolution's backward deposits the sums and the
-    identity of the dy they were taken over (``deposit``); the BatchNorm's backward uses them only when it receives
-    exactly that dy (``take``: so a second consumer of y, whose gradient autograd would add, falls back to the
-    reduction)."""
-    __slots__ = ("x", "mask", "mean", "x2", "mean2", "invstd", "gamma", "beta", "relu", "sums", "sums2", "dy_key",
-                 "store", "pending", "last_full")
+    """Joins a BatchNorm to the convolution(s) that read its output y: a data gradient into y -- the whole gradient of
+    y -- also accumulates the BatchNorm-backward sums (sum g, sum g (x - mean), g = dy where the ReLU passed) in its
+    epilogue, so the BatchNorm's backward skips its reduction sweep over dy and x. The BatchNorm's forward fills the
+    link (one ``fill_*`` per kind) and tags y with it (``y._k8s_bnstat``); the convolution's backward deposits the
+    sums and the identity of the dy they were taken over (``deposit``); the BatchNorm's backward uses them only when it
+    receives exactly that dy, unchanged (``take``: a second consumer of y, whose gradient autograd adds -- in place or
+    not -- makes it fall back to the reduction).
 
-    def __init__(self, store=None):
-        self.store = store  # the BatchNorm's ParamStore: its per-step zeroed scratch holds the sums
-        self.x = self.mask = self.mean = self.x2 = self.mean2 = None
-        self.invstd = self.gamma = self.beta = None
-        self.relu = False  # a non-residual BatchNorm + ReLU (mask None: g = relu_on(x) ? dy : 0, from the affine)
+    Kinds, and the data-gradient routes of ``ops.conv`` that can serve each:
+      relu  a non-residual BatchNorm + ReLU (ResNet's bn1 / bn2), the ReLU decision recomputed from the affine:
+            conv3x3_relu_sums, tile_relu_sums, parity_relu_sums, fused_1x1
+      mask  a residual BatchNorm, ``y = relu(BN(x) + r)``, with the packed ReLU mask: short_mask_sums, tile_mask_sums
+            (a masked residual addend: an identity block's conv1); short_entry_pending then parity_complete_sums (a
+            stage-entry block's conv1, then its downsample)
+      dual  the two-BatchNorm form of a downsample block's output (x2, mean2; two sets of sums): short_mask_sums,
+            tile_mask_sums
+      pool  the stem's BatchNorm + ReLU + max pool, per pooled element the window winner's x and ReLU bit: the first
+            of its two stride-1 data gradients takes no sums, the second, accumulating onto the first, takes them over
+            the final tensor (tile_final_sums); with a masked addend the mask routes"""
+    __slots__ = ("kind", "x", "mask", "mean", "x2", "mean2", "invstd", "gamma", "beta", "sums", "sums2", "dy_key",
+                 "store", "pending")
+
+    def __init__(self):
         self.sums = self.sums2 = self.dy_key = None
-        # sums over the first of two data gradients into y (a stage-entry block's conv1: deposit_pending), awaiting
-        # the second's correction (its downsample convolution, ops.conv._dgrad_strided_hip: complete); dy_key is set
-        # only once complete
+        # sums over the first of two data gradients into y (deposit_pending), awaiting the second's correction
+        # (complete); dy_key is set only once complete
         self.pending = False
-        # two stride-1 data gradients into y (the stem pool's output, read by layer 1's conv1 and downsample): the
-        # first takes no sums, the second -- accumulating onto the first -- takes them over the final tensor
-        self.last_full = False
+        self._fill(None, None, None, None)
+
+    def _fill(self, kind, store, x, mean, mask=None, x2=None, mean2=None, invstd=None, gamma=None, beta=None):
+        self.kind, self.store = kind, store  # store: the BatchNorm's ParamStore (its zeroed scratch holds the sums)
+        self.x, self.mean, self.mask, self.x2, self.mean2 = x, mean, mask, x2, mean2
+        self.invstd, self.gamma, self.beta = invstd, gamma, beta
+
+    def fill_relu(self, x, mean, invstd, gamma, beta, store=None):
+        self._fill("relu", store, x, mean, invstd=invstd, gamma=gamma, beta=beta)
+
+    def fill_mask(self, x, mask, mean, store=None):
+        self._fill("mask", store, x, mean, mask)
+
+    def fill_dual(self, x, mask, mean, x2, mean2, store=None):
+        self._fill("dual", store, x, mean, mask, x2, mean2)
+
+    def fill_pool(self, x, mask, mean, store=None):
+        self._fill("pool", store, x, mean, mask)
 
     @staticmethod
     def _key(t):
-        """The identity of the tensor a deposit's sums were taken over."""
-        return t.data_ptr(), tuple(t.shape)
+        """The identity of the tensor a deposit's sums were taken over: an in-place add keeps the pointer and the
+        shape, so the version counter is part of it."""
+        return t.data_ptr(), tuple(t.shape), t._version
 
     def deposit(self, sums, sums2, over):
         """The convolution's backward hands over the sums (``sums2``: the second BatchNorm's, or None) taken over the
@@ -156,15 +175,21 @@ class BnStatLink:
         """The second data gradient corrected the pending sums: they now hold for the final tensor ``over``."""
         self.dy_key, self.pending = self._key(over), False
 
+    def drop_pending(self):
+        """No data gradient can complete the pending sums: the BatchNorm takes its own reduction."""
+        self.sums, self.pending = None, False
+
+    def covers(self, t) -> bool:
+        """Whether a completed deposit's sums were taken over ``t`` as it is now."""
+        return self.sums is not None and self.dy_key == self._key(t)
+
     def take(self, dy):
-        """(sums, sums2) if they were taken over ``dy``, else None; clears the deposit either way."""
-        sums, sums2, key = self.sums, self.sums2, self.dy_key
+        """(sums, sums2) if they were taken over ``dy``, else None; clears the link either way (the BatchNorm's
+        backward is the last reader)."""
+        pre = (self.sums, self.sums2) if self.covers(dy) else None
         self.sums = self.sums2 = self.dy_key = None
-        self.x = self.mask = self.mean = self.x2 = self.mean2 = None  # the BatchNorm's backward is the last reader
-        self.invstd = self.gamma = self.beta = None
-        if sums is None or key != self._key(dy):
-            return None
-        return sums, sums2
+        self._fill(None, self.store, None, None)
+        return pre
 
 
 # BatchNorm-backward sums in the masked-addend 1x1 dgrad epilogue (BnStatLink); K8S_AMD_BN_BSTATS=0 for the A/B
@@ -294,15 +319,9 @@ class _StemS2D(torch.autograd.Function):
         else:
             _conv_impl()._wgrad_hip(C_, gy.contiguous(), xs, dw4, 1, 0, False)
         _conv_impl().STATS["hip_wgrad"] += 1
-        store = p.store
-        slot = store.slot_for_write(p)
-        if slot is not None:
-            C_.stem_dw_s2d(dw4, slot.view(p.shape))
-            store.mark_written(p)
-        else:
-            tmp = torch.empty(p.shape, device=xs.device, dtype=torch.float32)
-            C_.stem_dw_s2d(dw4, tmp)
-            store.deposit(p, tmp)
+        dw7, finish = _param_grad(p, xs.device)
+        C_.stem_dw_s2d(dw4, dw7)
+        finish()
         return None, None, None
 
 
@@ -351,9 +370,10 @@ class _BnAct(torch.autograd.Function):
         ctx.dy_link = dy_link if (dy_link is not None and not relu and res is None) else None
         ctx.stat_link = None
         if stat_link is not None and training and (mask is not None or ctx.relu_x):
-            stat_link.x, stat_link.mask, stat_link.mean, stat_link.store = x, mask, mean, pg.store
             if mask is None:
-                stat_link.relu, stat_link.invstd, stat_link.gamma, stat_link.beta = True, invstd, pg.master, pb.master
+                stat_link.fill_relu(x, mean, invstd, pg.master, pb.master, pg.store)
+            else:
+                stat_link.fill_mask(x, mask, mean, pg.store)
             ctx.stat_link = stat_link
         return y
 
@@ -367,9 +387,7 @@ class _BnAct(torch.autograd.Function):
             mask, ctx.dy_link.mask = ctx.dy_link.mask, None
         mask_out = isinstance(ctx.res_link, MaskLink) and mask is not None and ctx.has_res
         if _gpu(x):
-            sg, sb = store.slot_for_write(pg), store.slot_for_write(pb)
-            dg = sg if sg is not None else torch.empty(pg.shape, device=x.device, dtype=torch.float32)
-            db = sb if sb is not None else torch.empty(pb.shape, device=x.device, dtype=torch.float32)
+            dg, db, finish = _bn_param_grads(pg, pb, x.device)
             # residual gradient for a linked consumer: (dy, mask) instead of a written dres tensor
             handoff = isinstance(ctx.res_link, GradLink) and ctx.has_res and mask is not None
             want_dres = ctx.has_res and not (handoff or mask_out)
@@ -387,14 +405,7 @@ class _BnAct(torch.autograd.Function):
             elif mask_out:  # the producing plain BN masks dy itself (MaskLink)
                 dres = dy
                 ctx.res_link.mask = mask
-            if sg is not None:
-                store.mark_written(pg)
-            else:
-                store.deposit(pg, dg)
-            if sb is not None:
-                store.mark_written(pb)
-            else:
-                store.deposit(pb, db)
+            finish()
         else:
             dx, dres, dg, db = ref.bn_bwd(dy, x, y, mean, invstd, pg.master)
             store.deposit(pg, dg)
@@ -418,16 +429,17 @@ if BN_ONLOAD not in ("0", "1x1", "3x3"):  # an unknown value mus
     raise ValueError("K8S_AMD_BN_ONLOAD must be 0 (BN applied by its own pass), 1x1 or 3x3, not %r" % BN_ONLOAD)
 
 
-def _bn_param_grads(store, pg, pb, device):
-    sg, sb = store.slot_for_write(pg), store.slot_for_write(pb)
-    dg = sg if sg is not None else torch.empty(pg.shape, device=device, dtype=torch.float32)
-    db = sb if sb is not None else torch.empty(pb.shape, device=device, dtype=torch.float32)
+def _param_grad(p, device):
+    """(g, finish): the fp32 tensor of ``p``'s shape a kernel writes p's gradient into -- p's flat slot itself on its
+    first use this step, else a temporary -- and the call that marks the slot written or accumulates the temporary."""
+    slot = p.store.slot_for_write(p)
+    g = slot.view(p.shape) if slot is not None else torch.empty(p.shape, device=device, dtype=torch.float32)
+    return g, lambda: p.store.mark_written(p) if slot is not None else p.store.deposit(p, g)
 
-    def finish():
-        store.mark_written(pg) if sg is not None else store.deposit(pg, dg)
-        store.mark_written(pb) if sb is not None else store.deposit(pb, db)
 
-    return dg, db, finish
+def _bn_param_grads(pg, pb, device):
+    (dg, finish_g), (db, finish_b) = _param_grad(pg, device), _param_grad(pb, device)
+    return dg, db, lambda: (finish_g(), finish_b())
 
 
 class _BnReluConv(torch.autograd.Function):
@@ -465,11 +477,10 @@ class _BnReluConv(torch.autograd.Function):
         # the BatchNorm-backward sums in the data gradient's epilogue where a kernel takes them (BnStatLink)
         link = None
         if BN_BSTATS:
-            link = BnStatLink(pg.store)
-            link.x, link.mean, link.invstd, link.gamma, link.beta, link.relu = (x, mean, invstd, pg.master, pb.master,
-                                                                                True)
+            link = BnStatLink()
+            link.fill_relu(x, mean, invstd, pg.master, pb.master, pg.store)
         dz = impl.conv_bwd(gy, x, pw.weight, ctx.stride, ctx.padding, True, pw, xform=params, bn_link=link)
-        dg, db, finish = _bn_param_grads(pg.store, pg, pb, x.device)
+        dg, db, finish = _bn_param_grads(pg, pb, x.device)
         pre = link.take(dz) if link is not None else None
         if pre is not None:
             dx = _C().bn_bwd_relu_from_sums(dz, x, pre[0], mean, invstd, pg.master, pb.master, dg, db)[0]
@@ -544,7 +555,7 @@ def batch_norm_act(x, pg, pb, run_mean, run_var, residual=None, relu=True, train
     sub = SubLink() if (sub2 and SUB2_FUSED and sums is not None and _gpu(x)) else None
     y = _BnAct.apply(x, residual, pg.store.anchor, pg, pb, run_mean, run_var, training, momentum, eps, relu,
                      sums, res_link, dy_link, link, sub)
-    if link is not None and link.x is not None:
+    if link is not None and link.kind is not None:
         y._k8s_bnstat = link
     if sub is not None and sub.y is not None:
         y._k8s_sub2 = sub.y
@@ -1025,9 +1036,8 @@ class _BnReluMaxPool(torch.autograd.Function):
         ctx.pg, ctx.pb = pg, pb
         ctx.link = None
         if want:
-            link = BnStatLink(pg.store)
-            link.x, link.mask, link.mean, link.last_full = outs[4], outs[5], mean, True
-            y._k8s_bnstat = ctx.link = link
+            y._k8s_bnstat = ctx.link = BnStatLink()
+            ctx.link.fill_pool(outs[4], outs[5], mean, pg.store)
         ctx.mark_non_differentiable(idx)
         return y
 
@@ -1035,7 +1045,7 @@ class _BnReluMaxPool(torch.autograd.Function):
     def backward(ctx, dy):
         x, idx, mean, invstd = ctx.saved_tensors
         pg, pb = ctx.pg, ctx.pb
-        dg, db, finish = _bn_param_grads(pg.store, pg, pb, x.device)
+        dg, db, finish = _bn_param_grads(pg, pb, x.device)
         dy = dy.contiguous()
         pre = ctx.link.take(dy) if ctx.link is not None else None
         if pre is not None:
@@ -1082,8 +1092,7 @@ class _BnActDual(torch.autograd.Function):
         ctx.p = (pg, pb, pgr, pbr)
         ctx.stat_link = stat_link
         if stat_link is not None:
-            stat_link.x, stat_link.mask, stat_link.mean, stat_link.x2, stat_link.mean2 = x, mask, mean, xr, mean_r
-            stat_link.store = pg.store
+            stat_link.fill_dual(x, mask, mean, xr, mean_r, pg.store)
         return y
 
     @staticmethod
@@ -1092,8 +1101,8 @@ class _BnActDual(torch.autograd.Function):
         pg, pb, pgr, pbr = ctx.p
         dy = dy.contiguous()
         C_ = _C()
-        dg, db, finish = _bn_param_grads(pg.store, pg, pb, x.device)
-        dgr, dbr, finish_r = _bn_param_grads(pgr.store, pgr, pbr, x.device)
+        dg, db, finish = _bn_param_grads(pg, pb, x.device)
+        dgr, dbr, finish_r = _bn_param_grads(pgr, pbr, x.device)
         pre = ctx.stat_link.take(dy) if ctx.stat_link is not None else None
         if pre is not None and pre[1] is not None:  # both reductions came with dy (BnStatLink)
             dx, dxr = C_.bn_bwd_dual_from_sums(dy, mask, x, mean, invstd, pg.master, pb.master, dg, db, pre[0], xr,

@@ -698,16 +698,16 @@ def test_stage_entry_bn_sums_two_dgrads(cuda, N, H, K1, C, K2):
     mask = torch.randint(0, 256, (M * C // 8,), device=cuda, dtype=torch.uint8)
     mean = torch.randn(C, device=cuda) * 0.2
     link = K.BnStatLink()
-    link.x, link.mask, link.mean = x, mask, mean
+    link.fill_mask(x, mask, mean)
     sums = torch.zeros(C_.conv_stat_replicas, 2, C, device=cuda)
     out = C_.dgrad_short_bnstats(gy, w1, None, None, x.view(-1, C), mask, mean, sums).view(N, H, H, C)
     plain = C_.gemm(gy, True, w1, False, None, False, None, 0, None, False, 1.0, 1)
     assert torch.equal(out.view(-1, C), plain)
-    link.sums, link.pending = sums, True
+    link.deposit_pending(sums)
     dy2 = torch.randn(N, H // 2, H // 2, K2, device=cuda).bfloat16()
     w2 = (torch.randn(K2, 1, 1, C, device=cuda) * 0.05).bfloat16()
     dx = kc._dgrad_strided_hip(C_, dy2, w2, 2, 0, H, H, out, link)
-    assert dx.data_ptr() == out.data_ptr() and not link.pending and link.dy_key == (dx.data_ptr(), tuple(dx.shape))
+    assert dx.data_ptr() == out.data_ptr() and not link.pending and link.covers(dx)
     ref_dx = plain.float().view(N, H, H, C).clone()
     ref_dx[:, ::2, ::2, :] += (dy2.float().reshape(-1, K2) @ w2.float().reshape(K2, C)).view(N, H // 2, H // 2, C)
     assert _rel(dx, ref_dx) < 1e-2
@@ -720,7 +720,7 @@ def test_stage_entry_bn_sums_two_dgrads(cuda, N, H, K1, C, K2):
 def test_gemm_dgrad_bnstats_mask_accumulate(cuda):
     """The second of two stride-1 data gradients into the stem pool's output (layer 1's downsample after its conv1):
     the tile kernel accumulates onto the first's gradient and takes the BatchNorm-backward sums (mask kind) over the
-    final tensor in its epilogue (gemm.hip BST fast path; ops.conv._dgrad_hip, BnStatLink.last_full) -- against fp32
+    final tensor in its epilogue (gemm.hip BST fast path; ops.conv._dgrad_hip, BnStatLink pool kind) -- against fp32
     sums. Ragged M (not a multiple of the 128-row tile)."""
     from k8s_amd.ops import conv as kc
     from k8s_amd.ops import nn as K
@@ -737,12 +737,12 @@ def test_gemm_dgrad_bnstats_mask_accumulate(cuda):
     gy2 = torch.randn(N, H, H, K2, device=cuda).bfloat16()
     w2 = (torch.randn(K2, 1, 1, C, device=cuda) * 0.05).bfloat16()
     link = K.BnStatLink()
-    link.x, link.mask, link.mean, link.last_full = x, mask, mean, True
+    link.fill_pool(x, mask, mean)
     dx1 = kc._dgrad_hip(C_, gy1, w1, 0, None, link)
     assert link.sums is None and not link.pending
     dx = kc._dgrad_hip(C_, gy2, w2, 0, dx1, link)
     assert dx.data_ptr() == dx1.data_ptr()
-    assert link.dy_key == (dx.data_ptr(), tuple(dx.shape)) and link.sums is not None
+    assert link.covers(dx) and link.sums is not None
     ref = gy1.float().reshape(-1, K1) @ w1.float().reshape(K1, C) + gy2.float().reshape(-1, K2) @ w2.float().reshape(K2, C)
     assert _rel(dx.view(-1, C), ref) < 1e-2
     g = torch.where(_unpack_bits(mask, (M, C)), dx.float().view(-1, C), torch.zeros(M, C, device=cuda))
@@ -801,10 +801,10 @@ def test_strided_dgrad_bn_relu_sums(cuda, monkeypatch, N, H, C, K):
     invstd = torch.rsqrt(x.float().reshape(-1, C).var(0, unbiased=False) + 1e-5)
     gamma, beta = torch.rand(C, device=cuda) + 0.5, torch.randn(C, device=cuda) * 0.2
     link = K_.BnStatLink()
-    link.x, link.mean, link.invstd, link.gamma, link.beta, link.relu = x, mean, invstd, gamma, beta, True
+    link.fill_relu(x, mean, invstd, gamma, beta)
     monkeypatch.setattr(kc, "BSTATS_STRIDED", True)  # (off by default: neutral at the step level)
     dx = kc._dgrad_strided_hip(C_, gy, w, 2, 1, H, H, None, link)
-    assert link.sums is not None and link.dy_key == (dx.data_ptr(), tuple(dx.shape))
+    assert link.sums is not None and link.covers(dx)
     plain = kc._dgrad_strided_hip(C_, gy, w, 2, 1, H, H, None, None)
     assert torch.equal(dx, plain)
     ref = torch.nn.grad.conv2d_input((N, C, H, H), w.float().permute(0, 3, 1, 2), gy.float().permute(0, 3, 1, 2),

@@ -277,25 +277,29 @@ def test_bn_backward_sums_in_dgrad_epilogue_match_reduction(cuda):
             x = m.prepare_input(images.bfloat16())
             x8 = m.prepare_input(images.bfloat16(), s2d=False)
             y = torch.arange(4, device=cuda) % 10
-            n0 = kc.STATS["bn_bstats"]
+            n0, r0 = kc.STATS["bn_bstats"], kc.ROUTES.copy()
             store.begin_step()
             loss = K.cross_entropy(m(x), y)
             loss.backward()
             store.zero_unwritten()
-            n = kc.STATS["bn_bstats"] - n0
+            n, routes = kc.STATS["bn_bstats"] - n0, dict(kc.ROUTES - r0)
             _, ref = reference_grads(m, store, x8, y)
             err = {}
             for p in store.params:
                 r = ref[p.name].float()
                 err[p.name] = (p.grad.float() - r).norm().item() / (r.norm().item() + 1e-6)
-            return loss.item(), err, n
+            return loss.item(), err, n, routes
         finally:
             K.BN_BSTATS = old
 
-    l1, e1, n1 = run(True)
-    l0, e0, n0 = run(False)
+    l1, e1, n1, routes = run(True)
+    l0, e0, n0, _ = run(False)
     # s1b0 (dual), s1b1, s2b1, the stage-1/2 bn2 sums in conv3's dgrad, the s1b2 / s2b2 outputs' two-dgrad sums
     assert n0 == 0 and n1 >= 8, (n0, n1)
+    # the route every data gradient of the step takes (ops.conv.ROUTES), recorded at the commit before the dispatch was
+    # split into planners by tallying its branches: a changed count is a layer moved to another kernel
+    assert routes == {"fused_1x1": 6, "gemm_plain": 2, "implicit_flipped": 5, "parity": 4, "parity_complete_sums": 2,
+                      "short_entry_pending": 2, "short_mask_sums": 4, "tile_final_sums": 1, "tile_relu_sums": 2}, routes
     assert l1 == l0, (l1, l0)  # the forward is untouched (and deterministic at this size)
     bad = [(k, round(e1[k], 4), round(e0[k], 4)) for k in e0 if e1[k] > 1.5 * e0[k] + 0.02]
     assert not bad, bad
@@ -352,6 +356,47 @@ def test_bn_backward_sums_bottleneck_3x3_and_residual(cuda, H, cin, width):
         if err > 1e-2:
             bad.append((name, round(err, 4)))
     assert not bad, bad
+
+
+def test_bn_backward_sums_with_second_consumer(cuda):
+    """A BatchNorm + ReLU output read by a 3x3 convolution (whose data gradient can take the BatchNorm-backward sums)
+    and by a second consumer: autograd adds the two gradients of y -- in place onto the convolution's dx, or into
+    another tensor -- so sums taken over the convolution's part alone must not be used (ops.nn.BnStatLink.take).
+    ops.nn.BN_BSTATS on against off: x's gradient and the BatchNorm's parameter gradients agree, whichever path ran."""
+    from k8s_amd.models.resnet import BN, Conv
+
+    def run(on):
+        old = K.BN_BSTATS
+        K.BN_BSTATS = on
+        try:
+            torch.manual_seed(0)
+            store = ParamStore()
+            bn, conv = BN(store, "bn", 256), Conv(store, "conv", 256, 256, 3)
+            store.finalize(cuda, seed=5)
+            with torch.no_grad():
+                gen = torch.Generator(device="cpu").manual_seed(11)
+                bn.gamma.master.copy_((torch.rand(256, generator=gen) * 0.8 + 0.6).to(cuda))
+                bn.beta.master.copy_((torch.randn(256, generator=gen) * 0.1).to(cuda))
+            store.refresh_lowp()
+            bn.to(cuda)
+            g = torch.Generator(device="cpu").manual_seed(2)
+            x = torch.randn(2, 14, 14, 256, generator=g).to(cuda).bfloat16().requires_grad_(True)
+            ga = torch.randn(2, 14, 14, 256, generator=g).to(cuda)
+            gb = torch.randn(2, 14, 14, 256, generator=g).to(cuda)
+            store.begin_step()
+            y = bn(x, relu=True)
+            a, _ = conv(y)
+            ((a.float() * ga).sum() + (y.float() * gb).sum()).backward()
+            store.zero_unwritten()
+            return {"x": x.grad.float().clone(), "gamma": bn.gamma.grad.float().clone(),
+                    "beta": bn.beta.grad.float().clone()}
+        finally:
+            K.BN_BSTATS = old
+
+    g1, g0 = run(True), run(False)
+    for name, r in g0.items():
+        err = (g1[name] - r).norm().item() / (r.norm().item() + 1e-6)
+        assert err < 1e-2, (name, err)
 
 
 def test_fused_subsample_matches_separate_pass(cuda):
