@@ -46,6 +46,7 @@ std::vector<Tensor> norm_fwd(Tensor x, OptTensor res, Tensor gamma, OptTensor be
   Tensor xsum = res ? torch::empty_like(x) : Tensor();
   auto mean = torch::empty({rms ? 1 : R}, gamma.options());
   auto rstd = torch::empty({R}, gamma.options());
+  if (R == 0) return {y, mean, rstd, xsum};  // no rows: nothing to launch
   launch_norm_fwd(rms, cbf(x), res ? cbf(*res) : nullptr, res ? bf(xsum) : nullptr, f32(gamma), optf(beta), bf(y),
                   f32(mean), f32(rstd), R, D, (float)eps, cur_stream(), drop_state ? &dr : nullptr);
   return {y, mean, rstd, xsum};
@@ -62,6 +63,7 @@ std::vector<Tensor> norm_bwd_impl(Tensor dy, Tensor x, Tensor gamma, Tensor mean
   check_bf16_dense(dy, -1, "dy");
   TORCH_CHECK(dy.sizes() == x.sizes() && x.dim() >= 1 && x.size(-1) > 0, "dy / x: the same rows of D");
   const int D = (int)x.size(-1);
+  TORCH_CHECK(D % 8 == 0 && D <= 8192, "norm row length must be a multiple of 8 and <= 8192");
   const long R = x.numel() / D;
   check_channel_f32(gamma, D, "gamma");
   check_channel_f32(dgamma, D, "dgamma");
@@ -80,6 +82,12 @@ std::vector<Tensor> norm_bwd_impl(Tensor dy, Tensor x, Tensor gamma, Tensor mean
   }
   auto dx = torch::empty_like(x);
   Tensor da = drop ? torch::empty_like(x) : Tensor();
+  if (R == 0) {  // no rows: the sums over them are zero, nothing to launch
+    dgamma.zero_();
+    if (dbeta) dbeta->zero_();
+    if (dsum) dsum->zero_();
+    return {dx, da};
+  }
   auto work = torch::empty({k8s_amd::norm_workspace_floats(R, D)}, gamma.options());
   launch_norm_bwd(rms, cbf(dy), cbf(x), f32(gamma), f32(mean), f32(rstd), dres ? cbf(*dres) : nullptr, bf(dx),
                   f32(dgamma), dbeta ? f32(*dbeta) : nullptr, f32(work), R, D, cur_stream(),
@@ -114,6 +122,7 @@ std::vector<Tensor> xent_fwd(Tensor logits, Tensor labels, int64_t ignore_index,
   auto opt = logits.options().dtype(at::kFloat);
   auto loss = torch::empty({R}, opt);
   auto lse = torch::empty({R}, opt);
+  if (R == 0) return {loss, lse};
   launch_xent_fwd(logits.data_ptr(), is_bf16, labels.data_ptr<int64_t>(), R, V, logits.stride(0), f32(loss), f32(lse),
                   ignore_index, (float)smoothing, cur_stream());
   return {loss, lse};
@@ -143,6 +152,7 @@ Tensor xent_bwd(Tensor logits, Tensor labels, Tensor lse, Tensor dscale, int64_t
   TORCH_CHECK(dscale.is_cuda() && (dscale.numel() == 1 || dscale.numel() == R), "dscale: a GPU scalar or one per row");
   auto d = dscale.to(at::kFloat).contiguous();
   auto dl = torch::empty({R, Vpad}, logits.options());  // the kernel zeroes the pad columns itself
+  if (R == 0) return dl;
   launch_xent_bwd(logits.data_ptr(), is_bf16, labels.data_ptr<int64_t>(), f32(lse), f32(d), d.numel() == R, R, V, Vpad,
                   dl.data_ptr(), ignore_index, (float)smoothing, cur_stream());
   return dl;

@@ -5,6 +5,8 @@
 // per-row loss and log-sum-exp. The backward recomputes softmax from the saved
 // LSE and writes dlogits = (softmax - onehot) * dloss[row] in one pass, so the
 // [rows, vocab] probability matrix is never materialised.
+// -inf logits are masked classes: while a thread's running maximum is still -inf the exponentials are taken against
+// 0 (one select per trip), so nothing is ever exp(-inf - -inf).
 #include "common.h"
 #include "launchers.h"
 
@@ -43,10 +45,11 @@ __global__ void __launch_bounds__(256) xent_fwd_kernel(const T* __restrict__ log
 #pragma unroll
     for (int j = 1; j < 8; ++j) lm = fmaxf(lm, v[j]);
     const float nm = fmaxf(m, lm);
-    float acc = s * __expf(m - nm);
+    const float sm = nm == -INFINITY ? 0.f : nm;  // all -inf so far: exp(-inf - -inf) would be NaN
+    float acc = s * __expf(m - sm);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      acc += __expf(v[j] - nm);
+      acc += __expf(v[j] - sm);
       sumx += v[j];
     }
     s = acc;
@@ -55,7 +58,8 @@ __global__ void __launch_bounds__(256) xent_fwd_kernel(const T* __restrict__ log
   for (long i = V8 + threadIdx.x; i < V; i += 256) {
     const float v = load1<T>(x + i);
     const float nm = fmaxf(m, v);
-    s = s * __expf(m - nm) + __expf(v - nm);
+    const float sm = nm == -INFINITY ? 0.f : nm;
+    s = s * __expf(m - sm) + __expf(v - sm);
     m = nm;
     sumx += v;
   }
@@ -109,10 +113,11 @@ __global__ void __launch_bounds__(256) xent_eval_kernel(const T* __restrict__ lo
 #pragma unroll
     for (int j = 1; j < 8; ++j) lm = fmaxf(lm, v[j]);
     const float nm = fmaxf(m, lm);
-    float acc = s * __expf(m - nm);
+    const float sm = nm == -INFINITY ? 0.f : nm;  // all -inf so far: exp(-inf - -inf) would be NaN
+    float acc = s * __expf(m - sm);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      acc += __expf(v[j] - nm);
+      acc += __expf(v[j] - sm);
       cnt += (v[j] > xl || (v[j] == xl && i + j < lab)) ? 1.f : 0.f;
     }
     s = acc;
@@ -121,7 +126,8 @@ __global__ void __launch_bounds__(256) xent_eval_kernel(const T* __restrict__ lo
   for (long i = V8 + threadIdx.x; i < V; i += 256) {
     const float v = load1<T>(x + i);
     const float nm = fmaxf(m, v);
-    s = s * __expf(m - nm) + __expf(v - nm);
+    const float sm = nm == -INFINITY ? 0.f : nm;
+    s = s * __expf(m - sm) + __expf(v - sm);
     m = nm;
     cnt += (v > xl || (v == xl && i < lab)) ? 1.f : 0.f;
   }
