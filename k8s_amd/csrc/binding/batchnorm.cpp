@@ -236,6 +236,38 @@ std::vector<Tensor> bn_bwd_from_sums(Tensor dy, Tensor x, Tensor mask, Tensor su
   return bn_bwd_impl(dy, x, {}, mean, invstd, gamma, beta, false, dgamma, dbeta, want_dres, mask, &sums);
 }
 
+// The two halves of bn_bwd / bn_bwd_from_sums for a residual BatchNorm (packed mask), for a consumer of dx that applies
+// the backward as it loads (bwd1x1_fused with x3 / mask / params). bn_bwd_params: dgamma, dbeta and the params table
+// fp32 [sc | B | D | shift] -- from the producer's sums, or from its own reduce sweep without them. bn_bwd_apply: dx
+// from that table, the bits bn_bwd / bn_bwd_from_sums write.
+Tensor bn_bwd_params(Tensor dy, Tensor x, Tensor mask, OptTensor sums, Tensor mean, Tensor invstd, Tensor gamma,
+                     Tensor beta, Tensor dgamma, Tensor dbeta) {
+  const int C = bn_channels(x, "x", true);
+  const long M = x.numel() / C;
+  check_same_shape(dy, x, "dy");
+  check_bwd_vectors(mean, invstd, gamma, beta, dgamma, dbeta, C);
+  const uint8_t* mk = check_bit_mask(mask, x.numel(), "mask");
+  const bool pre = sums && sums->defined();
+  const int nrep = pre ? check_stat_sums(*sums, C, "sums", false) : 0;
+  auto params = torch::empty({4 * C}, gamma.options());
+  Tensor work;
+  if (!pre) work = torch::empty({k8s_amd::bn_workspace_floats(M, C)}, gamma.options());
+  launch_bn_bwd_params(cbf(dy), cbf(x), mk, pre ? f32(*sums) : nullptr, nrep, f32(mean), f32(invstd), f32(gamma),
+                       f32(beta), false, f32(dgamma), f32(dbeta), pre ? nullptr : f32(work), f32(params), M, C,
+                       cur_stream());
+  return params;
+}
+Tensor bn_bwd_apply(Tensor dy, Tensor x, Tensor mask, Tensor params) {
+  const int C = bn_channels(x, "x", true);
+  check_same_shape(dy, x, "dy");
+  const uint8_t* mk = check_bit_mask(mask, x.numel(), "mask");
+  check_channel_f32(params, 4L * C, "params");
+  TORCH_CHECK(params.device() == x.device(), "params: on x's device");
+  auto dx = torch::empty_like(x);
+  launch_bn_bwd_apply_pass(cbf(dy), cbf(x), mk, f32(params), false, bf(dx), nullptr, x.numel() / C, C, cur_stream());
+  return dx;
+}
+
 // Backward of bn_fwd_from_sums_dual: (dx, dx2) and both BatchNorms' dgamma / dbeta from one masked dy (dy and the
 // packed ReLU mask read once per pass). sums / sums2 (optional, together): the reduction done by dy's producer,
 // sums (sum g, sum g (x - mean)) and sums2 (slot 1: sum g (x2 - mean2)).
@@ -299,6 +331,10 @@ void bind_batchnorm(pybind11::module_& m) {
         "eps"_a);
   m.def("bn_bwd_relu_from_sums", &bn_bwd_relu_from_sums, "relu_x BatchNorm backward from a producer's sums");
   m.def("bn_bwd_from_sums", &bn_bwd_from_sums, "BatchNorm backward from a producer's reduction sums (final + apply)");
+  m.def("bn_bwd_params", &bn_bwd_params, "dy"_a, "x"_a, "mask"_a, "sums"_a, "mean"_a, "invstd"_a, "gamma"_a, "beta"_a,
+        "dgamma"_a, "dbeta"_a, "first half of a masked BatchNorm backward: dgamma, dbeta, params [sc | B | D | shift]");
+  m.def("bn_bwd_apply", &bn_bwd_apply, "dy"_a, "x"_a, "mask"_a, "params"_a,
+        "second half of a masked BatchNorm backward: dx from bn_bwd_params' table");
   m.def("bn_bwd_dual_from_sums", &bn_bwd_dual_from_sums, "bn_bwd_dual from a producer's reduction sums");
   m.def("bn_relu_maxpool", &bn_relu_maxpool, "x"_a, "sums"_a, "gamma"_a, "beta"_a, "run_mean"_a, "run_var"_a,
         "momentum"_a, "eps"_a, "want_link"_a = false);

@@ -116,8 +116,11 @@ Tensor conv3x3_dgrad_bnstats(Tensor gy, Tensor wt, Tensor x, Tensor gamma, Tenso
 // returns dz [M, C] = gy [M, K] . w [K, C]; writes (accumulate: adds) dw [K, C] fp32 = gy^T . relu(bf16(x scale +
 // shift)) with xform = fp32 [2, C] (scale | shift), and adds the BatchNorm-backward sums of dz (g = relu_on(x) ? dz : 0:
 // sum g, sum g (x - mean)) into sums, zeroed fp32 [conv_stat_replicas, 2, C].
+// x3, mask, params (optional, together): gy is the incoming dy of the residual BatchNorm that produced the convolution's
+// output, whose backward the kernel applies as it loads -- gy's tiles become bf16(fma(sc, mask ? dy : 0, fma(B, x3, D)))
+// with x3 bf16 [M, K], mask the packed ReLU bits uint8 [M, K / 8] and params fp32 [sc | B | D] (3K or more).
 Tensor bwd1x1_fused(Tensor gy, Tensor x, Tensor w, Tensor xform, Tensor gamma, Tensor beta, Tensor mean, Tensor invstd,
-                    Tensor dw, Tensor sums, bool accumulate) {
+                    Tensor dw, Tensor sums, bool accumulate, OptTensor x3, OptTensor mask, OptTensor params) {
   check_bf16_dense(gy, 2, "gy"); check_bf16_dense(x, 2, "x"); check_bf16_dense(w, 2, "w");
   const long M = gy.size(0), K = gy.size(1), C = x.size(1);
   TORCH_CHECK(x.size(0) == M && w.size(0) == K && w.size(1) == C, "shapes: gy [M, K], x [M, C], w [K, C]");
@@ -127,9 +130,24 @@ Tensor bwd1x1_fused(Tensor gy, Tensor x, Tensor w, Tensor xform, Tensor gamma, T
   TORCH_CHECK(dw.numel() == K * C, "dw must have K * C fp32 elements");
   check_channel_f32(xform, 2 * C, "xform (BatchNorm scale | shift)");
   const k8s_amd::BnBwdSums bb = bn_bwd_sums(x, mean, sums, {}, gamma, beta, invstd, {}, {}, {});
+  k8s_amd::Bwd1x1Bn3 bn3;
+  const bool onload = x3 || mask || params;
+  if (onload) {
+    TORCH_CHECK(x3 && mask && params, "bwd1x1_fused: x3, mask and params come together");
+    check_bf16_dense(*x3, 2, "x3");
+    TORCH_CHECK(x3->size(0) == M && x3->size(1) == K, "x3: the shape of gy, [M, K]");
+    bn3.mask = check_bit_mask(*mask, M * K, "mask");
+    check_aligned(*mask, "mask");
+    check_cuda(*params, "params"); check_dtype(*params, at::kFloat, "params"); check_aligned(*params, "params");
+    TORCH_CHECK(params->numel() >= 3 * K, "params: fp32 [sc | B | D], 3K elements or more");
+    TORCH_CHECK(x3->device() == gy.device() && mask->device() == gy.device() && params->device() == gy.device(),
+                "x3, mask and params: on gy's device");
+    bn3.x3 = cbf(*x3);
+    bn3.params = f32(*params);
+  }
   Tensor dz = torch::empty({M, C}, gy.options());
   launch_bwd1x1_fused(cbf(gy), cbf(x), cbf(w), f32(xform), bb.gamma, bb.beta, bb.mean, bb.invstd, bf(dz), f32(dw),
-                      bb.sums, M, (int)C, (int)K, accumulate, cur_stream());
+                      bb.sums, M, (int)C, (int)K, accumulate, cur_stream(), onload ? &bn3 : nullptr);
   return dz;
 }
 
@@ -219,7 +237,7 @@ void bind_conv(pybind11::module_& m) {
   m.def("conv_wgrad", &conv_wgrad, "x"_a, "dy"_a, "dw"_a, "stride"_a, "pad"_a, "dil"_a, "splits"_a, "accumulate"_a,
         "xform"_a = py::none());
   m.def("bwd1x1_fused", &bwd1x1_fused, "gy"_a, "x"_a, "w"_a, "xform"_a, "gamma"_a, "beta"_a, "mean"_a, "invstd"_a,
-        "dw"_a, "sums"_a, "accumulate"_a,
+        "dw"_a, "sums"_a, "accumulate"_a, "x3"_a = py::none(), "mask"_a = py::none(), "params"_a = py::none(),
         "1x1 data gradient, normalize-on-load weight gradient and BatchNorm-backward sums in one pass (bwd1x1_fused.hip)");
   m.def("bwd1x1_fused_ok", [](int64_t M, int64_t C, int64_t K) {
     return C <= 1024 && K <= 4096 && k8s_amd::bwd1x1_fused_ok(M, (int)C, (int)K);

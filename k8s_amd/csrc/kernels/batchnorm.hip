@@ -938,9 +938,17 @@ static void launch_bn_bwd_apply(const uint16_t* dy, const uint16_t* x, const uin
                      (int)relu_x, dx, dres, (int)nvec, C, make_fastdiv(C / 8), order);
 }
 
-void launch_bn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const float* invstd, const float* gamma,
-                   const float* beta, bool relu_x, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta,
-                   float* work, float* params, long M, int C, hipStream_t st, const uint8_t* mask) {
+// The first half of a BatchNorm backward: dgamma, dbeta and the params table [sc | B | D | shift] that the apply pass
+// -- launch_bn_bwd_apply_pass, or a consumer of dx that applies it on load (bwd1x1_fused.hip) -- reads. sums: the
+// reduction done by dy's producer ([nrep][2][C]); null: the reduce sweep over dy and x here (work: bn_workspace_floats).
+void launch_bn_bwd_params(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* sums, int nrep,
+                          const float* mean, const float* invstd, const float* gamma, const float* beta, bool relu_x,
+                          float* dgamma, float* dbeta, float* work, float* params, long M, int C, hipStream_t st) {
+  if (sums) {
+    hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums, nrep, C, dgamma,
+                       dbeta, 1.f / (float)M, mean, invstd, gamma, beta, params);
+    return;
+  }
   BnGeom g = bn_geom(C, M);
   const int nb = bn_reduce_blocks(M, g);
   // (round 3: the residual-BN reduce in address order, and its apply descending behind it, measured slower than
@@ -954,6 +962,19 @@ void launch_bn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, con
                        gamma, beta, (int)relu_x, M, C, g.tpr, g.rows_per_iter, work, mask, rdir);
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, FIN_CH)), dim3(256), 0, st, work, nb, C, dgamma, dbeta,
                      1.f / (float)M, mean, invstd, gamma, beta, params);
+}
+
+// The second half: dx (and dres) from dy, x, the mask or relu_x, and launch_bn_bwd_params' table.
+void launch_bn_bwd_apply_pass(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* params,
+                              bool relu_x, uint16_t* dx, uint16_t* dres, long M, int C, hipStream_t st) {
+  launch_bn_bwd_apply(dy, x, mask, params, relu_x, dx, dres, M, C, st);
+}
+
+void launch_bn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const float* invstd, const float* gamma,
+                   const float* beta, bool relu_x, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta,
+                   float* work, float* params, long M, int C, hipStream_t st, const uint8_t* mask) {
+  launch_bn_bwd_params(dy, x, mask, nullptr, 0, mean, invstd, gamma, beta, relu_x, dgamma, dbeta, work, params, M, C,
+                       st);
   launch_bn_bwd_apply(dy, x, mask, params, relu_x, dx, dres, M, C, st);
 }
 
@@ -963,8 +984,8 @@ void launch_bn_bwd_from_sums(const uint16_t* dy, const uint16_t* x, const uint8_
                              const float* mean, const float* invstd, const float* gamma, const float* beta,
                              uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta, float* params, long M, int C,
                              hipStream_t st) {
-  hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums, nrep, C, dgamma,
-                     dbeta, 1.f / (float)M, mean, invstd, gamma, beta, params);
+  launch_bn_bwd_params(dy, x, mask, sums, nrep, mean, invstd, gamma, beta, false, dgamma, dbeta, nullptr, params, M,
+                       C, st);
   launch_bn_bwd_apply(dy, x, mask, params, false, dx, dres, M, C, st);
 }
 

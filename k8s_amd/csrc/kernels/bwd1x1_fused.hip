@@ -29,6 +29,33 @@
 //    Measured (rocprofv3 --pmc, batch 3072): SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.39 at K = 256 and 0.37 at
 //    K = 512 over the whole kernel -- more than the fragment reads' layout predicts; the 8-B staging writes of dz and
 //    the element pass have not been looked at separately.
+//
+// ONLOAD (launch_bwd1x1_fused with a Bwd1x1Bn3): gy is not stored anywhere. It is dx3, the gradient the residual
+// BatchNorm after the convolution (bn3) would have written, dx3 = bf16(fma(sc, mask ? dy : 0, fma(B, x3, D))) -- the
+// expression, nesting and rounding helper of bn_bwd_apply_kernel -- and the kernel forms it tile by tile from that
+// BatchNorm's incoming dy, its input x3, its packed ReLU mask and its [sc | B | D] table, which is complete before
+// this kernel starts. The apply pass (read dy, x3, mask; write dx3) and this kernel's read of dx3 go away: 22.5 GB ->
+// 12.6 GB at batch 3072 / 56x56.
+//  * A stage is [dy image | x3 image | mask rows | x image]: the x3 image has the dy image's layout (same swizzle, same
+//    lane -> unit map), the mask tile is RS * K / 8 contiguous bytes, one or two waves' 16-B loads. That is 74 KB
+//    (K = 256) or 70 KB (K = 512) a stage, so the ring has two slots.
+//  * vmcnt: with two slots no younger stage is in flight when stage s is waited for -- stage s + 1 is issued after
+//    the barrier that follows the wait, into the slot stage s - 1's dW reads have just left -- so the wait is
+//    vmcnt(0) in every iteration, whatever a wave's load count per stage (2 LG, +1 for the mask waves, +1 for the x
+//    waves), and the dz stores of stage s - 1, long issued, cost it nothing. Nothing else loads through VGPRs inside
+//    the loop. The loads of stage s + 1 then have all of stage s (transform, dz, element pass, dW) to land.
+//  * After that barrier every thread rewrites its LG 16-B units of the dy image in place (it reads the dy unit, the x3
+//    unit at the same offset and the mask byte of (row, unit)), and one more barrier separates the pass from the dz
+//    MFMAs and the transposed dW reads. Everything after the tile is the plain form's code.
+//  * The table: at K = 256 a thread's units lie 16 rows apart, which swz_g maps to the same channel group, so its
+//    3 x 8 constants stay in registers; at K = 512 they lie 8 rows apart (two groups), w's fragments and the dW
+//    accumulators hold 128 VGPRs, and the table sits in LDS (fp32 [3K], read four channels at a time).
+//  * Rows past M: the plain form's zero line would turn into fma(B, x3, D) != 0 here, so this form reads the tile's
+//    last valid row in their place (which also makes every load a workgroup-uniform base plus a 32-bit lane offset:
+//    the per-lane 64-bit addresses and the zero-line select did not fit in the registers left at K = 512) and the
+//    transform writes zeros for them: the zero gy rows the rest of the kernel relies on.
+//  * At K = 512 both workgroups of a pair transform the whole tile (duplicated VALU / LDS work); measured per layer
+//    (benchmarks/bn3_onload.py) the form still beats apply + plain there, by less than at K = 256.
 #include <algorithm>
 #include <stdexcept>
 
@@ -65,7 +92,10 @@ __device__ __forceinline__ void tr_load(TrRaw& r, const char* img, int rb, int k
 #define K8S_LDS_TIE4(w, a, b, c, d) asm volatile(w : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
 
 struct Args {
-  const uint16_t *gy, *x, *w;
+  const uint16_t *gy, *x, *w;  // ONLOAD: gy is dy, and the tile becomes dx3 from the next three
+  const uint16_t* x3;
+  const uint8_t* mask;
+  const float* params;
   const float *xform, *gamma, *beta, *mean, *invstd;
   uint16_t* dz;
   float* dw;
@@ -80,11 +110,21 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 //   <256, 64, 3, 1>: 3 x 40 KB ring + 8 KB staging;  <512, 32, 4, 2>: 4 x 36 KB ring + 4 KB staging
-template <int K, int RS, int NSLOT, int HALVES>
+//   ONLOAD <256, 64, 2, 1>: 2 x 74 KB ring + 8 KB;   <512, 32, 2, 2>: 2 x 70 KB ring + 4 KB + 7.25 KB of tables
+template <int K, int RS, int NSLOT, int HALVES, bool ONLOAD>
 __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
   constexpr int RB = K * 2, UG = K / 8;
-  constexpr int IMG_G = RS * RB, IMG_X = RS * 128, STAGE = IMG_G + IMG_X, RING = NSLOT * STAGE;
+  constexpr int IMG_G = RS * RB, IMG_X = RS * 128;
+  constexpr int IMG_M = ONLOAD ? RS * UG : 0;  // packed mask rows: UG bytes each
+  constexpr int OFF_X = IMG_G + (ONLOAD ? IMG_G + IMG_M : 0);  // [gy | x3 | mask | x]
+  constexpr int STAGE = OFF_X + IMG_X, RING = NSLOT * STAGE;
   constexpr int LG = RS * UG / THREADS;  // gy LDS-DMA per thread per stage
+  constexpr int LPS = ONLOAD ? 2 * LG : LG;  // ... and the LDS-DMA every wave issues per stage
+  // dx3's per-channel constants (sc | B | D): a thread's logical unit is the same for all its LG units when the rows
+  // j * THREADS / UG apart agree in the bits swz_g reads (K = 256) -- registers; else an fp32 [3K] table in LDS
+  constexpr bool TREG = ONLOAD && (THREADS / UG) % 16 == 0;
+  constexpr bool TLDS = ONLOAD && !TREG;
+  static_assert(!ONLOAD || (IMG_M % 1024 == 0 && IMG_M / 1024 <= THREADS / 64), "mask tile: whole 1-KB wave loads");
   constexpr int XT = RS * 8;             // 16-B units of an x tile: the threads of the element pass
   constexpr int NKS = K / 32, KW = K / 8, KTW = KW / 16;
   static_assert(LG * THREADS == RS * UG && XT % 64 == 0 && XT <= THREADS && (RS == 32 || RS == 64), "tile");
@@ -92,9 +132,11 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
   // the element pass's per-channel constants (xform scale | shift, the BatchNorm's affine pair, mean): registers, or
   // at K = 512 -- where w's fragments and the dW accumulators take 128 -- a 5 x 64 fp32 table behind the staging tile
   constexpr bool PLDS = K > 256;
-  __shared__ __attribute__((aligned(1024))) char smem[RING + IMG_X + (PLDS ? 5 * CT * 4 : 0)];
+  __shared__ __attribute__((aligned(1024))) char smem[RING + IMG_X + (PLDS ? 5 * CT * 4 : 0) + (TLDS ? 3 * K * 4 : 0)];
+  static_assert(sizeof(smem) <= 160 * 1024, "LDS");
   char* stg = smem + RING;
   float* ptab = reinterpret_cast<float*>(stg + IMG_X);
+  float* btab = ptab + (PLDS ? 5 * CT : 0);
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -149,6 +191,24 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
       }
     }
   }
+  // ---- ONLOAD: the channel unit of this thread's LG units of the gy image, and its constants
+  const int tup = tid % UG, trow = tid / UG;
+  float tsc[8], tB[8], tD[8];
+  if constexpr (TREG) {
+    const float* t = a.params + (tup ^ swz_g(trow)) * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      tsc[j] = t[j];
+      tB[j] = t[K + j];
+      tD[j] = t[2 * K + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(tsc[j]), "+v"(tB[j]), "+v"(tD[j]));
+  }
+  if constexpr (TLDS) {
+    static_assert(!TLDS || PLDS, "the table's stores are ordered by the PLDS barrier");
+    for (int i = tid; i < 3 * K; i += THREADS) btab[i] = a.params[i];
+  }
   // every ordinary load is consumed here, before the first LDS-DMA is issued
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(wf[ks]));
@@ -162,6 +222,26 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
   auto issue = [&](int slot, int i) {
     char* st = smem + slot * STAGE;
     const long m0 = (long)(pair + i * a.npairs) * RS;
+    if constexpr (ONLOAD) {
+      // rows past M read the tile's last valid row instead of the zero line -- a workgroup-uniform base and a 32-bit
+      // offset per lane, which the registers this form has left need -- and the transform pass zeroes them
+      const unsigned last = (unsigned)min((long)RS - 1, M - 1 - m0);
+      const uint16_t* gb = a.gy + m0 * K;
+      const uint16_t* xb = a.x3 + m0 * K;
+#pragma unroll
+      for (int j = 0; j < LG; ++j) {
+        const unsigned row = j * (THREADS / UG) + trow;
+        const unsigned off = min(row, last) * K + (tup ^ swz_g(row)) * 8;
+        glds16(gb + off, st + j * (THREADS * 16) + wid * 1024);
+        glds16(xb + off, st + IMG_G + j * (THREADS * 16) + wid * 1024);
+      }
+      if (wid < IMG_M / 1024) {  // the tile's mask rows are contiguous: lane = 16 B of row q * 16 / UG
+        const unsigned q = (wid * 64 + lane) * 16;
+        glds16(a.mask + m0 * UG + min(q / UG, last) * UG + q % UG, st + 2 * IMG_G + wid * 1024);
+      }
+      if (wid < XT / 64) glds16(a.x + m0 * C + min((unsigned)erow, last) * C + ecol, st + OFF_X + wid * 1024);
+      return;
+    }
 #pragma unroll
     for (int j = 0; j < LG; ++j) {
       const int sl = j * THREADS + tid, row = sl / UG, up = sl % UG;
@@ -173,7 +253,7 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
     if (wid < XT / 64) {
       const long m = m0 + erow;
       const void* src = m < M ? (const void*)(a.x + m * C + ecol) : (const void*)g_zero16;
-      glds16(src, st + IMG_G + wid * 1024);
+      glds16(src, st + OFF_X + wid * 1024);
     }
   };
 
@@ -187,16 +267,55 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
   for (int s = 0; s < pre; ++s) issue(s, s);
   int slot = 0;
   for (int s = 0; s < n; ++s) {
-    // stage s landed: of the younger stages in flight each wave counts its LG gy loads (the x load of the waves that
-    // have one, and the dz stores, only make the wait stricter)
+    // stage s landed: of the younger stages in flight each wave counts the LPS loads every wave issues per stage (the
+    // x and mask loads of the waves that have one, and the dz stores, only make the wait stricter). ONLOAD's two-slot
+    // ring never has a younger stage in flight here -- stage s + 1 is issued below, after the barrier -- so its wait
+    // is always vmcnt(0), whatever a stage's load count.
     const int younger = min(n - 1, s + NSLOT - 2) - s;
-    if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LG) : "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LG) : "memory");
+    if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * LPS) : "memory");
+    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     lds_barrier();  // every wave's share of stage s is in LDS; stage s-1's reads are done
     if (s + NSLOT - 1 < n) issue(slot == 0 ? NSLOT - 1 : slot - 1, s + NSLOT - 1);  // into the slot of stage s-1
     char* G = smem + slot * STAGE;
-    char* X = G + IMG_G;
+    char* X = G + OFF_X;
+
+    // ---- ONLOAD: the dy image becomes dx3 = bf16(fma(sc, mask ? dy : 0, fma(B, x3, D))) in place, unit by unit (the
+    // expression and rounding of bn_bwd_apply_kernel); rows past M become the zero rows the rest relies on
+    if constexpr (ONLOAD) {
+      const int last = (int)min((long)RS - 1, M - 1 - (long)(pair + s * a.npairs) * RS);
+#pragma unroll
+      for (int j = 0; j < LG; ++j) {
+        const int row = j * (THREADS / UG) + trow;
+        const int u = tup ^ swz_g(row);
+        char* gp = G + j * (THREADS * 16) + tid * 16;
+        const bf16x8_t gv = *reinterpret_cast<const bf16x8_t*>(gp);
+        const bf16x8_t xv = *reinterpret_cast<const bf16x8_t*>(gp + IMG_G);
+        const uint32_t bits = *reinterpret_cast<const uint8_t*>(G + 2 * IMG_G + row * UG + u);
+        float o[8];
+#pragma unroll
+        for (int h = 0; h < 8; h += 4) {  // (TLDS: 12 table values live at a time, not 24 -- w and dW hold 128)
+          if constexpr (TLDS) {
+            const float* t = btab + u * 8 + h;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              tsc[h + i] = t[i];
+              tB[h + i] = t[K + i];
+              tD[h + i] = t[2 * K + i];
+            }
+          }
+#pragma unroll
+          for (int i = h; i < h + 4; ++i) {
+            const float g = (bits >> i) & 1u ? bf2f((uint16_t)gv[i]) : 0.f;
+            o[i] = __builtin_fmaf(tsc[i], g, __builtin_fmaf(tB[i], bf2f((uint16_t)xv[i]), tD[i]));
+            o[i] = row <= last ? o[i] : 0.f;
+          }
+          if constexpr (TLDS) asm volatile("" ::: "memory");  // (the next table reads stay behind this half's use)
+        }
+        *reinterpret_cast<bf16x8_t*>(gp) = pack_bf16x8(o);
+      }
+      lds_barrier();  // the dx3 tile is complete
+    }
 
     // ---- dz tile: rows rh * RS/2 .., channels ct * 16 ..; lane holds row (l & 15), channels 4 (l >> 4) + r
     {
@@ -332,23 +451,31 @@ bool bwd1x1_fused_ok(long M, int C, int K) {
   return M >= 1 && M < (1L << 31) && ((C == 64 && K == 256) || (C == 128 && K == 512));
 }
 
+// bn3: null, or the residual BatchNorm's backward applied on load -- gy is then its incoming dy, and the kernel forms
+// dx3 = fma(sc, mask ? dy : 0, fma(B, x3, D)) tile by tile instead of reading it (x3 [M][K] bf16, mask [M][K / 8]
+// packed bits, params fp32 [sc | B | D], 3K or more).
 void launch_bwd1x1_fused(const uint16_t* gy, const uint16_t* x, const uint16_t* w, const float* xform,
                          const float* gamma, const float* beta, const float* mean, const float* invstd, uint16_t* dz,
-                         float* dw, float* sums, long M, int C, int K, bool accumulate, hipStream_t st) {
+                         float* dw, float* sums, long M, int C, int K, bool accumulate, hipStream_t st,
+                         const Bwd1x1Bn3* bn3) {
   using namespace b1f;
   if (!bwd1x1_fused_ok(M, C, K)) throw std::runtime_error("bwd1x1_fused: (C, K) = (64, 256) or (128, 512), M < 2^31");
+  if (bn3 && !(bn3->x3 && bn3->mask && bn3->params)) throw std::runtime_error("bwd1x1_fused: x3, mask and params");
   if (!accumulate) (void)hipMemsetAsync(dw, 0, (size_t)K * C * sizeof(float), st);
-  Args a{gy, x, w, xform, gamma, beta, mean, invstd, dz, dw, sums, (int)M, C, 0, 0};
+  Args a{gy, x, w, nullptr, nullptr, nullptr, xform, gamma, beta, mean, invstd, dz, dw, sums, (int)M, C, 0, 0};
+  if (bn3) a.x3 = bn3->x3, a.mask = bn3->mask, a.params = bn3->params;
   const int cus = std::max(1, planner_cus());
   if (C == 64) {
     a.ntiles = (int)((M + 63) / 64);
     a.npairs = cus;
-    hipLaunchKernelGGL((bwd1x1_fused_kernel<256, 64, 3, 1>), dim3(cus), dim3(THREADS), 0, st, a);
+    if (bn3) hipLaunchKernelGGL((bwd1x1_fused_kernel<256, 64, 2, 1, true>), dim3(cus), dim3(THREADS), 0, st, a);
+    else hipLaunchKernelGGL((bwd1x1_fused_kernel<256, 64, 3, 1, false>), dim3(cus), dim3(THREADS), 0, st, a);
   } else {
     const int grid = std::max(16, cus / 16 * 16);  // pairs of workgroups, 8 pairs (one per XCD) at a time
     a.ntiles = (int)((M + 31) / 32);
     a.npairs = grid / 2;
-    hipLaunchKernelGGL((bwd1x1_fused_kernel<512, 32, 4, 2>), dim3(grid), dim3(THREADS), 0, st, a);
+    if (bn3) hipLaunchKernelGGL((bwd1x1_fused_kernel<512, 32, 2, 2, true>), dim3(grid), dim3(THREADS), 0, st, a);
+    else hipLaunchKernelGGL((bwd1x1_fused_kernel<512, 32, 4, 2, false>), dim3(grid), dim3(THREADS), 0, st, a);
   }
 }
 

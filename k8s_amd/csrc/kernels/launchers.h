@@ -90,6 +90,13 @@ constexpr int kConvStatReplicas = 32;  // must match STAT_REPL in gemm.hip
 void launch_bn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const float* invstd, const float* gamma,
                    const float* beta, bool relu_x, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta,
                    float* work, float* params, long M, int C, hipStream_t st, const uint8_t* mask = nullptr);
+// launch_bn_bwd / launch_bn_bwd_from_sums in their two halves: dgamma, dbeta and the params table [sc | B | D | shift]
+// (sums null: the reduce sweep here, work = bn_workspace_floats), then the apply pass that reads it
+void launch_bn_bwd_params(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* sums, int nrep,
+                          const float* mean, const float* invstd, const float* gamma, const float* beta, bool relu_x,
+                          float* dgamma, float* dbeta, float* work, float* params, long M, int C, hipStream_t st);
+void launch_bn_bwd_apply_pass(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* params,
+                              bool relu_x, uint16_t* dx, uint16_t* dres, long M, int C, hipStream_t st);
 // packed ReLU bits of a bf16 tensor (bit j of byte e = y[8e + j] > 0), nvec = numel / 8
 void launch_relu_mask(const uint16_t* y, uint8_t* mask, long nvec, hipStream_t st);
 
@@ -251,10 +258,20 @@ void launch_wgrad_stream(const uint16_t* x, const uint16_t* dy, float* dw, int N
 // in one pass over gy [M][K] and x [M][C]: dz = gy . w (bf16), dw [K][C] fp32 (+)= gy^T . relu(bf16(x scale + shift))
 // (xform = fp32 [2][C] scale | shift), and the BatchNorm-backward sums of dz (as BnBwdSums, relu kind) into the zeroed
 // sums [kConvStatReplicas][2][C]. (C, K) = (64, 256) or (128, 512), M < 2^31; dw is zeroed first unless accumulating.
+// bn3 (optional): gy is the incoming dy of the residual BatchNorm that produced the convolution's output, and the kernel
+// applies that BatchNorm's backward as it loads: its gy tile is bf16(fma(sc, mask ? dy : 0, fma(B, x3, D))), the bits
+// bn_bwd_apply_kernel would have written, never stored. x3 [M][K] bf16, mask [M][K / 8] packed ReLU bits, params fp32
+// [sc | B | D] (3K or more, launch_bn_bwd_params).
+struct Bwd1x1Bn3 {
+  const uint16_t* x3 = nullptr;
+  const uint8_t* mask = nullptr;
+  const float* params = nullptr;
+};
 bool bwd1x1_fused_ok(long M, int C, int K);
 void launch_bwd1x1_fused(const uint16_t* gy, const uint16_t* x, const uint16_t* w, const float* xform,
                          const float* gamma, const float* beta, const float* mean, const float* invstd, uint16_t* dz,
-                         float* dw, float* sums, long M, int C, int K, bool accumulate, hipStream_t st);
+                         float* dw, float* sums, long M, int C, int K, bool accumulate, hipStream_t st,
+                         const Bwd1x1Bn3* bn3 = nullptr);
 void launch_conv_dgrad_wtrans(const uint16_t* w, uint16_t* w2, int K, int R, int S, int C, hipStream_t st);
 // per-output-parity sub-weights of a stride-s dgrad (up to 16 parities x 16 taps), packed at off[p]
 struct DgradTaps {

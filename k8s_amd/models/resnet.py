@@ -31,13 +31,13 @@ class BN(nn.Module):
         self.register_buffer("running_var", torch.ones(c))
         self.momentum, self.eps = 0.1, 1e-5
 
-    def forward(self, x, residual=None, relu=True, res_link=None, dy_link=None, sub2=False):
+    def forward(self, x, residual=None, relu=True, res_link=None, dy_link=None, sub2=False, bn3_link=None):
         sums = None
         if isinstance(x, tuple):  # (conv output, fused statistics)
             x, sums = x
         return K.batch_norm_act(x, self.gamma, self.beta, self.running_mean, self.running_var, residual, relu,
                                 self.training, self.momentum, self.eps, sums=sums, res_link=res_link,
-                                dy_link=dy_link, sub2=sub2)
+                                dy_link=dy_link, sub2=sub2, bn3_link=bn3_link)
 
 
 class Conv(nn.Module):
@@ -94,13 +94,16 @@ class Bottleneck(nn.Module):
         # bn1 / bn2 + ReLU: normalised on load by the consuming convolution where ops.nn.BN_ONLOAD and its kernels
         # take it (ops.nn.bn_relu_conv: no apply pass, no z tensor), else applied by the BN kernel
         t = K.bn_relu_conv(t, self.bn1, self.conv2)
-        t = K.bn_relu_conv(t, self.bn2, self.conv3)
+        # identity block: bn3's backward apply pass is taken on load by conv3's fused backward where that kernel
+        # runs (ops.nn.Bn3Link: stages 1 and 2), so dx3 is never written
+        b3 = K.Bn3Link() if (self.down is None and self.training) else None
+        t = K.bn_relu_conv(t, self.bn2, self.conv3, bn3_link=b3)
         if dn is not None and fuse:
             y = K.bn_act_dual(t, self.bn3, dn, self.down_bn)
             if y is not None:
                 return y
             idn = self.down_bn(dn, relu=False, dy_link=mlink)
-        return self.bn3(t, residual=idn, relu=True, res_link=link or mlink, sub2=sub2)
+        return self.bn3(t, residual=idn, relu=True, res_link=link or mlink, sub2=sub2, bn3_link=b3)
 
 
 class ResNet(nn.Module):

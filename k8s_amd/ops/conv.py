@@ -38,7 +38,11 @@ from k8s_amd.ops._ext import load as _load
 # routes serving each; _plan_dgrad / _plan_dgrad_strided / _plan_bwd choose the route, ROUTES counts the ones that ran.
 
 STATS = {"hip_fwd": 0, "aten_fwd": 0, "hip_wgrad": 0, "aten_wgrad": 0, "hip_dgrad": 0, "aten_dgrad": 0,
-         "bn_bstats": 0, "hip_infer": 0, "aten_infer": 0}
+         "bn_bstats": 0, "hip_infer": 0, "aten_infer": 0,
+         # a residual BatchNorm that holds a nn.Bn3Link: fused 1x1 backwards that applied its backward on load, and
+         # apply passes (bn_bwd_apply) run for it instead, by its own backward or by the linked convolution's when it
+         # could not take the deferred form
+         "bn3_onload": 0, "bn3_apply": 0}
 ROUTES = collections.Counter()  # data-gradient route name -> times executed
 
 # (Round 5 built weight gradients on a second HIP stream -- each conv's dW kernel forked off the compute stream to
@@ -364,7 +368,9 @@ def _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link):
     """Which family forms a convolution backward's data gradient: "fused_1x1" (both gradients and the input
     BatchNorm + ReLU's backward sums in one pass over gy and x, bwd1x1_fused.hip), "stride1" (``_plan_dgrad``),
     "strided" (``_plan_dgrad_strided``) or "aten". Launches and allocates nothing. K8S_AMD_BWD1X1_FUSED=0 (read per
-    call: A/B, tests) keeps a normalize-on-load 1x1 convolution's two gradients on their two kernels."""
+    call: A/B, tests) keeps a normalize-on-load 1x1 convolution's two gradients on their two kernels. The fused family
+    is one route, "fused_1x1", in both of its forms; the launches that also apply the output BatchNorm's backward on
+    load (``conv_bwd``'s ``bn3``) are counted in ``STATS["bn3_onload"]``."""
     K, R, S, C = w.shape
     if (xform is not None and addend is None and R == 1 and S == 1 and stride == 1 and padding == 0
             and os.environ.get("K8S_AMD_BWD1X1_FUSED", "1") != "0" and _link_kind(bn_link, x.shape) == "relu"
@@ -391,14 +397,23 @@ def _finish_dw(p, gy, x, w, stride, padding):
         p.store.deposit(p, dw)
 
 
-def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None, x_sub=None, bn_link=None):
+def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None, x_sub=None, bn_link=None, bn3=None):
     """Returns dx (+ ``addend``, e.g. the residual branch's gradient of the same tensor, fused into the
     dgrad epilogue where our kernel runs) or None; deposits dw into ``p``'s flat gradient slot. ``xform``: the
     convolution's input is relu(bn(x)) normalised on load (see ``_wgrad_hip``); dx is then the gradient w.r.t.
     that normalised input. ``x_sub``: a 1x1 / pad-0 convolution's input already subsampled by its stride
-    (``nn._Conv2dNHWC`` with ``subsample_ok``): the weight gradient runs as the stride-1 product on it; ``x`` then only gives dx's shape."""
+    (``nn._Conv2dNHWC`` with ``subsample_ok``): the weight gradient runs as the stride-1 product on it; ``x`` then only gives dx's shape.
+    ``bn3``: a filled ``nn.Bn3Link`` -- the residual BatchNorm that read this convolution's output deferred its apply
+    pass, so ``gy`` may be that BatchNorm's incoming dy and not yet the gradient of the output. The fused 1x1 family
+    applies it on load when the link covers ``gy`` (``STATS["bn3_onload"]``); in every other case the apply pass runs
+    here first, on the ``gy`` received."""
     K, R, S, C = w.shape
     C_ = _load() if gy.is_cuda else None
+    if bn3 is not None and not (need_dx and bn3.covers(gy)
+                                and _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link) == "fused_1x1"):
+        STATS["bn3_apply"] += 1
+        gy = C_.bn_bwd_apply(gy.contiguous(), bn3.x3, bn3.mask, bn3.params)
+        bn3 = None
     if x_sub is not None:
         _wgrad_hip(C_, gy, x_sub, p.grad.view(p.shape), 1, 0, p.written)
         STATS["hip_wgrad"] += 1
@@ -414,11 +429,13 @@ def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None
     family = _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link) if need_dx else None
     if family == "fused_1x1":
         ROUTES[family] += 1
+        STATS["bn3_onload"] += bn3 is not None
         STATS["hip_wgrad"] += 1
         STATS["hip_dgrad"] += 1
         sums = _bn_sums(C_, bn_link, C, gy.device)
+        onload = {} if bn3 is None else {"x3": bn3.x3.view(-1, K), "mask": bn3.mask, "params": bn3.params}
         dz = C_.bwd1x1_fused(gy.view(-1, K), x.view(-1, C), w.view(K, C), xform, bn_link.gamma, bn_link.beta,
-                             bn_link.mean, bn_link.invstd, p.grad.view(K, C), sums, p.written).view(x.shape)
+                             bn_link.mean, bn_link.invstd, p.grad.view(K, C), sums, p.written, **onload).view(x.shape)
         _slot_written(p)
         bn_link.deposit(sums, None, dz)
         return dz

@@ -209,6 +209,49 @@ class MaskLink:
         self.mask = None
 
 
+def bn3_onload_on() -> bool:
+    """K8S_AMD_BN3_ONLOAD=0 (read per call: A/B, tests): a residual BatchNorm always runs its own apply pass."""
+    return os.environ.get("K8S_AMD_BN3_ONLOAD", "1") != "0" and os.environ.get("K8S_AMD_BWD1X1_FUSED", "1") != "0"
+
+
+class Bn3Link:
+    """Joins a residual BatchNorm (a bottleneck's bn3) to the normalize-on-load 1x1 convolution that produced its
+    input x3 (``bn_relu_conv(t, bn2, conv3, bn3_link=l)`` then ``batch_norm_act(x3, ..., bn3_link=l)``), x3 having no
+    other reader. dx3 = sc * (mask ? dy : 0) + B * x3 + D has one reader, that convolution's backward, which on the
+    fused kernel (bwd1x1_fused.hip) can form it tile by tile as it loads dy. So where the convolution said in its
+    forward that it can (``offer``), the BatchNorm's backward runs only its first half -- dgamma, dbeta and the
+    [sc | B | D] table -- leaves (x3, mask, params) and the identity of dy here (``fill``) and returns dy itself as
+    x3's gradient: no apply pass, no dx3 tensor. The convolution's backward takes the link (``take``) and hands it to
+    ``ops.conv.conv_bwd``, which applies the table on load if the gradient it received is that dy, unchanged
+    (``covers``), and otherwise runs the apply pass on what it received."""
+    __slots__ = ("y_key", "x3", "mask", "params", "dy_key")
+
+    def __init__(self):
+        self.y_key = self.x3 = self.mask = self.params = self.dy_key = None
+
+    def offer(self, y):
+        """The convolution's forward: its backward will be the fused family's for an output of this shape."""
+        self.y_key = (y.data_ptr(), tuple(y.shape))
+
+    def offered(self, x) -> bool:
+        return self.y_key == (x.data_ptr(), tuple(x.shape))
+
+    def fill(self, dy, x3, mask, params):
+        self.x3, self.mask, self.params, self.dy_key = x3, mask, params, BnStatLink._key(dy)
+
+    def covers(self, t) -> bool:
+        return self.dy_key == BnStatLink._key(t)
+
+    def take(self):
+        """The filled link's content as a link of its own (None if the BatchNorm did not defer); clears this one."""
+        if self.params is None:
+            return None
+        out = Bn3Link()
+        out.x3, out.mask, out.params, out.dy_key = self.x3, self.mask, self.params, self.dy_key
+        self.x3 = self.mask = self.params = self.dy_key = None
+        return out
+
+
 class _Conv2dNHWC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, anchor, p, stride, padding, with_stats, link=None, bn_link=None):
@@ -340,7 +383,7 @@ def stem_s2d_input(images, pad: int = 3):
 class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, anchor, pg, pb, run_mean, run_var, training, momentum, eps, relu, sums=None,
-                res_link=None, dy_link=None, stat_link=None, sub2=None):
+                res_link=None, dy_link=None, stat_link=None, sub2=None, bn3_link=None):
         x = x.contiguous()
         if res is not None:
             res = res.contiguous()
@@ -375,6 +418,9 @@ class _BnAct(torch.autograd.Function):
             else:
                 stat_link.fill_mask(x, mask, mean, pg.store)
             ctx.stat_link = stat_link
+        # the convolution that produced x takes this BatchNorm's apply pass into its backward (Bn3Link)
+        ctx.bn3_link = bn3_link if (bn3_link is not None and mask is not None and training
+                                    and bn3_link.offered(x)) else None
         return y
 
     @staticmethod
@@ -392,7 +438,13 @@ class _BnAct(torch.autograd.Function):
             handoff = isinstance(ctx.res_link, GradLink) and ctx.has_res and mask is not None
             want_dres = ctx.has_res and not (handoff or mask_out)
             pre = ctx.stat_link.take(dy) if ctx.stat_link is not None else None
-            if pre is not None and mask is None:  # relu_x: the reduction came with dy (BnStatLink)
+            if ctx.bn3_link is not None and not want_dres and bn3_onload_on():
+                # the first half only: x's producer applies the table as it loads dy (Bn3Link)
+                params = _C().bn_bwd_params(dy, x, mask, pre[0] if pre is not None else None, mean, invstd,
+                                            pg.master, pb.master, dg, db)
+                ctx.bn3_link.fill(dy, x, mask, params)
+                dx, dres = dy, None
+            elif pre is not None and mask is None:  # relu_x: the reduction came with dy (BnStatLink)
                 dx, dres = _C().bn_bwd_relu_from_sums(dy, x, pre[0], mean, invstd, pg.master, pb.master, dg, db)[0], None
             elif pre is not None:  # the reduction came with dy from its producer's epilogue (BnStatLink)
                 dx, dres = _C().bn_bwd_from_sums(dy, x, mask, pre[0], mean, invstd, pg.master, pb.master, dg, db,
@@ -400,6 +452,8 @@ class _BnAct(torch.autograd.Function):
             else:
                 dx, dres = _C().bn_bwd(dy, x, y, mean, invstd, pg.master, pb.master, ctx.relu_x, dg, db, want_dres,
                                        mask)
+            if ctx.bn3_link is not None and dx is not dy:
+                _conv_impl().STATS["bn3_apply"] += 1
             if handoff:
                 dres = MaskedGrad(dy, mask)
             elif mask_out:  # the producing plain BN masks dy itself (MaskLink)
@@ -413,7 +467,7 @@ class _BnAct(torch.autograd.Function):
         if ctx.has_res and isinstance(ctx.res_link, GradLink):  # hand dres to the node that adds it in a kernel
             ctx.res_link.grad, dres = dres, None
         return (dx, (dres if ctx.has_res else None), None, None, None, None, None, None, None, None, None, None, None,
-                None, None, None)
+                None, None, None, None)
 
 
 # Which BatchNorm + ReLU outputs of a ResNet bottleneck are normalised on load by the convolution that consumes them
@@ -451,7 +505,7 @@ class _BnReluConv(torch.autograd.Function):
     Returns (y, y's BN statistics sums) like ``conv2d_nhwc(..., with_stats=True)``."""
 
     @staticmethod
-    def forward(ctx, x, sums, anchor, pg, pb, run_mean, run_var, momentum, eps, pw, stride, padding):
+    def forward(ctx, x, sums, anchor, pg, pb, run_mean, run_var, momentum, eps, pw, stride, padding, bn3_link=None):
         C_ = _C()
         x = x.contiguous()
         M = x.numel() // x.shape[-1]
@@ -466,6 +520,14 @@ class _BnReluConv(torch.autograd.Function):
         ctx.x_requires_grad = x.requires_grad
         ctx.mark_non_differentiable(ysums)
         ctx.set_materialize_grads(False)
+        # the backward will be the fused family's (ops.conv._plan_bwd, but for the switches read per call): it can
+        # take the output BatchNorm's apply pass (Bn3Link)
+        ctx.bn3_link = None
+        K_, R, S, C = w.shape
+        if (bn3_link is not None and BN_BSTATS and R == 1 and S == 1 and stride == 1 and padding == 0
+                and C_.bwd1x1_fused_ok(M, C, K_)):
+            bn3_link.offer(y)
+            ctx.bn3_link = bn3_link
         return y, ysums
 
     @staticmethod
@@ -479,7 +541,8 @@ class _BnReluConv(torch.autograd.Function):
         if BN_BSTATS:
             link = BnStatLink()
             link.fill_relu(x, mean, invstd, pg.master, pb.master, pg.store)
-        dz = impl.conv_bwd(gy, x, pw.weight, ctx.stride, ctx.padding, True, pw, xform=params, bn_link=link)
+        bn3 = ctx.bn3_link.take() if ctx.bn3_link is not None else None
+        dz = impl.conv_bwd(gy, x, pw.weight, ctx.stride, ctx.padding, True, pw, xform=params, bn_link=link, bn3=bn3)
         dg, db, finish = _bn_param_grads(pg, pb, x.device)
         pre = link.take(dz) if link is not None else None
         if pre is not None:
@@ -487,7 +550,7 @@ class _BnReluConv(torch.autograd.Function):
         else:
             dx, _ = _C().bn_bwd(dz, x, None, mean, invstd, pg.master, pb.master, True, dg, db, False)
         finish()
-        return (dx if ctx.x_requires_grad else None,) + (None,) * 11
+        return (dx if ctx.x_requires_grad else None,) + (None,) * 12
 
 
 # Largest BatchNorm channel count normalised on load (K8S_AMD_ONLOAD_MAXC). The on-load operand path feeds the MFMAs
@@ -513,18 +576,18 @@ def onload_ok(x, conv) -> bool:
             bool(_C().conv3x3_staged_ok(x.shape[1], x.shape[2], C, K_, R, S, conv.stride, conv.pad)))
 
 
-def bn_relu_conv(t, bn, conv):
+def bn_relu_conv(t, bn, conv, bn3_link=None):
     """``conv(bn(t))`` for ``t = (x, sums)`` from ``conv2d_nhwc(..., with_stats=True)``, a training-mode ReLU
     BatchNorm ``bn`` (models/resnet.BN) and a convolution ``conv`` (models/resnet.Conv): normalised on load
     (``_BnReluConv``) where the kernels take it (``onload_ok``), else the separate BN apply + conv. Returns (y, y's
-    sums)."""
+    sums). ``bn3_link``: a Bn3Link shared with the residual BatchNorm that is y's only reader."""
     x, sums = t if isinstance(t, tuple) else (t, None)
     w = conv.w
     if (sums is not None and bn.training and _gpu(x) and x.dtype == torch.bfloat16 and x.shape[-1] % 64 == 0
             and w.weight.dtype == torch.bfloat16 and w.shape[0] % 8 == 0 and w.grad.dtype == torch.float32
             and onload_ok(x, conv)):
         return _BnReluConv.apply(x, sums, w.store.anchor, bn.gamma, bn.beta, bn.running_mean, bn.running_var,
-                                 bn.momentum, bn.eps, w, conv.stride, conv.pad)
+                                 bn.momentum, bn.eps, w, conv.stride, conv.pad, bn3_link)
     return conv(bn(t))
 
 
@@ -544,17 +607,18 @@ class SubLink:
 
 
 def batch_norm_act(x, pg, pb, run_mean, run_var, residual=None, relu=True, training=True, momentum=0.1,
-                   eps=1e-5, sums=None, res_link=None, dy_link=None, sub2=False):
+                   eps=1e-5, sums=None, res_link=None, dy_link=None, sub2=False, bn3_link=None):
     """y = act(BN(x) + residual) over the last (channel) dim of an NHWC tensor.
 
     ``sums`` (fp32 [2, C] from ``conv2d_nhwc(..., with_stats=True)``) skips the statistics pass.
     ``res_link``: the residual's gradient is handed to that GradLink (and NOT returned to autograd); the
     node consuming the link must add it (``conv2d_nhwc(..., grad_link=link)`` on the same tensor).
-    ``res_link`` may also be a MaskLink whose ``dy_link`` end is the plain BN that produced ``residual``."""
+    ``res_link`` may also be a MaskLink whose ``dy_link`` end is the plain BN that produced ``residual``.
+    ``bn3_link``: the Bn3Link given to the ``bn_relu_conv`` that produced ``x``, whose only reader this is."""
     link = BnStatLink() if (BN_BSTATS and relu and training and _gpu(x)) else None
     sub = SubLink() if (sub2 and SUB2_FUSED and sums is not None and _gpu(x)) else None
     y = _BnAct.apply(x, residual, pg.store.anchor, pg, pb, run_mean, run_var, training, momentum, eps, relu,
-                     sums, res_link, dy_link, link, sub)
+                     sums, res_link, dy_link, link, sub, bn3_link)
     if link is not None and link.kind is not None:
         y._k8s_bnstat = link
     if sub is not None and sub.y is not None:
