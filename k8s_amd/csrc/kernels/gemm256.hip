@@ -567,13 +567,43 @@ constexpr int LDS_BYTES = 2 * STAGE;   // 128 KB
 #define K8S_G4_MFMA(acc, b, a) \
   asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(b), "v"(a))
 
-// X: the transformer linears' bf16 epilogue extras -- bias (fp32, added before the one rounding of the staged
-// value), ReLU / GELU of the staged pre-activation, its copy to `pre` (what the activation backward reads) and a bf16
-// accumulate (C = result + old C; a residual's second gradient contribution) -- in the row-contiguous copy-out. Its
-// own instantiation so the plain kernels keep their code and registers.
+// What the copy-out of a bf16 tile does besides storing it. The output itself (C, ldc, bias, alpha, fp32 / bf16,
+// accumulate, the tall-K slab stride) is a g256::Epi, as for the ring kernel. Everything but a Linear without extras
+// runs on the X instantiations -- their own, so the plain kernels keep their code and registers.
+enum class EpiKind : int {
+  Linear,     // the transformer linears' extras in the row-contiguous copy-out: bias (fp32, added before the one
+              // rounding of the staged value), Epi::act (0 none, 1 ReLU, 2 GELU) of the staged pre-activation, its copy
+              // to Epi::pre (what the activation backward reads) and a bf16 accumulate (C = result + old C; a
+              // residual's second gradient contribution)
+  ActBwd,     // C = result * act'(act_in) and the column sums of the stored C (copy_out_x)
+  SwigluBwd,  // C = dgu from gu and the result (copy_out_x)
+  SwigluFwd,  // C = gu, h = silu(gate) up (copy_out_swiglu)
+  Rope,       // rotary embedding of the q / k heads (copy_out_rope)
+  BnStats,    // BatchNorm statistics of the stored C (copy_out_stats)
+  BnBwdSums,  // BatchNorm-backward sums of the stored C (copy_out_bnbwd)
+};
+// The operands of each kind (the others' stay null / 0); the copy_out_* comments say what they hold.
+struct Fused {
+  EpiKind kind;
+  const uint16_t* act_in;    // ActBwd: [M][N], Epi::act 1 (ReLU): the ReLU output, 2 (GELU): the pre-activation
+  float* colsum_part;        // ActBwd: [M / 128][N] partial column sums of C
+  const uint16_t* gu;        // SwigluBwd: [M][2N] gate | up
+  long up_off;               // SwigluBwd, blk 0: the up half's column offset (F)
+  int blk;                   // SwigluBwd: 0 gate | up halves, 64: blocks of 64 gate then 64 up columns
+  uint16_t* h;               // SwigluFwd: [M][N / 2]
+  const int* pos;            // Rope: [M] row positions
+  const float* table;        // Rope: [maxpos][64][2] (cos, sin)
+  int rot_cols;              // Rope: columns < rot_cols are q / k heads
+  float* stats;              // BnStats: [kConvStatReplicas][2][N]
+  const uint16_t* bn_x;      // BnBwdSums: the BatchNorm's input [M][N]
+  const float* bn_tab;       // BnBwdSums: [gamma | beta | mean | invstd] fp32 [4][N]
+  float* bn_sums;            // BnBwdSums: [kConvStatReplicas][2][N]
+};
+
 // Tall-K split (gridDim.y > 1, the weight gradients of outputs with fewer tiles than CUs): split y reduces K range
-// [y kps, min(K, (y + 1) kps)) into the fp32 slab at C + y * slab (plain store), combined by splitk_reduce; the last
-// split may be shorter, so the split count is free to fill the chip (9 BERT tiles x 28 splits = 252 blocks).
+// [y kps, min(K, (y + 1) kps)) into the fp32 slab at C + y * Epi::slab (plain store), combined by splitk_reduce; the
+// last split may be shorter, so the split count is free to fill the chip (9 BERT tiles x 28 splits = 252 blocks).
+
 // GELU(tanh) of 8 values, 2 at a time on the packed fp32 ALU (v_pk_mul / v_pk_fma): x * 1 / (1 + 2^(c (x + k1 x^3)))
 __device__ __forceinline__ void gelu8(float (&f)[8]) {
   const f32x2_t k1 = {0.044715f, 0.044715f};
@@ -589,18 +619,9 @@ __device__ __forceinline__ void gelu8(float (&f)[8]) {
   }
 }
 
-// the X copy-out (8 groups of 4 chunks of this wave's staged 128 x 128 tile): pre-activation copy, ACT (0 none, 1 ReLU,
-// 2 GELU) and ACC (C = result + old C, the old C of group g + 1 loaded before group g is processed, so each group
-// waits for loads issued a group earlier)
-// d/dx GELU(tanh) (elementwise.hip's act_bwd form: t = tanh(k0 (x + k1 x^3)) on v_exp / v_rcp)
-__device__ __forceinline__ float gelu_tanh_grad(float x) {
-  const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-  const float t = 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(2.8853900817779268f * k0 *
-                                                                                  (x + k1 * x * x * x)));
-  return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) * k0 * (1.f + 3.f * k1 * x * x);
-}
-
-// f *= GELU'(x) for 8 values, 2 at a time on the packed fp32 ALU (the gelu_tanh_grad formula)
+// f *= GELU'(x) for 8 values, 2 at a time on the packed fp32 ALU. d/dx GELU(tanh) in elementwise.hip's act_bwd form:
+// with t = tanh(k0 (x + k1 x^3)) = 1 - 2 / (1 + 2^(2 log2(e) k0 (x + k1 x^3))) on v_exp / v_rcp,
+// GELU'(x) = (1 + t) / 2 + x (1 - t^2) k0 (1 + 3 k1 x^2) / 2
 __device__ __forceinline__ void gelu_grad_mul8(float (&f)[8], const float (&xs)[8]) {
   const float k0 = 0.7978845608028654f, k1 = 0.044715f;
   const f32x2_t one = {1.f, 1.f}, half = {0.5f, 0.5f};
@@ -622,25 +643,27 @@ __device__ __forceinline__ void gelu_grad_mul8(float (&f)[8], const float (&xs)[
   }
 }
 
-// ACT < 0: the data gradient of a linear whose input is an activation's output, fused with that activation's
-// backward (-1 ReLU: `pre` holds the ReLU output; -2 GELU: the pre-activation): C = dgrad * act'(pre), and the
-// per-column sums of the stored bf16 C (the producing linear's bias gradient) -- this wave's 128 columns summed over
-// its 128 rows into one partial row of `cpart` (folded by colsum_fold_kernel). `pre` is read a group ahead, as the
-// accumulate's old C.
-// ACT = -3: SwiGLU backward (Llama's down-projection data gradient): C / pre are the [M][2F] dgu / gu buffers
-// (ldc = 2F), the GEMM's N = F columns are the gate half; with d = this data gradient, g = gate (pre at off), u = up
-// (pre at off + fo): dgate = d u silu'(g) at off, dup = d silu(g) at off + fo -- elementwise.hip's swiglu_bwd_kernel
-// formula on the same bf16 inputs, so the fused result is bit-identical to the two-pass one.
-template <int ACT, bool ACC, class Off, class Stg>
-__device__ __forceinline__ void copy_out_x(uint16_t* __restrict__ C, uint16_t* __restrict__ pre, const char* stg,
-                                           const Off& coff, const Stg& staged, float* __restrict__ cpart = nullptr,
-                                           long fo = 0) {
-  (void)stg;
-  static_assert(!(ACT < 0 && ACC), "activation backward without accumulate");
-  constexpr bool RD = ACC || ACT < 0;  // a bf16 operand per chunk read a group ahead (old C, or pre)
-  constexpr bool SW = ACT == -3;
+// The copy-out of the Linear, ActBwd and SwigluBwd kinds (8 groups of 4 chunks of this wave's staged 128 x 128 tile).
+// Linear: the pre-activation copy to `pre`, ACT (0 none, 1 ReLU, 2 GELU) and ACC (C = result + old C, the old C of
+// group g + 1 loaded before group g is processed, so each group waits for loads issued a group earlier).
+// ActBwd: the data gradient of a linear whose input is an activation's output, fused with that activation's backward
+// (ACT 1 ReLU: `in` holds the ReLU output; 2 GELU: the pre-activation): C = dgrad * act'(in), and the per-column sums
+// of the stored bf16 C (the producing linear's bias gradient) -- this wave's 128 columns summed over its 128 rows into
+// one partial row of `cpart` (folded by colsum_fold_kernel). `in` is read a group ahead, as the accumulate's old C.
+// SwigluBwd (Llama's down-projection data gradient): C / in are the [M][2F] dgu / gu buffers (ldc = 2F), the GEMM's
+// N = F columns are the gate half; with d = this data gradient, g = gate (in at off), u = up (in at off + fo):
+// dgate = d u silu'(g) at off, dup = d silu(g) at off + fo -- elementwise.hip's swiglu_bwd_kernel formula on the same
+// bf16 inputs, so the fused result is bit-identical to the two-pass one.
+template <EpiKind KIND, int ACT, bool ACC, class Off, class Stg>
+__device__ __forceinline__ void copy_out_x(uint16_t* __restrict__ C, uint16_t* __restrict__ pre,
+                                           const uint16_t* __restrict__ in, const Off& coff, const Stg& staged,
+                                           float* __restrict__ cpart = nullptr, long fo = 0) {
+  constexpr bool SW = KIND == EpiKind::SwigluBwd, BWD = SW || KIND == EpiKind::ActBwd;
+  static_assert(BWD || KIND == EpiKind::Linear, "copy_out_x: Linear, ActBwd or SwigluBwd");
+  static_assert(!(BWD && ACC), "activation backward without accumulate");
+  constexpr bool RD = ACC || BWD;  // a bf16 operand per chunk read a group ahead (old C, or in)
   bf16x8_t oldc[2][4], oldu[SW ? 2 : 1][SW ? 4 : 1];
-  const uint16_t* rsrc = ACT < 0 ? pre : C;
+  const uint16_t* rsrc = BWD ? in : C;
   float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if constexpr (RD) {
 #pragma unroll
@@ -679,14 +702,14 @@ __device__ __forceinline__ void copy_out_x(uint16_t* __restrict__ C, uint16_t* _
         *reinterpret_cast<bf16x8_t*>(C + off) = pack_bf16x8(dg);
         *reinterpret_cast<bf16x8_t*>(C + off + fo) = pack_bf16x8(du);
         continue;
-      } else if constexpr (ACT < 0) {
+      } else if constexpr (BWD) {
         float f[8], x[8];
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
           x[r] = bf2f((uint16_t)oldc[grp & 1][q][r]);
           f[r] = bf2f((uint16_t)v[r]);
         }
-        if constexpr (ACT == -1) {
+        if constexpr (ACT == 1) {
 #pragma unroll
           for (int r = 0; r < 8; ++r) f[r] = x[r] > 0.f ? f[r] : 0.f;
         } else {
@@ -718,7 +741,7 @@ __device__ __forceinline__ void copy_out_x(uint16_t* __restrict__ C, uint16_t* _
       *reinterpret_cast<bf16x8_t*>(C + off) = v;
     }
   }
-  if constexpr (ACT < 0 && !SW) {
+  if constexpr (BWD && !SW) {
     // lanes l, l ^ 16, l ^ 32, l ^ 48 hold the same 8 columns (chunk l & 15) of different rows
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
@@ -733,8 +756,8 @@ __device__ __forceinline__ void copy_out_x(uint16_t* __restrict__ C, uint16_t* _
   }
 }
 
-// ACT = 3: the gate|up projection with its SwiGLU in the epilogue (Llama). The weight's rows are laid out in blocks of
-// 64 gate rows then the 64 matching up rows, so each wave's staged 128 columns hold gate block b in columns 0-63 and up
+// SwigluFwd: the gate|up projection with its SwiGLU in the epilogue (Llama). The weight's rows are laid out in blocks
+// of 64 gate rows then the 64 matching up rows, so each wave's staged 128 columns hold gate block b in columns 0-63 and up
 // block b in 64-127 (the rotate-half pairing of copy_out_rope): chunk c's partner is chunk c + 8 of the same staged
 // row, no other wave's piece is read and no barrier is needed. Every wave stores its staged piece to C (= gu [M][2F],
 // what the backward reads), then h = silu(g) u (elementwise.hip swiglu_fwd_kernel's formula on the same bf16 inputs:
@@ -761,7 +784,7 @@ __device__ __forceinline__ void copy_out_swiglu(uint16_t* __restrict__ C, uint16
   }
 }
 
-// ACT = 4: the QKV projection with the rotary embedding of its q / k heads in the copy-out (Llama). A wave's staged
+// Rope: the QKV projection with the rotary embedding of its q / k heads in the copy-out (Llama). A wave's staged
 // 128 columns are exactly one head of D = 128; the rotate-half partner of chunk ch (8 columns) is chunk ch ^ 8 of the
 // same staged row, the angle table row is pos[row]. elementwise.hip rope_kernel's formula (explicit fmas, the same
 // rounding), so the fused output is bit-identical to the projection + the in-place rope pass it replaces. `rot`: this
@@ -804,28 +827,13 @@ __device__ __forceinline__ void copy_out_rope(uint16_t* __restrict__ C, const ch
   }
 }
 
-// ACT = 5: the BatchNorm statistics of the stored bf16 values (per-column sum / sum of squares -- the conv epilogue
-// statistics of gemm.hip, [kConvStatReplicas][2][N]) for ResNet's deep-reduction 1x1 convolutions. Every lane keeps the
-// sums of its fixed 8 columns (chunk lane & 15) over its rows; lanes l, l ^ 16, l ^ 32, l ^ 48 are folded by shuffles,
-// each wave parks its 128 + 128 partials at the head of its own (already copied-out) staged region, and after one
-// barrier thread t adds the two wave rows' partials of column t % 128 of wave column t / 128: 2 full-wave atomic
-// instructions per wave.
-template <class Off, class Stg>
-__device__ __forceinline__ void copy_out_stats(uint16_t* __restrict__ C, float* __restrict__ stats, char* smem,
-                                               char* stg, const Off& coff, const Stg& staged, int rep, int N, int n0) {
+// The end of the two statistics copy-outs: every lane holds two sums (sm, sq) of its fixed 8 columns (chunk lane & 15)
+// over its rows. Lanes l, l ^ 16, l ^ 32, l ^ 48 are folded by shuffles, each wave parks its 128 + 128 partials at the
+// head of its own (already copied-out) staged region, and after one barrier thread t adds the two wave rows' partials
+// of column t % 128 of wave column t / 128 to dst [kConvStatReplicas][2][N]: 2 full-wave atomic instructions per wave.
+__device__ __forceinline__ void add_column_sums(float (&sm)[8], float (&sq)[8], float* __restrict__ dst, char* smem,
+                                                char* stg, int rep, int N, int n0) {
   const int lane = threadIdx.x & 63;
-  float sm[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-  for (int it = 0; it < 32; ++it) {
-    const bf16x8_t v = staged(it);
-    *reinterpret_cast<bf16x8_t*>(C + coff(it)) = v;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const float f = bf2f((uint16_t)v[r]);
-      sm[r] += f;
-      sq[r] = __builtin_fmaf(f, f, sq[r]);
-    }
-  }
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     sm[r] += __shfl_xor(sm[r], 16);
@@ -847,12 +855,32 @@ __device__ __forceinline__ void copy_out_stats(uint16_t* __restrict__ C, float* 
   const int t = threadIdx.x, wcol = t >> 7, c = t & 127;
   const float* p0 = reinterpret_cast<const float*>(smem + (0 * 2 + wcol) * 32768);  // wave (wr 0, wc)
   const float* p1 = reinterpret_cast<const float*>(smem + (1 * 2 + wcol) * 32768);  // wave (wr 1, wc)
-  float* d = stats + (long)rep * 2 * N + n0 + wcol * 128 + c;
+  float* d = dst + (long)rep * 2 * N + n0 + wcol * 128 + c;
   atomicAdd(d, p0[c] + p1[c]);
   atomicAdd(d + N, p0[128 + c] + p1[128 + c]);
 }
 
-// ACT = 6 (a data gradient dx = dy . w): the BatchNorm-backward sums of dx for the relu(BN(x)) that produced the
+// BnStats: the BatchNorm statistics of the stored bf16 values (per-column sum / sum of squares -- the conv epilogue
+// statistics of gemm.hip, [kConvStatReplicas][2][N]) for ResNet's deep-reduction 1x1 convolutions (add_column_sums).
+template <class Off, class Stg>
+__device__ __forceinline__ void copy_out_stats(uint16_t* __restrict__ C, float* __restrict__ stats, char* smem,
+                                               char* stg, const Off& coff, const Stg& staged, int rep, int N, int n0) {
+  float sm[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, sq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (int it = 0; it < 32; ++it) {
+    const bf16x8_t v = staged(it);
+    *reinterpret_cast<bf16x8_t*>(C + coff(it)) = v;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const float f = bf2f((uint16_t)v[r]);
+      sm[r] += f;
+      sq[r] = __builtin_fmaf(f, f, sq[r]);
+    }
+  }
+  add_column_sums(sm, sq, stats, smem, stg, rep, N, n0);
+}
+
+// BnBwdSums (a data gradient dx = dy . w): the BatchNorm-backward sums of dx for the relu(BN(x)) that produced the
 // convolution's input (launchers.h BnBwdSums): g = relu_on(x) ? dx : 0, sums[rep][0][c] += sum g, [1][c] += sum g (x -
 // mean). x is read at the output positions (same layout), in two halves of 16 rows per lane, each half's loads issued
 // before the previous half is consumed; tab = [gamma | beta | mean | invstd] fp32 [4][N].
@@ -886,42 +914,18 @@ __device__ __forceinline__ void copy_out_bnbwd(uint16_t* __restrict__ C, const u
       sq[r] = __builtin_fmaf(g, xf - mu[r], sq[r]);
     }
   }
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    sm[r] += __shfl_xor(sm[r], 16);
-    sm[r] += __shfl_xor(sm[r], 32);
-    sq[r] += __shfl_xor(sq[r], 16);
-    sq[r] += __shfl_xor(sq[r], 32);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's staged reads are done: reuse its region
-  if (lane < 16) {
-    float* part = reinterpret_cast<float*>(stg);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      part[lane * 8 + r] = sm[r];
-      part[128 + lane * 8 + r] = sq[r];
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  g256::barrier();
-  const int t = threadIdx.x, wcol = t >> 7, c = t & 127;
-  const float* p0 = reinterpret_cast<const float*>(smem + (0 * 2 + wcol) * 32768);  // wave (wr 0, wc)
-  const float* p1 = reinterpret_cast<const float*>(smem + (1 * 2 + wcol) * 32768);  // wave (wr 1, wc)
-  float* d = sums + (long)rep * 2 * N + n0 + wcol * 128 + c;
-  atomicAdd(d, p0[c] + p1[c]);
-  atomicAdd(d + N, p0[128 + c] + p1[128 + c]);
+  add_column_sums(sm, sq, sums, smem, stg, rep, N, n0);
 }
 
 template <bool AMN, bool BMN, bool X>
 __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __restrict__ A, long lda,
-                                                             const uint16_t* __restrict__ B, long ldb, void* Cv,
-                                                             long ldc, int M, int N, int K, float alpha, int kps,
-                                                             g256r::SkArgs SK, int out_f32, int accumulate,
-                                                             const float* __restrict__ bias, int act,
-                                                             uint16_t* __restrict__ pre, long slab,
-                                                             float* __restrict__ cpart, const int* __restrict__ rpos,
-                                                             const float* __restrict__ rtab, int rcols) {
+                                                             const uint16_t* __restrict__ B, long ldb, g256::Epi E,
+                                                             Fused F, int M, int N, int K, int kps,
+                                                             g256r::SkArgs SK) {
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
+  void* Cv = E.c;
+  const long ldc = E.ldc;
+  const float alpha = E.alpha;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid >> 1, wc = wid & 1;
@@ -934,7 +938,7 @@ __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __r
     const int lam = g256r::xcd_remap(bid + gridDim.x * blockIdx.y, gridDim.x * gridDim.y);
     split = lam / gridDim.x;
     wg = lam - split * gridDim.x;
-    Cv = reinterpret_cast<float*>(Cv) + (long)split * slab;
+    Cv = reinterpret_cast<float*>(Cv) + (long)split * E.slab;
   } else if (bid < SK.full) {
     wg = g256r::xcd_remap(bid, SK.full);
     kps = K;
@@ -1085,8 +1089,8 @@ __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __r
   if constexpr (X) {
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      bj[j] = bias ? *reinterpret_cast<const f32x4_t*>(bias + n0 + wc * 128 + j * 16 + 4 * (lane >> 4))
-                   : f32x4_t{0.f, 0.f, 0.f, 0.f};
+      bj[j] = E.bias ? *reinterpret_cast<const f32x4_t*>(E.bias + n0 + wc * 128 + j * 16 + 4 * (lane >> 4))
+                     : f32x4_t{0.f, 0.f, 0.f, 0.f};
   }
 #pragma unroll
   for (int p = 0; p < 16; ++p) dma(p, 0, 0);
@@ -1189,8 +1193,8 @@ __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __r
     }
     __syncthreads();
   }
-  if (out_f32) {  // fp32 (the weight gradients, stored or accumulated into the flat slots): straight from the
-                  // fragments, 16 B per lane (4 lanes = one 64-B row piece)
+  if (E.out_f32) {  // fp32 (the weight gradients, stored or accumulated into the flat slots): straight from the
+                    // fragments, 16 B per lane (4 lanes = one 64-B row piece)
     float* C = reinterpret_cast<float*>(Cv);
 #pragma unroll
     for (int f = 0; f < 8; ++f) {
@@ -1205,7 +1209,7 @@ __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __r
         }
         v *= alpha;
         f32x4_t* cp = reinterpret_cast<f32x4_t*>(C + m * ldc + n0 + wc * 128 + j * 16 + 4 * g);
-        if (accumulate) v += *cp;
+        if (E.accumulate) v += *cp;
         *cp = v;
       }
     }
@@ -1245,46 +1249,63 @@ __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __r
     const int idx = it * 64 + lane, lr = idx >> 4, ch = idx & 15;
     return *reinterpret_cast<const bf16x8_t*>(stg + lr * 256 + ((ch ^ (lr & 15)) << 4));
   };
-  if (!X || (act == 0 && !accumulate && !pre)) {  // (a bias alone was added while staging: the plain copy)
+  if (!X || (F.kind == EpiKind::Linear && E.act == 0 && !E.accumulate && !E.pre)) {
+    // (a bias alone was added while staging: the plain copy)
 #pragma unroll 4
     for (int it = 0; it < 32; ++it) *reinterpret_cast<bf16x8_t*>(C + coff(it)) = staged(it);
   } else if constexpr (X) {
-    // the activation and the accumulate are compile-time in the loop body (copy_out<ACT, ACC>): with them as run-time
-    // values the compiler branched per ELEMENT and serialised every GELU chain (exp -> add -> rcp -> mul, s_nop
-    // between): BERT-base's FFN1 forward took 1013 us against 543 us for the bias-only QKV forward of 3/4 its FLOPs
-    if (act < 0) {  // activation backward (data-gradient form only): a partial row of column sums per (tile, wave row)
-      if constexpr (!AMN && BMN) {
-        if (act == -3) {  // SwiGLU backward: no column sums; the up half `slab` columns to the right
-          copy_out_x<-3, false>(C, pre, stg, coff, staged, nullptr, slab);
-        } else if (act == -4) {  // the same on the 64-blocked gate|up layout (copy_out_swiglu): h column j is gate
-                                 // column (j / 64) 128 + j % 64, its up column 64 further
-          auto coff_b = [&](int it) {
-            const int idx = it * 64 + lane, lr = idx >> 4, ch = idx & 15;
-            return (long)(m0 + wr * 128 + lr) * ldc + 2 * (n0 + wc * 128) + (ch >> 3) * 128 + (ch & 7) * 8;
-          };
-          copy_out_x<-3, false>(C, pre, stg, coff_b, staged, nullptr, 64);
+    const int row0 = m0 + wr * 128, col0 = n0 + wc * 128;  // this wave's piece
+    const int rep = (m0 >> 8) % kConvStatReplicas;
+    switch (F.kind) {
+      case EpiKind::Linear:
+        // the activation and the accumulate are compile-time in the loop body (copy_out_x<.., ACT, ACC>): with them
+        // as run-time values the compiler branched per ELEMENT and serialised every GELU chain (exp -> add -> rcp ->
+        // mul, s_nop between): BERT-base's FFN1 forward took 1013 us against 543 us for the bias-only QKV forward of
+        // 3/4 its FLOPs
+        if (E.act == 2) {
+          if (E.accumulate) copy_out_x<EpiKind::Linear, 2, true>(C, E.pre, nullptr, coff, staged);
+          else copy_out_x<EpiKind::Linear, 2, false>(C, E.pre, nullptr, coff, staged);
+        } else if (E.act == 1) {
+          if (E.accumulate) copy_out_x<EpiKind::Linear, 1, true>(C, E.pre, nullptr, coff, staged);
+          else copy_out_x<EpiKind::Linear, 1, false>(C, E.pre, nullptr, coff, staged);
         } else {
-          float* const cp = cpart + (long)((m0 >> 8) * 2 + wr) * N + n0 + wc * 128;
-          if (act == -2) copy_out_x<-2, false>(C, pre, stg, coff, staged, cp);
-          else copy_out_x<-1, false>(C, pre, stg, coff, staged, cp);
+          if (E.accumulate) copy_out_x<EpiKind::Linear, 0, true>(C, E.pre, nullptr, coff, staged);
+          else copy_out_x<EpiKind::Linear, 0, false>(C, E.pre, nullptr, coff, staged);
         }
-      }
-    } else if (act == 3) {
-      copy_out_swiglu(C, pre, stg, coff, staged, m0 + wr * 128, (n0 + wc * 128) / 2, N);
-    } else if (act == 5) {
-      copy_out_stats(C, cpart, smem, stg, coff, staged, (m0 >> 8) % kConvStatReplicas, N, n0);
-    } else if (act == 6) {
-      copy_out_bnbwd(C, pre, rtab, cpart, smem, stg, coff, staged, (m0 >> 8) % kConvStatReplicas, N, n0,
-                     n0 + wc * 128);
-    } else if (act == 4) {
-      copy_out_rope(C, stg, (long)(m0 + wr * 128) * ldc + n0 + wc * 128, ldc, n0 + wc * 128 < rcols, rpos, rtab,
-                    m0 + wr * 128);
-    } else if (act == 2) {
-      if (accumulate) copy_out_x<2, true>(C, pre, stg, coff, staged); else copy_out_x<2, false>(C, pre, stg, coff, staged);
-    } else if (act == 1) {
-      if (accumulate) copy_out_x<1, true>(C, pre, stg, coff, staged); else copy_out_x<1, false>(C, pre, stg, coff, staged);
-    } else {
-      if (accumulate) copy_out_x<0, true>(C, pre, stg, coff, staged); else copy_out_x<0, false>(C, pre, stg, coff, staged);
+        break;
+      case EpiKind::ActBwd:  // (data-gradient form only) a partial row of column sums per (tile, wave row)
+        if constexpr (!AMN && BMN) {
+          float* const cp = F.colsum_part + (long)((m0 >> 8) * 2 + wr) * N + col0;
+          if (E.act == 2) copy_out_x<EpiKind::ActBwd, 2, false>(C, nullptr, F.act_in, coff, staged, cp);
+          else copy_out_x<EpiKind::ActBwd, 1, false>(C, nullptr, F.act_in, coff, staged, cp);
+        }
+        break;
+      case EpiKind::SwigluBwd:  // (data-gradient form only) no column sums; the up half up_off columns to the right
+        if constexpr (!AMN && BMN) {
+          if (F.blk) {  // the 64-blocked gate|up layout (copy_out_swiglu): h column j is gate column
+                        // (j / 64) 128 + j % 64, its up column 64 further
+            auto coff_b = [&](int it) {
+              const int idx = it * 64 + lane, lr = idx >> 4, ch = idx & 15;
+              return (long)(row0 + lr) * ldc + 2 * col0 + (ch >> 3) * 128 + (ch & 7) * 8;
+            };
+            copy_out_x<EpiKind::SwigluBwd, 0, false>(C, nullptr, F.gu, coff_b, staged, nullptr, 64);  // (= F.blk)
+          } else {
+            copy_out_x<EpiKind::SwigluBwd, 0, false>(C, nullptr, F.gu, coff, staged, nullptr, F.up_off);
+          }
+        }
+        break;
+      case EpiKind::SwigluFwd:
+        copy_out_swiglu(C, F.h, stg, coff, staged, row0, col0 / 2, N);
+        break;
+      case EpiKind::Rope:
+        copy_out_rope(C, stg, (long)row0 * ldc + col0, ldc, col0 < F.rot_cols, F.pos, F.table, row0);
+        break;
+      case EpiKind::BnStats:
+        copy_out_stats(C, F.stats, smem, stg, coff, staged, rep, N, n0);
+        break;
+      case EpiKind::BnBwdSums:
+        copy_out_bnbwd(C, F.bn_x, F.bn_tab, F.bn_sums, smem, stg, coff, staged, rep, N, n0, col0);
+        break;
     }
   }
 }
@@ -1300,29 +1321,70 @@ static bool w4_enabled() {
   const char* e = getenv("K8S_AMD_GEMM_W4");
   return !(e && e[0] == '0');
 }
-static bool w4_ok(bool a_kmajor, bool b_kmajor, bool c_f32, int M, int N, int K, long lda, long ldb, long ldc,
-                  const float* bias, int act, const uint16_t* pre, bool accumulate, int splits, int sk) {
-  if (!w4_enabled()) return false;
-  (void)sk;
-  (void)a_kmajor;  // every operand layout: K-major (read as rows) or MN-major (transposed reads)
-  (void)b_kmajor;
+// Whole tiles of a product the 4-wave kernel can run (enabled, M, N % 256, K % 64); 0: none
+static long w4_tiles(int M, int N, int K) {
+  return w4_enabled() && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 ? (long)(M / 256) * (N / 256) : 0;
+}
+// The whole-tile gate every fused form shares: at least one wave of them
+static bool w4_whole_tiles(int M, int N, int K) { return w4_tiles(M, N, K) >= planner_cus(); }
+static bool w4_ok(bool c_f32, int M, int N, int K, long lda, long ldb, long ldc, const float* bias, int act,
+                  const uint16_t* pre, bool accumulate, int splits) {
   const bool extras = bias || act != 0 || pre || (accumulate && !c_f32);
   if (c_f32 && extras) return false;             // fp32 outputs: plain store / accumulate
   if (reinterpret_cast<uintptr_t>(bias) % 16 != 0) return false;  // the epilogue reads the bias as 16-B vectors
   if (splits > 1 && (!c_f32 || accumulate)) return false;  // split slabs: plain fp32 stores
-  if (M % 256 != 0 || N % 256 != 0 || K % 64 != 0 || (lda | ldb | ldc) % 8 != 0) return false;
-  const long tiles = (long)(M / 256) * (N / 256);
-  return splits > 1 ? tiles * splits >= 3L * planner_cus() / 4 : tiles >= planner_cus();
+  if ((lda | ldb | ldc) % 8 != 0) return false;
+  const long tiles = w4_tiles(M, N, K);
+  return splits > 1 ? tiles > 0 && tiles * splits >= 3L * planner_cus() / 4 : w4_whole_tiles(M, N, K);
 }
 // K range per split of a tall-K split on the 4-wave kernel (whole 64-deep stages; the last split takes the rest)
 static int w4_split_kps(int K, int splits) { return (K / 64 + splits - 1) / splits * 64; }
 
-// Data gradient fused with the backward of the activation that produced the GEMM's input (see copy_out_x, ACT < 0):
+namespace g4 {
+// The one launch of gemm_w4_kernel: the grid -- whole tiles, then gemm256_plan's stream-K tail when a workspace is
+// given, or `splits` > 1 tall-K ranges over gridDim.y -- and the instantiation for the operand layouts (K-major, or
+// MN-major) and `x` (the X extras: a bias, or anything the copy-out does besides storing). Returns the K ranges
+// launched.
+static int launch(const uint16_t* A, long lda, bool a_kmajor, const uint16_t* B, long ldb, bool b_kmajor, bool x,
+                  const g256::Epi& e, const Fused& f, int M, int N, int K, int splits, float* sk_slabs, int* sk_sync,
+                  hipStream_t st) {
+  const int tiles = (M / 256) * (N / 256);
+  g256r::SkArgs sk{tiles, 1, nullptr, nullptr};
+  int blocks = tiles, kps = K, ysplits = 1;
+  if (splits > 1) {
+    kps = w4_split_kps(K, splits);
+    ysplits = (K + kps - 1) / kps;  // every one non-empty
+  } else if (sk_slabs && sk_sync) {
+    const Gemm256Plan plan = gemm256_plan(M, N, K);
+    if (plan.sk > 1) {  // fixed up in-kernel, as in the ring kernel
+      sk = g256r::SkArgs{plan.full, plan.sk, sk_slabs, sk_sync};
+      kps = plan.kps;
+      blocks = plan.full + (tiles - plan.full) * plan.sk;
+    }
+  }
+  auto go = [&](auto amn, auto bmn, auto xx) {
+    hipLaunchKernelGGL((gemm_w4_kernel<decltype(amn)::value, decltype(bmn)::value, decltype(xx)::value>),
+                       dim3(blocks, ysplits), dim3(THREADS), 0, st, A, lda, B, ldb, e, f, M, N, K, kps, sk);
+  };
+  auto pick_x = [&](auto amn, auto bmn) {
+    if (x) go(amn, bmn, std::true_type{});
+    else go(amn, bmn, std::false_type{});
+  };
+  if (a_kmajor && b_kmajor) pick_x(std::false_type{}, std::false_type{});
+  else if (a_kmajor) pick_x(std::false_type{}, std::true_type{});
+  else if (b_kmajor) pick_x(std::true_type{}, std::false_type{});
+  else pick_x(std::true_type{}, std::true_type{});
+  return ysplits;
+}
+// A fused kind's output: plain bf16 C [M][.] of row stride ldc (no bias, alpha 1)
+static g256::Epi bf16_out(uint16_t* c, long ldc) { return g256::Epi{c, ldc, nullptr, nullptr, 0, 0, 0, 1.f, 0}; }
+}  // namespace g4
+
+// ActBwd: the data gradient fused with the backward of the activation that produced the GEMM's input (copy_out_x):
 // C[M][N] = (A . B) * act'(pre), db[N] = column sums of C (fp32, written or added), A K-major [M][K], B [K][N]
-// (the linear's weight). 4-wave kernel shapes only (w4_dact_ok); `part` holds (M / 128) x N floats.
+// (the linear's weight). `part` holds (M / 128) x N floats.
 bool gemm_w4_dact_ok(int M, int N, int K, long lda, long ldb, long ldc) {
-  return w4_enabled() && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && (lda | ldb | ldc) % 8 == 0 &&
-         (long)(M / 256) * (N / 256) >= planner_cus();
+  return w4_whole_tiles(M, N, K) && (lda | ldb | ldc) % 8 == 0;
 }
 long gemm_w4_dact_part_floats(int M, int N) { return (long)(M / 128) * N; }
 void launch_gemm_w4_dact(const uint16_t* A, long lda, const uint16_t* B, long ldb, uint16_t* C, long ldc, int M, int N,
@@ -1330,24 +1392,17 @@ void launch_gemm_w4_dact(const uint16_t* A, long lda, const uint16_t* B, long ld
                          float* sk_slabs, int* sk_sync, hipStream_t st) {
   if (!gemm_w4_dact_ok(M, N, K, lda, ldb, ldc) || (act != 1 && act != 2) || ldc != N)
     throw std::runtime_error("gemm_w4_dact: shape / activation outside the 4-wave kernel's contract");
-  Gemm256Plan plan = gemm256_plan(M, N, K);
-  if (!sk_slabs || !sk_sync) plan.sk = 1;
-  const int tiles = (M / 256) * (N / 256);
-  g256r::SkArgs sk{tiles, 1, nullptr, nullptr};
-  int blocks = tiles, kps = K;
-  if (plan.sk > 1) {
-    sk = g256r::SkArgs{plan.full, plan.sk, sk_slabs, sk_sync};
-    kps = plan.kps;
-    blocks = plan.full + (tiles - plan.full) * plan.sk;
-  }
-  hipLaunchKernelGGL((g4::gemm_w4_kernel<false, true, true>), dim3(blocks), dim3(g4::THREADS), 0, st, A, lda, B, ldb,
-                     (void*)C, ldc, M, N, K, 1.f, kps, sk, 0, 0, nullptr, -act, const_cast<uint16_t*>(pre), 0L, part,
-                     nullptr, nullptr, 0);
+  g256::Epi e = g4::bf16_out(C, ldc);
+  e.act = act;
+  g4::Fused f{g4::EpiKind::ActBwd};
+  f.act_in = pre;
+  f.colsum_part = part;
+  g4::launch(A, lda, true, B, ldb, false, true, e, f, M, N, K, 1, sk_slabs, sk_sync, st);
   launch_colsum_fold(part, M / 128, N, db, db_accumulate, st);
 }
 
-// Llama's down-projection data gradient fused with the SwiGLU backward (copy_out_x ACT = -3): dgu [M][2F] from
-// g [M][K] (K-major) . w [K][F] (MN-major) and gu [M][2F]; the 4-wave kernel's whole-tile shapes (N = F).
+// SwigluBwd: Llama's down-projection data gradient fused with the SwiGLU backward (copy_out_x): dgu [M][2F] (row
+// stride 2F, gate half at column 0) from g [M][K] (K-major) . w [K][F] (MN-major) and gu [M][2F]; N = F.
 bool gemm_w4_swiglu_ok(int M, int F, int K, long lda, long ldb) {
   return gemm_w4_dact_ok(M, F, K, lda, ldb, 2L * F);
 }
@@ -1356,75 +1411,46 @@ void launch_gemm_w4_swiglu_bwd(const uint16_t* A, long lda, const uint16_t* B, l
                                hipStream_t st) {
   if (!gemm_w4_swiglu_ok(M, F, K, lda, ldb) || (blk != 0 && blk != 64))
     throw std::runtime_error("gemm_w4_swiglu_bwd: shape outside the 4-wave kernel's contract");
-  Gemm256Plan plan = gemm256_plan(M, F, K);
-  if (!sk_slabs || !sk_sync) plan.sk = 1;
-  const int tiles = (M / 256) * (F / 256);
-  g256r::SkArgs sk{tiles, 1, nullptr, nullptr};
-  int blocks = tiles, kps = K;
-  if (plan.sk > 1) {
-    sk = g256r::SkArgs{plan.full, plan.sk, sk_slabs, sk_sync};
-    kps = plan.kps;
-    blocks = plan.full + (tiles - plan.full) * plan.sk;
-  }
-  // C = dgu (row stride 2F, gate half at column 0), pre = gu, slab = F: the up half's column offset (blk = 64: the
-  // blocked layout, act -4)
-  hipLaunchKernelGGL((g4::gemm_w4_kernel<false, true, true>), dim3(blocks), dim3(g4::THREADS), 0, st, A, lda, B, ldb,
-                     (void*)dgu, 2L * F, M, F, K, 1.f, kps, sk, 0, 0, nullptr, blk ? -4 : -3,
-                     const_cast<uint16_t*>(gu), (long)F, nullptr, nullptr, nullptr, 0);
+  g4::Fused f{g4::EpiKind::SwigluBwd};
+  f.gu = gu;
+  f.up_off = F;
+  f.blk = blk;
+  g4::launch(A, lda, true, B, ldb, false, true, g4::bf16_out(dgu, 2L * F), f, M, F, K, 1, sk_slabs, sk_sync, st);
 }
 
-// Llama's gate|up projection with the SwiGLU in the epilogue (copy_out_swiglu): gu [M][2F] = A [M][K] . B [2F][K]^T
-// (both K-major; B's rows in the 64-blocked gate|up order) and h [M][F] = silu(gate) up. Whole 256 x 256 tiles.
+// SwigluFwd: Llama's gate|up projection with the SwiGLU in the epilogue (copy_out_swiglu): gu [M][2F] = A [M][K] .
+// B [2F][K]^T (both K-major; B's rows in the 64-blocked gate|up order) and h [M][F] = silu(gate) up.
 bool gemm_w4_swiglu_fwd_ok(int M, int F, int K, long lda, long ldb) {
-  return w4_enabled() && M % 256 == 0 && F % 128 == 0 && K % 64 == 0 && (lda | ldb) % 8 == 0 &&
-         (long)(M / 256) * (2 * F / 256) >= planner_cus();  // (2F % 256: whole tiles, each 2 gate|up block pairs)
+  // (F % 128: 2F in whole tiles, each 2 gate|up block pairs)
+  return F % 128 == 0 && w4_whole_tiles(M, 2 * F, K) && (lda | ldb) % 8 == 0;
 }
 void launch_gemm_w4_swiglu_fwd(const uint16_t* A, long lda, const uint16_t* B, long ldb, uint16_t* gu, uint16_t* h,
                                int M, int F, int K, float* sk_slabs, int* sk_sync, hipStream_t st) {
   if (!gemm_w4_swiglu_fwd_ok(M, F, K, lda, ldb))
     throw std::runtime_error("gemm_w4_swiglu_fwd: shape outside the 4-wave kernel's contract");
-  const int N = 2 * F;
-  Gemm256Plan plan = gemm256_plan(M, N, K);
-  if (!sk_slabs || !sk_sync) plan.sk = 1;
-  const int tiles = (M / 256) * (N / 256);
-  g256r::SkArgs sk{tiles, 1, nullptr, nullptr};
-  int blocks = tiles, kps = K;
-  if (plan.sk > 1) {
-    sk = g256r::SkArgs{plan.full, plan.sk, sk_slabs, sk_sync};
-    kps = plan.kps;
-    blocks = plan.full + (tiles - plan.full) * plan.sk;
-  }
-  hipLaunchKernelGGL((g4::gemm_w4_kernel<false, false, true>), dim3(blocks), dim3(g4::THREADS), 0, st, A, lda, B, ldb,
-                     (void*)gu, (long)N, M, N, K, 1.f, kps, sk, 0, 0, nullptr, 3, h, 0L, nullptr, nullptr, nullptr, 0);
+  g4::Fused f{g4::EpiKind::SwigluFwd};
+  f.h = h;
+  g4::launch(A, lda, true, B, ldb, true, true, g4::bf16_out(gu, 2L * F), f, M, 2 * F, K, 1, sk_slabs, sk_sync, st);
 }
 
-// Llama's QKV projection with the rotary embedding of the q / k heads (columns < rot_cols, head dim 128) in the
+// Rope: Llama's QKV projection with the rotary embedding of the q / k heads (columns < rot_cols, head dim 128) in the
 // copy-out (copy_out_rope): y [M][N] = A [M][K] . B [N][K]^T, both K-major; pos [M] int32, table [maxpos][64][2].
 bool gemm_w4_rope_ok(int M, int N, int K, long lda, long ldb, int rot_cols) {
-  return w4_enabled() && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && (lda | ldb) % 8 == 0 && rot_cols % 128 == 0 &&
-         rot_cols <= N && (long)(M / 256) * (N / 256) >= planner_cus();
+  return w4_whole_tiles(M, N, K) && (lda | ldb) % 8 == 0 && rot_cols % 128 == 0 && rot_cols <= N;
 }
 void launch_gemm_w4_rope(const uint16_t* A, long lda, const uint16_t* B, long ldb, uint16_t* y, int M, int N, int K,
                          const int* pos, const float* table, int rot_cols, float* sk_slabs, int* sk_sync,
                          hipStream_t st) {
   if (!gemm_w4_rope_ok(M, N, K, lda, ldb, rot_cols))
     throw std::runtime_error("gemm_w4_rope: shape outside the 4-wave kernel's contract");
-  Gemm256Plan plan = gemm256_plan(M, N, K);
-  if (!sk_slabs || !sk_sync) plan.sk = 1;
-  const int tiles = (M / 256) * (N / 256);
-  g256r::SkArgs sk{tiles, 1, nullptr, nullptr};
-  int blocks = tiles, kps = K;
-  if (plan.sk > 1) {
-    sk = g256r::SkArgs{plan.full, plan.sk, sk_slabs, sk_sync};
-    kps = plan.kps;
-    blocks = plan.full + (tiles - plan.full) * plan.sk;
-  }
-  hipLaunchKernelGGL((g4::gemm_w4_kernel<false, false, true>), dim3(blocks), dim3(g4::THREADS), 0, st, A, lda, B, ldb,
-                     (void*)y, (long)N, M, N, K, 1.f, kps, sk, 0, 0, nullptr, 4, nullptr, 0L, nullptr, pos, table,
-                     rot_cols);
+  g4::Fused f{g4::EpiKind::Rope};
+  f.pos = pos;
+  f.table = table;
+  f.rot_cols = rot_cols;
+  g4::launch(A, lda, true, B, ldb, true, true, g4::bf16_out(y, N), f, M, N, K, 1, sk_slabs, sk_sync, st);
 }
 
-// ResNet's deep-reduction 1x1 convolution forwards with the BatchNorm statistics epilogue (copy_out_stats):
+// BnStats: ResNet's deep-reduction 1x1 convolution forwards with the BatchNorm statistics epilogue (copy_out_stats):
 // y [M][N] = x [M][K] . w [N][K]^T, stats [kConvStatReplicas][2][N] (zeroed by the caller). $K8S_AMD_W4_STATS=0 keeps
 // them on the 128 x 128 tile kernel (A/B; read per call); K8S_AMD_W4_STATS_MINK (default 512) is the smallest
 // reduction taken.
@@ -1433,48 +1459,29 @@ bool gemm_w4_stats_ok(int M, int N, int K) {
   if (e && e[0] == '0') return false;
   const char* mk = getenv("K8S_AMD_W4_STATS_MINK");
   const int mink = mk ? atoi(mk) : 512;
-  return w4_enabled() && K >= mink && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 &&
-         (long)(M / 256) * (N / 256) >= planner_cus();
+  return K >= mink && w4_whole_tiles(M, N, K);
 }
 void launch_gemm_w4_stats(const uint16_t* A, long lda, const uint16_t* B, long ldb, uint16_t* y, int M, int N, int K,
                           float* stats, float* sk_slabs, int* sk_sync, hipStream_t st) {
-  Gemm256Plan plan = gemm256_plan(M, N, K);
-  if (!sk_slabs || !sk_sync) plan.sk = 1;
-  const int tiles = (M / 256) * (N / 256);
-  g256r::SkArgs sk{tiles, 1, nullptr, nullptr};
-  int blocks = tiles, kps = K;
-  if (plan.sk > 1) {
-    sk = g256r::SkArgs{plan.full, plan.sk, sk_slabs, sk_sync};
-    kps = plan.kps;
-    blocks = plan.full + (tiles - plan.full) * plan.sk;
-  }
-  hipLaunchKernelGGL((g4::gemm_w4_kernel<false, false, true>), dim3(blocks), dim3(g4::THREADS), 0, st, A, lda, B, ldb,
-                     (void*)y, (long)N, M, N, K, 1.f, kps, sk, 0, 0, nullptr, 5, nullptr, 0L, stats, nullptr, nullptr,
-                     0);
+  if (!gemm_w4_stats_ok(M, N, K) || (lda | ldb) % 8 != 0)
+    throw std::runtime_error("gemm_w4_stats: shape outside the 4-wave kernel's contract");
+  g4::Fused f{g4::EpiKind::BnStats};
+  f.stats = stats;
+  g4::launch(A, lda, true, B, ldb, true, true, g4::bf16_out(y, N), f, M, N, K, 1, sk_slabs, sk_sync, st);
 }
 
-// A data gradient dx [M][N] = dy [M][K] . w [K][N] (w stored MN-major, the 1x1 convolution's [Kout][Cin]) with the
-// BatchNorm-backward sums of dx in the epilogue (copy_out_bnbwd); whole 256 x 256 tiles, stream-K tail with a workspace.
-bool gemm_w4_dgrad_bnstats_ok(int M, int N, int K) {
-  return w4_enabled() && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && (long)(M / 256) * (N / 256) >= planner_cus();
-}
+// BnBwdSums: a data gradient dx [M][N] = dy [M][K] . w [K][N] (w stored MN-major, the 1x1 convolution's [Kout][Cin])
+// with the BatchNorm-backward sums of dx in the epilogue (copy_out_bnbwd); stream-K tail with a workspace.
+bool gemm_w4_dgrad_bnstats_ok(int M, int N, int K) { return w4_whole_tiles(M, N, K); }
 void launch_gemm_w4_dgrad_bnstats(const uint16_t* A, const uint16_t* B, uint16_t* y, int M, int N, int K,
                                   const uint16_t* x, const float* tab, float* sums, float* sk_slabs, int* sk_sync,
                                   hipStream_t st) {
   if (!gemm_w4_dgrad_bnstats_ok(M, N, K)) throw std::runtime_error("w4 dgrad BatchNorm sums: outside the contract");
-  Gemm256Plan plan = gemm256_plan(M, N, K);
-  if (!sk_slabs || !sk_sync) plan.sk = 1;
-  const int tiles = (M / 256) * (N / 256);
-  g256r::SkArgs sk{tiles, 1, nullptr, nullptr};
-  int blocks = tiles, kps = K;
-  if (plan.sk > 1) {
-    sk = g256r::SkArgs{plan.full, plan.sk, sk_slabs, sk_sync};
-    kps = plan.kps;
-    blocks = plan.full + (tiles - plan.full) * plan.sk;
-  }
-  hipLaunchKernelGGL((g4::gemm_w4_kernel<false, true, true>), dim3(blocks), dim3(g4::THREADS), 0, st, A, (long)K, B,
-                     (long)N, (void*)y, (long)N, M, N, K, 1.f, kps, sk, 0, 0, nullptr, 6, const_cast<uint16_t*>(x), 0L,
-                     sums, nullptr, tab, 0);
+  g4::Fused f{g4::EpiKind::BnBwdSums};
+  f.bn_x = x;
+  f.bn_tab = tab;
+  f.bn_sums = sums;
+  g4::launch(A, K, true, B, N, false, true, g4::bf16_out(y, N), f, M, N, K, 1, sk_slabs, sk_sync, st);
 }
 
 // Stream-K tail plan for a grid of 256 x 256 tiles on P = planner_cus() CUs (one block per CU; 256 on MI355X): with
@@ -1521,9 +1528,7 @@ bool gemm256_eligible(int M, int N, int K, bool a_kmajor, bool b_kmajor) {
     // K8S_AMD_GEMM256_MINK (default 768: off) for the A/B
     const char* e = getenv("K8S_AMD_GEMM256_MINK");
     const int mink = e ? atoi(e) : 768;
-    if (K < mink || !w4_enabled() || M % 256 != 0 || N % 256 != 0 ||
-        (long)(M / 256) * (N / 256) < planner_cus())
-      return false;
+    if (K < mink || !w4_whole_tiles(M, N, K)) return false;
   }
   if (!a_kmajor && M % 8 != 0) return false;
   if (!b_kmajor && N % 8 != 0) return false;
@@ -1545,7 +1550,7 @@ bool gemm256_eligible(int M, int N, int K, bool a_kmajor, bool b_kmajor) {
 int gemm256_choose_splits(int M, int N, int K) {
   const long tiles = (long)((M + 255) / 256) * ((N + 255) / 256);
   const long fill = 3L * planner_cus() / 4;
-  if (w4_enabled() && M % 256 == 0 && N % 256 == 0 && K % 64 == 0) {
+  if (w4_tiles(M, N, K) > 0) {
     // the 4-wave kernel takes uneven splits: as many as fit one wave of (tile, split) blocks at one block per CU,
     // each >= 512 deep (8 stages) -- BERT-base's weight gradients at 131k tokens: 9 tiles x 28, 27 x 9, 36 x 7
     long s = planner_cus() / tiles;
@@ -1577,45 +1582,17 @@ void launch_gemm256(const uint16_t* A, long lda, bool a_kmajor, const uint16_t* 
     throw std::runtime_error("gemm256 split-K: plain fp32 output and a workspace");
   g256::Epi e{splits > 1 ? (void*)ws : C, ldc, bias, pre, c_f32 ? 1 : 0, act, (splits == 1 && accumulate) ? 1 : 0,
               alpha, splits > 1 ? (long)M * N : 0};
-  Gemm256Plan plan = gemm256_plan(M, N, K);
-  if (splits > 1 || !sk_slabs || !sk_sync) plan.sk = 1;  // tall-K split, or no stream-K workspace given
   using namespace g256r;
-  if (w4_ok(a_kmajor, b_kmajor, c_f32, M, N, K, lda, ldb, ldc, bias, act, pre, splits > 1 ? false : accumulate,
-            splits, plan.sk)) {
-    const int tiles = (M / 256) * (N / 256);
-    g256r::SkArgs sk{tiles, 1, nullptr, nullptr};
-    int blocks = tiles, kps = K, ysplits = 1;
-    if (splits > 1) {  // tall-K split: slabs of ws, then splitk_reduce (which also applies `accumulate`)
-      kps = w4_split_kps(K, splits);
-      ysplits = (K + kps - 1) / kps;
-    } else if (plan.sk > 1) {  // the stream-K tail (gemm256_plan), fixed up in-kernel as in the ring kernel
-      sk = g256r::SkArgs{plan.full, plan.sk, sk_slabs, sk_sync};
-      kps = plan.kps;
-      blocks = plan.full + (tiles - plan.full) * plan.sk;
-    }
+  if (w4_ok(c_f32, M, N, K, lda, ldb, ldc, bias, act, pre, splits > 1 ? false : accumulate, splits)) {
+    // (a tall-K split: slabs of ws, then splitk_reduce, which also applies `accumulate`)
     const bool x = bias || act != 0 || pre || (accumulate && !c_f32);
-    void* const cv = splits > 1 ? (void*)ws : C;
-    const int acc = splits > 1 ? 0 : (accumulate ? 1 : 0);
-#define K8S_W4L(AM, BM, XX)                                                                                         \
-  hipLaunchKernelGGL((g4::gemm_w4_kernel<AM, BM, XX>), dim3(blocks, ysplits), dim3(g4::THREADS), 0, st, A, lda, B, \
-                     ldb, cv, ldc, M, N, K, alpha, kps, sk, c_f32 ? 1 : 0, acc, bias, act, pre, (long)M * N, nullptr,   \
-                     nullptr, nullptr, 0)
-#define K8S_W4X(AM, BM)       \
-  do {                        \
-    if (x)                    \
-      K8S_W4L(AM, BM, true);  \
-    else                      \
-      K8S_W4L(AM, BM, false); \
-  } while (0)
-    if (a_kmajor && b_kmajor) K8S_W4X(false, false);
-    else if (a_kmajor) K8S_W4X(false, true);
-    else if (b_kmajor) K8S_W4X(true, false);
-    else K8S_W4X(true, true);
-#undef K8S_W4X
-#undef K8S_W4L
+    const int ysplits = g4::launch(A, lda, a_kmajor, B, ldb, b_kmajor, x, e, g4::Fused{g4::EpiKind::Linear}, M, N, K,
+                                   splits, sk_slabs, sk_sync, st);
     if (splits > 1) splitk_reduce(ws, ysplits, (long)M * N, reinterpret_cast<float*>(C), accumulate, st);
     return;
   }
+  Gemm256Plan plan = gemm256_plan(M, N, K);
+  if (splits > 1 || !sk_slabs || !sk_sync) plan.sk = 1;  // tall-K split, or no stream-K workspace given
   while (splits > 1 && K % (64 * splits) != 0) --splits;  // the ring kernel takes even splits only (ws holds more)
   e.slab = splits > 1 ? (long)M * N : 0;
   if (splits == 1) {

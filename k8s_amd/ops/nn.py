@@ -73,7 +73,7 @@ class ActLink:
     """Joins a linear with an activation (the producer, ``linear(x, W1, b1, act="gelu", act_link=l)``) to the linear
     that reads its output (the consumer, ``linear(y, W2, b2, act_in=l)``): the consumer's data gradient is formed as
     (dy . W2) * act'(pre), with the producer's bias gradient as its column sums, in the 4-wave GEMM's epilogue
-    (gemm256.hip copy_out_x ACT < 0; ``gemm.dact_ok`` shapes) -- the producer's backward then skips its
+    (gemm256.hip copy_out_x, ActBwd; ``gemm.dact_ok`` shapes) -- the producer's backward then skips its
     activation-backward pass (read dy and pre, write g) and its bias column sums. BERT's FFN1 -> FFN2."""
     __slots__ = ("saved", "act", "pb", "done")
 
@@ -84,7 +84,7 @@ class ActLink:
 class SwiGLULink:
     """Joins ``swiglu(gu, link=l)`` to the linear that reads its output (``linear(y, W, swiglu_in=l)``, Llama's down
     projection): that linear's data gradient takes the SwiGLU backward in its epilogue and produces the gradient of gu
-    directly (gemm256.hip copy_out_x ACT = -3, ``gemm.swiglu_ok`` shapes), so neither the [T, F] gradient of the
+    directly (gemm256.hip copy_out_x, SwigluBwd; ``gemm.swiglu_ok`` shapes), so neither the [T, F] gradient of the
     SwiGLU output nor the separate SwiGLU-backward pass over gu exists. ``blk``: gu's column layout (0 = gate | up
     halves, 64 = blocks of 64 gate then 64 up columns, ``linear_swiglu``)."""
     __slots__ = ("saved", "dgu", "blk")

@@ -303,8 +303,8 @@ def _gelu_grad(x):
 @pytest.mark.parametrize("act", [1, 2])
 def test_gemm_dact_matches_fp32(cuda, act):
     """Data gradient fused with the input activation's backward and the producer's bias gradient (gemm256.hip
-    copy_out_x ACT < 0, `gemm_dact`): dx = (g . W) * act'(pre), db = column sums of dx, against fp32 PyTorch; db
-    written, then accumulated onto an existing value."""
+    copy_out_x, the ActBwd kind, `gemm_dact`): dx = (g . W) * act'(pre), db = column sums of dx, against fp32 PyTorch;
+    db written, then accumulated onto an existing value."""
     torch.manual_seed(10)
     M, Nout, Kin = 16384, 768, 3072  # BERT-base FFN2's data gradient: 64 x 12 = 768 tiles
     g = torch.randn(M, Nout, device=cuda).bfloat16()
@@ -407,7 +407,7 @@ def test_gemm_swiglu_fwd_matches_two_pass():
 
 
 def test_gemm_swiglu_bwd_blocked_matches_two_pass():
-    """The SwiGLU backward in the down projection's data gradient on the 64-blocked gate|up layout (act -4) against
+    """The SwiGLU backward in the down projection's data gradient on the 64-blocked gate|up layout (blk = 64) against
     the two-pass form (blocked SwiGLU-backward kernel), bit-identical, and an fp32 reference."""
     torch.manual_seed(6)
     C = _C()
@@ -448,3 +448,130 @@ def test_gemm_rope_matches_two_pass():
     ref = x.float() @ w.float().t()
     ref = torch.cat([K._rope_ref(ref[:, :rot], pos, table), ref[:, rot:]], -1)
     assert _rel(y, ref) < 2e-2
+
+
+def _fused_swiglu_bwd(C, blk):
+    M, F, K = 512, 768, 1024
+    g = (torch.randn(M, K, device="cuda") * 0.5).bfloat16()
+    w = (torch.randn(K, F, device="cuda") * 0.05).bfloat16()
+    gu = torch.randn(M, 2 * F, device="cuda").bfloat16()
+    assert C.gemm_swiglu_bwd_ok(M, F, K)
+
+    def check(dgu):
+        dy = C.gemm(g, True, w, False, None, False, None, 0, None, False, 1.0, 1)
+        assert torch.equal(dgu, C.swiglu_bwd(gu, dy, blk))
+
+    return lambda: (C.gemm_swiglu_bwd(g, w, gu, blk),), check, 1
+
+
+def _fused_swiglu_fwd(C):
+    M, F, K = 512, 384, 1024
+    x = (torch.randn(M, K, device="cuda") * 0.5).bfloat16()
+    w = (torch.randn(2 * F, K, device="cuda") * 0.05).bfloat16()
+    assert C.gemm_swiglu_fwd_ok(M, F, K)
+
+    def check(gu, h):
+        gu2 = C.gemm(x, True, w, True, None, False, None, 0, None, False, 1.0, 1)
+        assert torch.equal(gu, gu2)
+        assert torch.equal(h, C.swiglu_fwd(gu2, 64))
+
+    return lambda: tuple(C.gemm_swiglu_fwd(x, w)), check, 2
+
+
+def _fused_rope(C):
+    from k8s_amd.ops import nn as K_
+
+    M, N, K, rot = 512, 6 * 128, 1024, 512
+    x = (torch.randn(M, K, device="cuda") * 0.5).bfloat16()
+    w = (torch.randn(N, K, device="cuda") * 0.05).bfloat16()
+    pos = torch.randint(0, 4096, (M,), device="cuda", dtype=torch.int32)
+    table = K_.rope_table(4096, 128, 500000.0, "cuda")
+    assert C.gemm_rope_ok(M, N, K, rot)
+
+    def check(y):
+        y2 = C.gemm(x, True, w, True, None, False, None, 0, None, False, 1.0, 1)
+        C.rope_(y2[:, :rot], pos, table, False)
+        assert torch.equal(y, y2)
+
+    return lambda: (C.gemm_rope(x, w, pos, table, rot),), check, 1
+
+
+def _fused_dgrad_bnstats(C):
+    M, N, K = 512, 768, 1024
+    gy = torch.randn(M, K, device="cuda").bfloat16()
+    w = (torch.randn(K, N, device="cuda") * 0.05).bfloat16()
+    x = (torch.randn(M, N, device="cuda") * 1.5 + 0.2).bfloat16()
+    mean = x.float().mean(0)
+    invstd = torch.rsqrt(x.float().var(0, unbiased=False) + 1e-5)
+    gamma, beta = torch.rand(N, device="cuda") + 0.5, torch.randn(N, device="cuda") * 0.2
+    assert C.gemm_dgrad_bnstats_ok(M, N, K)
+
+    def run():
+        sums = torch.zeros(C.conv_stat_replicas, 2, N, device="cuda")
+        return C.gemm_dgrad_bnstats(gy, w, x, gamma, beta, mean, invstd, sums), sums
+
+    def check(dx, sums):
+        assert torch.equal(dx, C.gemm(gy, True, w, False, None, False, None, 0, None, False, 1.0, 1))
+        scale = gamma * invstd
+        z = (x.float() * scale + torch.addcmul(beta, -mean, scale)).bfloat16().float()
+        g = torch.where(z > 0, dx.float(), torch.zeros_like(dx.float()))
+        tot = sums.sum(0)
+        print("dgrad_bnstats sums:", _rel(tot[0], g.sum(0)), _rel(tot[1], (g * (x.float() - mean)).sum(0)))
+        assert _rel(tot[0], g.sum(0)) < 1e-3
+        assert _rel(tot[1], (g * (x.float() - mean)).sum(0)) < 1e-3
+
+    return run, check, 1  # the sums are atomic adds: only dx must repeat bit for bit
+
+
+def _fused_dact(C, act):
+    M, N, K = 512, 768, 1024
+    g = torch.randn(M, K, device="cuda").bfloat16()
+    w = (torch.randn(K, N, device="cuda") * 0.05).bfloat16()
+    pre = torch.randn(M, N, device="cuda").bfloat16()
+    if act == 1:
+        pre = torch.relu(pre)  # the ReLU path reads the ReLU output
+    assert C.gemm_dact_ok(M, N, K)
+
+    def run():
+        db = torch.empty(N, device="cuda")
+        return C.gemm_dact(g, w, pre, act, db, False), db
+
+    def check(dx, db):
+        deriv = (pre.float() > 0).float() if act == 1 else _gelu_grad(pre.float())
+        print("dact:", _rel(dx, (g.float() @ w.float()) * deriv), _rel(db, dx.float().sum(0)))
+        assert _rel(dx, (g.float() @ w.float()) * deriv) < 1e-2
+        assert _rel(db, dx.float().sum(0)) < 1e-4  # the sums of the stored bf16 values
+
+    return run, check, 1
+
+
+@pytest.mark.parametrize("case", ["swiglu_bwd", "swiglu_bwd_blocked", "swiglu_fwd", "rope", "dgrad_bnstats",
+                                  "dact_relu", "dact_gelu"])
+def test_gemm_w4_fused_epilogues_on_stream_k_tail(cuda, case):
+    """Every fused epilogue of the 4-wave kernel that is launched with a stream-K workspace, on a grid with a tail:
+    with the planners sized for 4 CUs, M = 512, N = 768, K = 1024 is 6 tiles -- 4 whole, then 2 tiles split 2 ways
+    (512 deep each), 8 blocks -- and gemm256_eligible (cost 79 954 against 98 304), so the plain `gemm` each case
+    compares with takes the same kernel and the same plan, and the two-pass forms are bit-identical as in the
+    whole-wave tests above. Each launch runs three times with equal results: the fix-up sums in a fixed order. (The
+    BatchNorm-statistics epilogue is launched without a workspace and never takes a tail.)"""
+    C = _C()
+    torch.manual_seed(21)
+    C.set_planner_cus(4)
+    try:
+        run, check, nbit = {  # (launch, its checks, how many of its outputs repeat bit for bit)
+            "swiglu_bwd": lambda: _fused_swiglu_bwd(C, 0),
+            "swiglu_bwd_blocked": lambda: _fused_swiglu_bwd(C, 64),
+            "swiglu_fwd": lambda: _fused_swiglu_fwd(C),
+            "rope": lambda: _fused_rope(C),
+            "dgrad_bnstats": lambda: _fused_dgrad_bnstats(C),
+            "dact_relu": lambda: _fused_dact(C, 1),
+            "dact_gelu": lambda: _fused_dact(C, 2),
+        }[case]()
+        outs = [run() for _ in range(3)]
+        for o in outs[1:]:
+            for a, b in list(zip(o, outs[0]))[:nbit]:
+                assert torch.equal(a, b)
+        check(*outs[0])
+        torch.cuda.synchronize()
+    finally:
+        C.set_planner_cus(0)

@@ -652,11 +652,12 @@ def test_conv3x3_dgrad_bnstats_epilogue(cuda, N, H, C, K):
 
 
 @pytest.mark.parametrize("M,K,N", [(9000, 256, 64), (4100, 512, 128), (1000, 384, 72),
-                                   # the 4-wave kernel's copy_out_bnbwd: whole waves, and a stream-K tail
+                                   # the 4-wave kernel's copy_out_bnbwd: whole waves, and a last wave too full for a
+                                   # stream-K tail (1176 tiles: 152 of 256 left; the tail: test_gemm256_gpu.py)
                                    (65536, 1024, 256), (150528, 2048, 512)])
 def test_gemm_dgrad_bnstats_epilogue(cuda, M, K, N):
-    """The 1x1 data gradient on its regular kernel (the tile kernel's BST epilogue, or the 4-wave kernel's ACT 6
-    copy-out) with the BatchNorm-backward sums of the relu(BN(x)) that fed the convolution: dx bitwise equal to the
+    """The 1x1 data gradient on its regular kernel (the tile kernel's BST epilogue, or the 4-wave kernel's copy_out_bnbwd)
+    with the BatchNorm-backward sums of the relu(BN(x)) that fed the convolution: dx bitwise equal to the
     plain dgrad, the sums against fp32 sums over the stored dx with the forward's ReLU decision."""
     C_ = _C()
     assert C_.gemm_dgrad_bnstats_ok(M, N, K)
