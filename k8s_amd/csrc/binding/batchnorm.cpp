@@ -302,6 +302,37 @@ std::vector<Tensor> bn_bwd_dual_impl(const Tensor& dy, const Tensor& mask, const
                      bf(dx2), f32(dgamma2), f32(dbeta2), f32(work2), f32(params2), M, C, cur_stream());
   return {dx, dx2};
 }
+// The first half of bn_bwd_dual / bn_bwd_dual_from_sums: dgamma / dbeta of both BatchNorms and the two params tables
+// fp32 [sc | B | D | shift], (params, params2). sums / sums2 (optional, together): the producer's reduction; without
+// them the dual reduce sweep runs here. bn_bwd_apply(dy, x, mask, params) and bn_bwd_apply(dy, x2, mask, params2) then
+// give the dx and dx2 bn_bwd_dual writes, bit for bit -- or a consumer applies a table on load (bwd1x1_fused).
+std::vector<Tensor> bn_bwd_dual_params(Tensor dy, Tensor mask, Tensor x, Tensor mean, Tensor invstd, Tensor gamma,
+                                       Tensor beta, Tensor dgamma, Tensor dbeta, OptTensor sums, Tensor x2,
+                                       Tensor mean2, Tensor invstd2, Tensor gamma2, Tensor beta2, Tensor dgamma2,
+                                       Tensor dbeta2, OptTensor sums2) {
+  const bool pre = sums && sums->defined();
+  TORCH_CHECK(pre == (sums2 && sums2->defined()), "sums and sums2 come together");
+  const int C = bn_channels(x, "x", !pre);
+  const long M = x.numel() / C;
+  check_same_shape(dy, x, "dy");
+  check_same_shape(x2, x, "x2");
+  check_bwd_vectors(mean, invstd, gamma, beta, dgamma, dbeta, C);
+  check_bwd_vectors(mean2, invstd2, gamma2, beta2, dgamma2, dbeta2, C);
+  const uint8_t* mk = check_bit_mask(mask, x.numel(), "mask");
+  const int nrep = pre ? check_stat_sums(*sums, C, "sums", false) : 0;
+  TORCH_CHECK(!pre || check_stat_sums(*sums2, C, "sums2", false) == nrep, "sums / sums2: the same replica count");
+  auto params = torch::empty({4 * C}, gamma.options()), params2 = torch::empty({4 * C}, gamma.options());
+  Tensor work, work2;
+  if (!pre) {
+    work = torch::empty({k8s_amd::bn_workspace_floats(M, C)}, gamma.options());
+    work2 = torch::empty({k8s_amd::bn_workspace_floats(M, C)}, gamma.options());
+  }
+  launch_bn_bwd_dual_params(cbf(dy), mk, cbf(x), pre ? f32(*sums) : nullptr, nrep, f32(mean), f32(invstd), f32(gamma),
+                            f32(beta), f32(dgamma), f32(dbeta), pre ? nullptr : f32(work), f32(params), cbf(x2),
+                            pre ? f32(*sums2) : nullptr, f32(mean2), f32(invstd2), f32(gamma2), f32(beta2),
+                            f32(dgamma2), f32(dbeta2), pre ? nullptr : f32(work2), f32(params2), M, C, cur_stream());
+  return {params, params2};
+}
 std::vector<Tensor> bn_bwd_dual(Tensor dy, Tensor mask, Tensor x, Tensor mean, Tensor invstd, Tensor gamma,
                                 Tensor beta, Tensor dgamma, Tensor dbeta, Tensor x2, Tensor mean2, Tensor invstd2,
                                 Tensor gamma2, Tensor beta2, Tensor dgamma2, Tensor dbeta2) {
@@ -336,6 +367,10 @@ void bind_batchnorm(pybind11::module_& m) {
   m.def("bn_bwd_apply", &bn_bwd_apply, "dy"_a, "x"_a, "mask"_a, "params"_a,
         "second half of a masked BatchNorm backward: dx from bn_bwd_params' table");
   m.def("bn_bwd_dual_from_sums", &bn_bwd_dual_from_sums, "bn_bwd_dual from a producer's reduction sums");
+  m.def("bn_bwd_dual_params", &bn_bwd_dual_params, "dy"_a, "mask"_a, "x"_a, "mean"_a, "invstd"_a, "gamma"_a, "beta"_a,
+        "dgamma"_a, "dbeta"_a, "sums"_a, "x2"_a, "mean2"_a, "invstd2"_a, "gamma2"_a, "beta2"_a, "dgamma2"_a,
+        "dbeta2"_a, "sums2"_a,
+        "first half of bn_bwd_dual(_from_sums): both dgamma / dbeta and (params, params2), each [sc | B | D | shift]");
   m.def("bn_relu_maxpool", &bn_relu_maxpool, "x"_a, "sums"_a, "gamma"_a, "beta"_a, "run_mean"_a, "run_var"_a,
         "momentum"_a, "eps"_a, "want_link"_a = false);
   m.def("pool_bn_bwd_from_sums", &pool_bn_bwd_from_sums);

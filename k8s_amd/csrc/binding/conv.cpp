@@ -119,8 +119,15 @@ Tensor conv3x3_dgrad_bnstats(Tensor gy, Tensor wt, Tensor x, Tensor gamma, Tenso
 // x3, mask, params (optional, together): gy is the incoming dy of the residual BatchNorm that produced the convolution's
 // output, whose backward the kernel applies as it loads -- gy's tiles become bf16(fma(sc, mask ? dy : 0, fma(B, x3, D)))
 // with x3 bf16 [M, K], mask the packed ReLU bits uint8 [M, K / 8] and params fp32 [sc | B | D] (3K or more).
-Tensor bwd1x1_fused(Tensor gy, Tensor x, Tensor w, Tensor xform, Tensor gamma, Tensor beta, Tensor mean, Tensor invstd,
-                    Tensor dw, Tensor sums, bool accumulate, OptTensor x3, OptTensor mask, OptTensor params) {
+// addend, winner_x, winner_bits, winner_mean (optional, together, (C, K) = (64, 256), and then without xform / gamma /
+// beta / mean / invstd): the final form, for a convolution reading a stored x whose data gradient is the second into
+// it. dw = gy^T . x with x as stored; the result bf16(bf16(gy . w) + addend) (the tile kernel's accumulating epilogue's
+// rounding) is written over addend [M, C] and addend itself is returned; sums take the pool kind's g = bit ? stored result : 0, sum g and sum g (winner_x -
+// winner_mean), winner_x bf16 [M, C] and winner_bits uint8 [M * C / 8] from the pooled forward (bn_relu_maxpool).
+Tensor bwd1x1_fused(Tensor gy, Tensor x, Tensor w, OptTensor xform, OptTensor gamma, OptTensor beta, OptTensor mean,
+                    OptTensor invstd, Tensor dw, Tensor sums, bool accumulate, OptTensor x3, OptTensor mask,
+                    OptTensor params, OptTensor addend, OptTensor winner_x, OptTensor winner_bits,
+                    OptTensor winner_mean) {
   check_bf16_dense(gy, 2, "gy"); check_bf16_dense(x, 2, "x"); check_bf16_dense(w, 2, "w");
   const long M = gy.size(0), K = gy.size(1), C = x.size(1);
   TORCH_CHECK(x.size(0) == M && w.size(0) == K && w.size(1) == C, "shapes: gy [M, K], x [M, C], w [K, C]");
@@ -128,8 +135,35 @@ Tensor bwd1x1_fused(Tensor gy, Tensor x, Tensor w, Tensor xform, Tensor gamma, T
               "bwd1x1_fused: (C, K) = (64, 256) or (128, 512), 1 <= M < 2^31");
   check_cuda(dw, "dw"); check_dtype(dw, at::kFloat, "dw"); check_aligned(dw, "dw");
   TORCH_CHECK(dw.numel() == K * C, "dw must have K * C fp32 elements");
-  check_channel_f32(xform, 2 * C, "xform (BatchNorm scale | shift)");
-  const k8s_amd::BnBwdSums bb = bn_bwd_sums(x, mean, sums, {}, gamma, beta, invstd, {}, {}, {});
+  const bool fin = addend || winner_x || winner_bits || winner_mean;
+  k8s_amd::BnBwdSums bb;
+  k8s_amd::Bwd1x1Final fn;
+  if (fin) {
+    TORCH_CHECK(addend && winner_x && winner_bits && winner_mean,
+                "bwd1x1_fused: addend, winner_x, winner_bits and winner_mean come together");
+    TORCH_CHECK(!xform && !gamma && !beta && !mean && !invstd,
+                "bwd1x1_fused: the final form takes x as stored -- no xform, gamma, beta, mean or invstd");
+    TORCH_CHECK(k8s_amd::bwd1x1_final_ok(M, (int)C, (int)K), "bwd1x1_fused: the final form is (C, K) = (64, 256) only");
+    check_bf16_dense(*addend, 2, "addend"); check_bf16_dense(*winner_x, 2, "winner_x");
+    TORCH_CHECK(addend->size(0) == M && addend->size(1) == C, "addend: the shape of x, [M, C]");
+    TORCH_CHECK(winner_x->size(0) == M && winner_x->size(1) == C, "winner_x: the shape of x, [M, C]");
+    fn.winner_bits = check_bit_mask(*winner_bits, M * C, "winner_bits");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(fn.winner_bits) & 3) == 0, "winner_bits must be 4-byte aligned");
+    check_channel_f32(*winner_mean, C, "winner_mean");
+    check_stat_sums(sums, C, "bn sums", true);
+    TORCH_CHECK(addend->device() == gy.device() && winner_x->device() == gy.device() &&
+                    winner_bits->device() == gy.device() && winner_mean->device() == gy.device() &&
+                    sums.device() == gy.device(),
+                "addend, winner_x, winner_bits, winner_mean and sums: on gy's device");
+    fn.addend = cbf(*addend);
+    fn.winner_x = cbf(*winner_x);
+    fn.winner_mean = f32(*winner_mean);
+    bb.sums = f32(sums);
+  } else {
+    TORCH_CHECK(xform && gamma && beta && mean && invstd, "bwd1x1_fused: xform, gamma, beta, mean and invstd");
+    check_channel_f32(*xform, 2 * C, "xform (BatchNorm scale | shift)");
+    bb = bn_bwd_sums(x, *mean, sums, {}, gamma, beta, invstd, {}, {}, {});
+  }
   k8s_amd::Bwd1x1Bn3 bn3;
   const bool onload = x3 || mask || params;
   if (onload) {
@@ -145,9 +179,15 @@ Tensor bwd1x1_fused(Tensor gy, Tensor x, Tensor w, Tensor xform, Tensor gamma, T
     bn3.x3 = cbf(*x3);
     bn3.params = f32(*params);
   }
-  Tensor dz = torch::empty({M, C}, gy.options());
-  launch_bwd1x1_fused(cbf(gy), cbf(x), cbf(w), f32(xform), bb.gamma, bb.beta, bb.mean, bb.invstd, bf(dz), f32(dw),
-                      bb.sums, M, (int)C, (int)K, accumulate, cur_stream(), onload ? &bn3 : nullptr);
+  Tensor dz = fin ? *addend : torch::empty({M, C}, gy.options());
+  Tensor part;  // the final form's per-workgroup dW slabs
+  if (fin) {
+    part = torch::empty({k8s_amd::bwd1x1_final_workspace(M, (int)C, (int)K)}, dw.options());
+    fn.dw_partials = f32(part);
+  }
+  launch_bwd1x1_fused(cbf(gy), cbf(x), cbf(w), fin ? nullptr : f32(*xform), bb.gamma, bb.beta, bb.mean, bb.invstd,
+                      bf(dz), f32(dw), bb.sums, M, (int)C, (int)K, accumulate, cur_stream(), onload ? &bn3 : nullptr,
+                      fin ? &fn : nullptr);
   return dz;
 }
 
@@ -238,10 +278,15 @@ void bind_conv(pybind11::module_& m) {
         "xform"_a = py::none());
   m.def("bwd1x1_fused", &bwd1x1_fused, "gy"_a, "x"_a, "w"_a, "xform"_a, "gamma"_a, "beta"_a, "mean"_a, "invstd"_a,
         "dw"_a, "sums"_a, "accumulate"_a, "x3"_a = py::none(), "mask"_a = py::none(), "params"_a = py::none(),
+        "addend"_a = py::none(), "winner_x"_a = py::none(), "winner_bits"_a = py::none(),
+        "winner_mean"_a = py::none(),
         "1x1 data gradient, normalize-on-load weight gradient and BatchNorm-backward sums in one pass (bwd1x1_fused.hip)");
   m.def("bwd1x1_fused_ok", [](int64_t M, int64_t C, int64_t K) {
     return C <= 1024 && K <= 4096 && k8s_amd::bwd1x1_fused_ok(M, (int)C, (int)K);
   }, "M"_a, "C"_a, "K"_a, "whether bwd1x1_fused takes this shape");
+  m.def("bwd1x1_final_ok", [](int64_t M, int64_t C, int64_t K) {
+    return C <= 1024 && K <= 4096 && k8s_amd::bwd1x1_final_ok(M, (int)C, (int)K);
+  }, "M"_a, "C"_a, "K"_a, "whether bwd1x1_fused's final form (addend, winner_*) takes this shape");
   m.def("wgrad_stream_eligible",&k8s_amd::wgrad_stream_eligible, "tall-K weight-gradient kernel takes this shape");
   m.def("conv_dgrad_wtrans", &conv_dgrad_wtrans);
   m.def("conv_dgrad_wsub", &conv_dgrad_wsub);

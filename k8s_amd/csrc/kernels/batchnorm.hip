@@ -998,30 +998,24 @@ void launch_bn_bwd_relu_from_sums(const uint16_t* dy, const uint16_t* x, const f
   launch_bn_bwd_apply(dy, x, nullptr, params, true, dx, nullptr, M, C, st);
 }
 
-void launch_bn_bwd_dual_from_sums(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* sums,
-                                  int nrep, const float* mean, const float* invstd, const float* gamma,
-                                  const float* beta, uint16_t* dx, float* dgamma, float* dbeta, float* params,
-                                  const uint16_t* x2, const float* sums2, const float* mean2, const float* invstd2,
-                                  const float* gamma2, const float* beta2, uint16_t* dx2, float* dgamma2,
-                                  float* dbeta2, float* params2, long M, int C, hipStream_t st) {
-  hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums, nrep, C, dgamma,
-                     dbeta, 1.f / (float)M, mean, invstd, gamma, beta, params);
-  hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums2, nrep, C, dgamma2,
-                     dbeta2, 1.f / (float)M, mean2, invstd2, gamma2, beta2, params2);
-  const long nvec = M * C / 8;
-  if (nvec >= (1L << 31)) throw std::runtime_error("BatchNorm tensor too large (>= 2^31 vectors)");
-  hipLaunchKernelGGL(bn_bwd_apply_dual_kernel, dim3(cdiv(nvec, BN_THREADS)), dim3(BN_THREADS), 0, st, dy, mask, x,
-                     params, dx, x2, params2, dx2, (int)nvec, C, make_fastdiv(C / 8),
-                     stream_order_mode() ? (stream_dir(0) ? 1 : 2) : 0);
-}
-
-// Backward of launch_bn_fwd_from_sums_dual: both BatchNorms' (dgamma, dbeta, dx) from one masked dy in one reduce
-// sweep and one apply pass (work / work2: bn_workspace_floats each; params / params2: fp32 [4][C] each).
-void launch_bn_bwd_dual(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* mean,
-                        const float* invstd, const float* gamma, const float* beta, uint16_t* dx, float* dgamma,
-                        float* dbeta, float* work, float* params, const uint16_t* x2, const float* mean2,
-                        const float* invstd2, const float* gamma2, const float* beta2, uint16_t* dx2, float* dgamma2,
-                        float* dbeta2, float* work2, float* params2, long M, int C, hipStream_t st) {
+// The first half of both BatchNorm backwards of launch_bn_fwd_from_sums_dual: dgamma / dbeta of both and the two
+// params tables [sc | B | D | shift] that the dual apply pass -- or, per half, launch_bn_bwd_apply_pass or a consumer
+// that applies the table on load (bwd1x1_fused.hip) -- reads. sums / sums2: the reduction done by dy's producer (sums:
+// sum g, sum g (x - mean); sums2 slot 1: sum g (x2 - mean2)); both null: one reduce sweep over dy, x and x2 here
+// (work / work2: bn_workspace_floats each).
+void launch_bn_bwd_dual_params(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* sums, int nrep,
+                               const float* mean, const float* invstd, const float* gamma, const float* beta,
+                               float* dgamma, float* dbeta, float* work, float* params, const uint16_t* x2,
+                               const float* sums2, const float* mean2, const float* invstd2, const float* gamma2,
+                               const float* beta2, float* dgamma2, float* dbeta2, float* work2, float* params2, long M,
+                               int C, hipStream_t st) {
+  if (sums) {
+    hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums, nrep, C, dgamma,
+                       dbeta, 1.f / (float)M, mean, invstd, gamma, beta, params);
+    hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums2, nrep, C, dgamma2,
+                       dbeta2, 1.f / (float)M, mean2, invstd2, gamma2, beta2, params2);
+    return;
+  }
   BnGeom g = bn_geom(C, M);
   const int nb = bn_reduce_blocks(M, g);
   const int rdir = stream_dir(1);
@@ -1031,11 +1025,40 @@ void launch_bn_bwd_dual(const uint16_t* dy, const uint8_t* mask, const uint16_t*
                      1.f / (float)M, mean, invstd, gamma, beta, params);
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, FIN_CH)), dim3(256), 0, st, work2, nb, C, dgamma2, dbeta2,
                      1.f / (float)M, mean2, invstd2, gamma2, beta2, params2);
+}
+
+// The second half: both gradients in one pass over dy, the mask, x and x2.
+static void launch_bn_bwd_apply_dual(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* params,
+                                     uint16_t* dx, const uint16_t* x2, const float* params2, uint16_t* dx2, long M,
+                                     int C, hipStream_t st) {
   const long nvec = M * C / 8;
   if (nvec >= (1L << 31)) throw std::runtime_error("BatchNorm tensor too large (>= 2^31 vectors)");
   hipLaunchKernelGGL(bn_bwd_apply_dual_kernel, dim3(cdiv(nvec, BN_THREADS)), dim3(BN_THREADS), 0, st, dy, mask, x,
                      params, dx, x2, params2, dx2, (int)nvec, C, make_fastdiv(C / 8),
                      stream_order_mode() ? (stream_dir(0) ? 1 : 2) : 0);
+}
+
+void launch_bn_bwd_dual_from_sums(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* sums,
+                                  int nrep, const float* mean, const float* invstd, const float* gamma,
+                                  const float* beta, uint16_t* dx, float* dgamma, float* dbeta, float* params,
+                                  const uint16_t* x2, const float* sums2, const float* mean2, const float* invstd2,
+                                  const float* gamma2, const float* beta2, uint16_t* dx2, float* dgamma2,
+                                  float* dbeta2, float* params2, long M, int C, hipStream_t st) {
+  launch_bn_bwd_dual_params(dy, mask, x, sums, nrep, mean, invstd, gamma, beta, dgamma, dbeta, nullptr, params, x2,
+                            sums2, mean2, invstd2, gamma2, beta2, dgamma2, dbeta2, nullptr, params2, M, C, st);
+  launch_bn_bwd_apply_dual(dy, mask, x, params, dx, x2, params2, dx2, M, C, st);
+}
+
+// Backward of launch_bn_fwd_from_sums_dual: both BatchNorms' (dgamma, dbeta, dx) from one masked dy in one reduce
+// sweep and one apply pass (work / work2: bn_workspace_floats each; params / params2: fp32 [4][C] each).
+void launch_bn_bwd_dual(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* mean,
+                        const float* invstd, const float* gamma, const float* beta, uint16_t* dx, float* dgamma,
+                        float* dbeta, float* work, float* params, const uint16_t* x2, const float* mean2,
+                        const float* invstd2, const float* gamma2, const float* beta2, uint16_t* dx2, float* dgamma2,
+                        float* dbeta2, float* work2, float* params2, long M, int C, hipStream_t st) {
+  launch_bn_bwd_dual_params(dy, mask, x, nullptr, 0, mean, invstd, gamma, beta, dgamma, dbeta, work, params, x2,
+                            nullptr, mean2, invstd2, gamma2, beta2, dgamma2, dbeta2, work2, params2, M, C, st);
+  launch_bn_bwd_apply_dual(dy, mask, x, params, dx, x2, params2, dx2, M, C, st);
 }
 
 // ---- stem BatchNorm + ReLU + 3x3 / s2 / p1 max pool (see bn_relu_maxpool_fwd_kernel)

@@ -56,6 +56,44 @@
 //    transform writes zeros for them: the zero gy rows the rest of the kernel relies on.
 //  * At K = 512 both workgroups of a pair transform the whole tile (duplicated VALU / LDS work); measured per layer
 //    (benchmarks/bn3_onload.py) the form still beats apply + plain there, by less than at K = 256.
+//
+// FINAL (launch_bwd1x1_fused with a Bwd1x1Final; (C, K) = (64, 256) only): the x side of a convolution that reads a
+// stored tensor and whose data gradient is the second into it -- ResNet's stage-1 downsample convolution on the stem
+// pool's output, after conv1's. Per row m and channel c
+//   dW uses x as stored (no xform; the x image is not rewritten);
+//   out[m][c] = bf16(float(bf16(product)) + float(addend[m][c])), written over the addend: the two roundings of the
+//   tile kernel's accumulating epilogue (gemm.hip: "the staged value is already bf16"), whose launch this one
+//   replaces, so the step computes what it computed (a single rounding of the fp32 sum was built first: it differed
+//   from that kernel in 26 % of the elements by one ulp, enough to move the stem's dbeta -- a sum that cancels -- by
+//   1.4e-2 in a batch-2 block, tests/test_dual_onload_gpu.py's bound being 1e-2);
+//   g = bit ? stored out : 0, sums[0] += g, sums[1] += g (xw - mean): the pool kind (winner x [M][64], its packed ReLU
+//   bits [M][8]) of gemm_dgrad_bnstats_mask without add_src.
+// Both the plain and the ONLOAD form exist (gy a materialised gradient, or dy transformed on load exactly as above).
+//  * Space: the addend, the winner x and the bits are 16.5 KB per 64-row tile more, which the ONLOAD <256, 64, 2, 1>
+//    ring (156 of 160 KB) has no room for. The final forms therefore walk 32-row tiles: a stage is [dy | x3 | mask | x
+//    | addend | winner x | bits] = 16 + 16 + 1 + 4 + 4 + 4 + 1 KB = 46 KB in a ring of three (plain: 16 + 4 + 4 + 4 + 1
+//    = 29 KB, ring of four), every operand by LDS-DMA, so "nothing loads through VGPRs inside the loop" still holds
+//    and there is no second kind of load to count. Both forms use the RS = 32 dz path, so their fp32 sums have one
+//    order and out agrees bit for bit between them.
+//  * Loads per stage and wave: LG (plain, 2) or 2 LG (ONLOAD, 4) for every wave; +1 for the ONLOAD mask wave (0); +3
+//    for the element-pass waves 0..3 (x, addend, winner x: same lane -> unit map, same swz128 image); +1 for wave 7's
+//    bits, 4 B per lane (global_load_lds_dword: row lane / 2, half lane & 1 -- 64 lanes are exactly the tile's 256 B,
+//    and an 8-B row can be clamped or zero-filled per lane, which a 16-B unit spanning two rows could not be).
+//  * vmcnt: the ring logic is the plain form's, now also for ONLOAD. When stage s is waited for, the younger stages in
+//    flight are s + 1 (.. s + NSLOT - 2), each at least LPS = LG or 2 LG loads of this wave, so vmcnt(younger * LPS)
+//    retires all of stage s: a wave with extra loads in a younger stage (up to 4 + 1 + 3 of them on wave 0) only waits
+//    for the first of those too, which were issued a whole stage earlier. The out stores are older than every load
+//    counted and change nothing. The loads are in order and of one kind, as before.
+//  * The element pass reads the staged dz unit, the addend unit, the winner x unit and one bits byte, adds, rounds,
+//    stores out, and adds the sums over the stored values; x is left alone.
+//  * Rows past M: zero rows of gy give dz = 0, but out = addend would not be zero where the ONLOAD form's clamped
+//    loads repeat the last valid row, so both forms store nothing and take no sums for them (bits read as 0).
+//  * dW leaves as one fp32 [K][64] slab per workgroup (plain stores, 16 MB chip-wide -- what the other forms send
+//    through atomics) and splitk_reduce sums the slabs in workgroup order: the layer's weight gradient was
+//    wgrad_stream's, which is repeatable bit for bit, and tests/test_resnet_gpu.py compares whole-model gradients of
+//    two runs for equality. No memset of dW.
+//  * In place: a tile's addend rows are in LDS (its stage has been waited for) before the same workgroup stores its
+//    out rows, and no other workgroup touches them.
 #include <algorithm>
 #include <stdexcept>
 
@@ -101,6 +139,11 @@ struct Args {
   float* dw;
   float* sums;
   int M, C, ntiles, npairs;
+  // FINAL: dz is the addend's own storage (out = bf16(bf16 product + addend), in place), xw / bits the pooled
+  // forward's winner x [M][64] and its packed ReLU bits [M][8], mean the winner's BatchNorm mean
+  const uint16_t *addend, *xw;
+  const uint8_t* bits;
+  float* dwpart;  // FINAL: fp32 [workgroup][K][C] partials of dW, summed in workgroup order after the kernel
 };
 
 __device__ __forceinline__ void lds_barrier() {
@@ -109,15 +152,24 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// 4 B per lane into LDS at (wave-uniform base + lane * 4): the FINAL form's bits tile, 8-B rows
+__device__ __forceinline__ void glds4(const void* src, void* lds_base) {
+  __builtin_amdgcn_global_load_lds(src, (lds_void*)lds_base, 4, 0, 0);
+}
+
 //   <256, 64, 3, 1>: 3 x 40 KB ring + 8 KB staging;  <512, 32, 4, 2>: 4 x 36 KB ring + 4 KB staging
 //   ONLOAD <256, 64, 2, 1>: 2 x 74 KB ring + 8 KB;   <512, 32, 2, 2>: 2 x 70 KB ring + 4 KB + 7.25 KB of tables
-template <int K, int RS, int NSLOT, int HALVES, bool ONLOAD>
+//   FINAL  <256, 32, 4, 1>: 4 x 29 KB ring + 4 KB;   ONLOAD FINAL <256, 32, 3, 1>: 3 x 46 KB ring + 4 KB
+template <int K, int RS, int NSLOT, int HALVES, bool ONLOAD, bool FINAL = false>
 __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
   constexpr int RB = K * 2, UG = K / 8;
   constexpr int IMG_G = RS * RB, IMG_X = RS * 128;
   constexpr int IMG_M = ONLOAD ? RS * UG : 0;  // packed mask rows: UG bytes each
   constexpr int OFF_X = IMG_G + (ONLOAD ? IMG_G + IMG_M : 0);  // [gy | x3 | mask | x]
-  constexpr int STAGE = OFF_X + IMG_X, RING = NSLOT * STAGE;
+  // FINAL: [.. | x | addend | winner x | bits]; the bits tile is RS * 8 B, one wave's 4-B loads, in a 1-KB slot
+  constexpr int OFF_A = OFF_X + IMG_X, OFF_W = OFF_A + IMG_X, OFF_B = OFF_W + IMG_X;
+  constexpr int STAGE = FINAL ? OFF_B + 1024 : OFF_X + IMG_X, RING = NSLOT * STAGE;
+  static_assert(!FINAL || (K == 256 && RS == 32 && HALVES == 1), "the final form: (C, K) = (64, 256), 32-row tiles");
   constexpr int LG = RS * UG / THREADS;  // gy LDS-DMA per thread per stage
   constexpr int LPS = ONLOAD ? 2 * LG : LG;  // ... and the LDS-DMA every wave issues per stage
   // dx3's per-channel constants (sc | B | D): a thread's logical unit is the same for all its LG units when the rows
@@ -173,10 +225,14 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
   float xsc[8], xsh[8], gsc[8], gsh[8], mu[8], ps[8], pq[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    xsc[j] = a.xform[ecol + j];
-    xsh[j] = a.xform[C + ecol + j];
     mu[j] = a.mean[ecol + j];
-    bn_affine_regs(a.gamma[ecol + j], a.beta[ecol + j], mu[j], a.invstd[ecol + j], gsc[j], gsh[j]);
+    if constexpr (!FINAL) {
+      xsc[j] = a.xform[ecol + j];
+      xsh[j] = a.xform[C + ecol + j];
+      bn_affine_regs(a.gamma[ecol + j], a.beta[ecol + j], mu[j], a.invstd[ecol + j], gsc[j], gsh[j]);
+    } else {
+      xsc[j] = xsh[j] = gsc[j] = gsh[j] = 0.f;  // (unused: x is the dW operand as stored, the ReLU decision a bit)
+    }
     ps[j] = pq[j] = 0.f;
   }
   if constexpr (PLDS) {
@@ -212,7 +268,10 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
   // every ordinary load is consumed here, before the first LDS-DMA is issued
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) asm volatile("" : "+v"(wf[ks]));
-  if constexpr (!PLDS) {
+  if constexpr (FINAL) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(mu[j]));
+  } else if constexpr (!PLDS) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(xsc[j]), "+v"(xsh[j]), "+v"(gsc[j]), "+v"(gsh[j]), "+v"(mu[j]));
   } else {
@@ -239,7 +298,18 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
         const unsigned q = (wid * 64 + lane) * 16;
         glds16(a.mask + m0 * UG + min(q / UG, last) * UG + q % UG, st + 2 * IMG_G + wid * 1024);
       }
-      if (wid < XT / 64) glds16(a.x + m0 * C + min((unsigned)erow, last) * C + ecol, st + OFF_X + wid * 1024);
+      if (wid < XT / 64) {
+        const unsigned eoff = min((unsigned)erow, last) * C + ecol;
+        glds16(a.x + m0 * C + eoff, st + OFF_X + wid * 1024);
+        if constexpr (FINAL) {
+          glds16(a.addend + m0 * C + eoff, st + OFF_A + wid * 1024);
+          glds16(a.xw + m0 * C + eoff, st + OFF_W + wid * 1024);
+        }
+      }
+      if constexpr (FINAL) {  // lane = 4 B of row lane / 2
+        if (wid == THREADS / 64 - 1)
+          glds4(a.bits + m0 * 8 + min((unsigned)lane >> 1, last) * 8 + (lane & 1) * 4, st + OFF_B);
+      }
       return;
     }
 #pragma unroll
@@ -254,6 +324,16 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
       const long m = m0 + erow;
       const void* src = m < M ? (const void*)(a.x + m * C + ecol) : (const void*)g_zero16;
       glds16(src, st + OFF_X + wid * 1024);
+      if constexpr (FINAL) {
+        glds16(m < M ? (const void*)(a.addend + m * C + ecol) : (const void*)g_zero16, st + OFF_A + wid * 1024);
+        glds16(m < M ? (const void*)(a.xw + m * C + ecol) : (const void*)g_zero16, st + OFF_W + wid * 1024);
+      }
+    }
+    if constexpr (FINAL) {  // lane = 4 B of row lane / 2
+      if (wid == THREADS / 64 - 1) {
+        const long m = m0 + (lane >> 1);
+        glds4(m < M ? (const void*)(a.bits + m * 8 + (lane & 1) * 4) : (const void*)g_zero16, st + OFF_B);
+      }
     }
   };
 
@@ -360,7 +440,30 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
     lds_barrier();  // the staged dz tile is complete
 
     // ---- element pass: store dz, add the sums, z over x in place
-    if (wid < XT / 64) {
+    if constexpr (FINAL) {
+      // ---- element pass, final form: out = bf16(staged bf16 product + addend) -- the rounding of the tile kernel's
+      // accumulating epilogue (gemm.hip), whose launch this one replaces -- stored over the addend, and the sums over
+      // g = bit ? stored out : 0 against the winner's x (rows past M: no store, no sums -- their out is an addend the
+      // clamped loads repeated); x stays as stored
+      if (wid < XT / 64) {
+        const bf16x8_t dzv = *reinterpret_cast<const bf16x8_t*>(stg + tid * 16);
+        const bf16x8_t adv = *reinterpret_cast<const bf16x8_t*>(G + OFF_A + tid * 16);
+        const bf16x8_t xv = *reinterpret_cast<const bf16x8_t*>(G + OFF_W + tid * 16);
+        const long m = (long)(pair + s * a.npairs) * RS + erow;
+        const uint32_t bits = m < M ? (uint32_t) * reinterpret_cast<const uint8_t*>(G + OFF_B + erow * 8 + eu) : 0u;
+        float o[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = bf2f((uint16_t)dzv[j]) + bf2f((uint16_t)adv[j]);
+        const bf16x8_t ov = pack_bf16x8(o);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float g = (bits >> j) & 1u ? bf2f((uint16_t)ov[j]) : 0.f;
+          ps[j] += g;
+          pq[j] = __builtin_fmaf(g, bf2f((uint16_t)xv[j]) - mu[j], pq[j]);
+        }
+        if (m < M) *reinterpret_cast<bf16x8_t*>(a.dz + m * C + ecol) = ov;
+      }
+    } else if (wid < XT / 64) {
       const bf16x8_t dzv = *reinterpret_cast<const bf16x8_t*>(stg + tid * 16);
       const bf16x8_t xv = *reinterpret_cast<const bf16x8_t*>(X + tid * 16);
       if constexpr (PLDS) {
@@ -413,6 +516,18 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
   }
 
   // ---- dW partials: lane holds dW[k = wid * KW + i * 16 + (lane & 15)][c0 + j * 16 + 4 (lane >> 4) + r]
+  if constexpr (FINAL) {
+    // this workgroup's slab, plain 16-B stores: the slabs are summed in workgroup order by splitk_reduce, so dW does
+    // not depend on the order the workgroups finish in (the layer's weight gradient was a deterministic kernel's)
+    float* slab = a.dwpart + (long)bid * K * CT;
+#pragma unroll
+    for (int i = 0; i < KTW; ++i) {
+      const int k = wid * KW + i * 16 + (lane & 15);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        *reinterpret_cast<f32x4_t*>(slab + (long)k * CT + j * 16 + 4 * (lane >> 4)) = dwa[i][j];
+    }
+  } else
 #pragma unroll
   for (int i = 0; i < KTW; ++i) {
     const int k = wid * KW + i * 16 + (lane & 15);
@@ -450,22 +565,48 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
 bool bwd1x1_fused_ok(long M, int C, int K) {
   return M >= 1 && M < (1L << 31) && ((C == 64 && K == 256) || (C == 128 && K == 512));
 }
+// ... and of the final form (Bwd1x1Final): (C, K) = (64, 256) only
+bool bwd1x1_final_ok(long M, int C, int K) { return bwd1x1_fused_ok(M, C, K) && C == 64; }
+// fp32 elements of Bwd1x1Final::dw_partials: one [K][C] slab per workgroup that has a tile
+long bwd1x1_final_workspace(long M, int C, int K) {
+  return std::min<long>(std::max(1, planner_cus()), (M + 31) / 32) * K * C;
+}
 
 // bn3: null, or the residual BatchNorm's backward applied on load -- gy is then its incoming dy, and the kernel forms
 // dx3 = fma(sc, mask ? dy : 0, fma(B, x3, D)) tile by tile instead of reading it (x3 [M][K] bf16, mask [M][K / 8]
 // packed bits, params fp32 [sc | B | D], 3K or more).
+// fin: null, or the final form -- x is the dW operand as stored (xform / gamma / beta / invstd null, mean unused), dz is
+// fin->addend's storage, and the sums are the pool kind's over the stored sum.
 void launch_bwd1x1_fused(const uint16_t* gy, const uint16_t* x, const uint16_t* w, const float* xform,
                          const float* gamma, const float* beta, const float* mean, const float* invstd, uint16_t* dz,
                          float* dw, float* sums, long M, int C, int K, bool accumulate, hipStream_t st,
-                         const Bwd1x1Bn3* bn3) {
+                         const Bwd1x1Bn3* bn3, const Bwd1x1Final* fin) {
   using namespace b1f;
   if (!bwd1x1_fused_ok(M, C, K)) throw std::runtime_error("bwd1x1_fused: (C, K) = (64, 256) or (128, 512), M < 2^31");
   if (bn3 && !(bn3->x3 && bn3->mask && bn3->params)) throw std::runtime_error("bwd1x1_fused: x3, mask and params");
-  if (!accumulate) (void)hipMemsetAsync(dw, 0, (size_t)K * C * sizeof(float), st);
-  Args a{gy, x, w, nullptr, nullptr, nullptr, xform, gamma, beta, mean, invstd, dz, dw, sums, (int)M, C, 0, 0};
+  if (fin) {
+    if (!bwd1x1_final_ok(M, C, K)) throw std::runtime_error("bwd1x1_fused, final form: (C, K) = (64, 256)");
+    if (!(fin->addend && fin->winner_x && fin->winner_bits && fin->winner_mean) || dz != fin->addend)
+      throw std::runtime_error("bwd1x1_fused, final form: addend (the output), winner_x, winner_bits, winner_mean");
+    if (xform || gamma || beta || mean || invstd)
+      throw std::runtime_error("bwd1x1_fused, final form: no xform operands");
+  }
+  if (fin && !fin->dw_partials) throw std::runtime_error("bwd1x1_fused, final form: dw_partials");
+  if (!accumulate && !fin) (void)hipMemsetAsync(dw, 0, (size_t)K * C * sizeof(float), st);
+  Args a{gy, x, w, nullptr, nullptr, nullptr, xform, gamma, beta, mean, invstd, dz, dw, sums, (int)M, C, 0, 0,
+         nullptr, nullptr, nullptr, nullptr};
   if (bn3) a.x3 = bn3->x3, a.mask = bn3->mask, a.params = bn3->params;
   const int cus = std::max(1, planner_cus());
-  if (C == 64) {
+  if (fin) {
+    a.mean = fin->winner_mean, a.addend = fin->addend, a.xw = fin->winner_x, a.bits = fin->winner_bits;
+    a.dwpart = fin->dw_partials;
+    a.ntiles = (int)((M + 31) / 32);
+    a.npairs = cus;
+    if (bn3) hipLaunchKernelGGL((bwd1x1_fused_kernel<256, 32, 3, 1, true, true>), dim3(cus), dim3(THREADS), 0, st, a);
+    else hipLaunchKernelGGL((bwd1x1_fused_kernel<256, 32, 4, 1, false, true>), dim3(cus), dim3(THREADS), 0, st, a);
+    // workgroups 0 .. min(cus, ntiles) - 1 each wrote a slab: dw (+)= their sum, in that order
+    splitk_reduce(fin->dw_partials, std::min(cus, a.ntiles), (long)K * C, dw, accumulate, st);
+  } else if (C == 64) {
     a.ntiles = (int)((M + 63) / 64);
     a.npairs = cus;
     if (bn3) hipLaunchKernelGGL((bwd1x1_fused_kernel<256, 64, 2, 1, true>), dim3(cus), dim3(THREADS), 0, st, a);

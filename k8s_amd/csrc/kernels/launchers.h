@@ -83,6 +83,16 @@ void launch_bn_bwd_dual(const uint16_t* dy, const uint8_t* mask, const uint16_t*
                         float* dbeta, float* work, float* params, const uint16_t* x2, const float* mean2,
                         const float* invstd2, const float* gamma2, const float* beta2, uint16_t* dx2, float* dgamma2,
                         float* dbeta2, float* work2, float* params2, long M, int C, hipStream_t st);
+// launch_bn_bwd_dual / launch_bn_bwd_dual_from_sums without their apply pass: dgamma / dbeta of both BatchNorms and the
+// two params tables [sc | B | D | shift] (sums and sums2 null: the dual reduce sweep here, work / work2 =
+// bn_workspace_floats each). Each half's table is then applied by launch_bn_bwd_apply_pass(dy, x or x2, mask, ...) or
+// by a consumer on load.
+void launch_bn_bwd_dual_params(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* sums, int nrep,
+                               const float* mean, const float* invstd, const float* gamma, const float* beta,
+                               float* dgamma, float* dbeta, float* work, float* params, const uint16_t* x2,
+                               const float* sums2, const float* mean2, const float* invstd2, const float* gamma2,
+                               const float* beta2, float* dgamma2, float* dbeta2, float* work2, float* params2, long M,
+                               int C, hipStream_t st);
 void launch_bn_finalize_sums(const float* gamma, const float* beta, const float* sums, int nrep, float* save_mean,
                              float* save_invstd, float* run_mean, float* run_var, float* params, long M, int C,
                              float eps, float momentum, hipStream_t st);
@@ -267,11 +277,26 @@ struct Bwd1x1Bn3 {
   const uint8_t* mask = nullptr;
   const float* params = nullptr;
 };
+// fin (optional, (C, K) = (64, 256) only): the final form, for a convolution whose input is a stored tensor and whose
+// data gradient is the second into it (ResNet's stage-1 downsample convolution on the stem pool's output). x is the dW
+// operand as stored (xform, gamma, beta, mean, invstd null); out = bf16(bf16(gy . w) + addend), the rounding of the tile
+// kernel's accumulating epilogue, is written over addend (dz == addend); the sums are the pool kind's over the stored sum: g = bit ? out : 0, sums[r][0] += g,
+// sums[r][1] += g (winner_x - winner_mean), winner_x [M][64] bf16 and winner_bits [M][8] the pooled forward's window
+// winners and their packed ReLU bits. With bn3 the gy tile is formed on load as above.
+struct Bwd1x1Final {
+  const uint16_t* addend = nullptr;
+  const uint16_t* winner_x = nullptr;
+  const uint8_t* winner_bits = nullptr;
+  const float* winner_mean = nullptr;
+  float* dw_partials = nullptr;  // bwd1x1_final_workspace floats: dW's per-workgroup slabs, summed in order into dw
+};
 bool bwd1x1_fused_ok(long M, int C, int K);
+bool bwd1x1_final_ok(long M, int C, int K);
+long bwd1x1_final_workspace(long M, int C, int K);
 void launch_bwd1x1_fused(const uint16_t* gy, const uint16_t* x, const uint16_t* w, const float* xform,
                          const float* gamma, const float* beta, const float* mean, const float* invstd, uint16_t* dz,
                          float* dw, float* sums, long M, int C, int K, bool accumulate, hipStream_t st,
-                         const Bwd1x1Bn3* bn3 = nullptr);
+                         const Bwd1x1Bn3* bn3 = nullptr, const Bwd1x1Final* fin = nullptr);
 void launch_conv_dgrad_wtrans(const uint16_t* w, uint16_t* w2, int K, int R, int S, int C, hipStream_t st);
 // per-output-parity sub-weights of a stride-s dgrad (up to 16 parities x 16 taps), packed at off[p]
 struct DgradTaps {

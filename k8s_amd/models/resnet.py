@@ -46,9 +46,10 @@ class Conv(nn.Module):
         self.w = store.new(name + ".weight", (cout, k, k, cin), init_kaiming_normal(cin * k * k))
         self.stride, self.pad = stride, k // 2
 
-    def forward(self, x, grad_link=None):
+    def forward(self, x, grad_link=None, bn3_link=None):
         # BN statistics are accumulated in the conv epilogue (returned alongside y)
-        return K.conv2d_nhwc(x, self.w, self.stride, self.pad, with_stats=True, grad_link=grad_link)
+        return K.conv2d_nhwc(x, self.w, self.stride, self.pad, with_stats=True, grad_link=grad_link,
+                             bn3_link=bn3_link)
 
 
 class Bottleneck(nn.Module):
@@ -82,10 +83,14 @@ class Bottleneck(nn.Module):
         # downsample block: bn3's ReLU mask is applied by the downsample BN's backward as it reads dy. The branch is
         # built FIRST so autograd (highest sequence number first) runs its backward LAST: the stride-2 1x1 dgrad
         # then accumulates onto conv1's dx (shared GradLink) instead of zero-filling the 3 parities it never writes
-        mlink = dn = None
+        # ... and where its two BatchNorms run as one (bn_act_dual) and both convolutions can take their half of that
+        # backward's apply pass on load (the stage-1 entry block: conv3 and the stride-1 downsample convolution on
+        # the fused 1x1 backward), two Bn3Links join them, so neither dx3 nor the downsample's gradient is written
+        mlink = dn = b3r = None
         if self.down is not None:
             mlink = K.MaskLink()
-            dn = self.down(x, grad_link=dlink)
+            b3r = K.Bn3Link() if self.training else None
+            dn = self.down(x, grad_link=dlink, bn3_link=b3r)
             # bn3 + downsample BN in one apply pass where the fused kernel applies (ops.nn.bn_act_dual)
             fuse = K.BN_DUAL and isinstance(dn, tuple) and dn[1] is not None and self.training and dn[0].is_cuda
             if not fuse:
@@ -96,14 +101,15 @@ class Bottleneck(nn.Module):
         t = K.bn_relu_conv(t, self.bn1, self.conv2)
         # identity block: bn3's backward apply pass is taken on load by conv3's fused backward where that kernel
         # runs (ops.nn.Bn3Link: stages 1 and 2), so dx3 is never written
-        b3 = K.Bn3Link() if (self.down is None and self.training) else None
+        b3 = K.Bn3Link() if self.training else None
         t = K.bn_relu_conv(t, self.bn2, self.conv3, bn3_link=b3)
         if dn is not None and fuse:
-            y = K.bn_act_dual(t, self.bn3, dn, self.down_bn)
+            y = K.bn_act_dual(t, self.bn3, dn, self.down_bn, bn3_link=b3, bn3_link_r=b3r)
             if y is not None:
                 return y
             idn = self.down_bn(dn, relu=False, dy_link=mlink)
-        return self.bn3(t, residual=idn, relu=True, res_link=link or mlink, sub2=sub2, bn3_link=b3)
+        return self.bn3(t, residual=idn, relu=True, res_link=link or mlink, sub2=sub2,
+                        bn3_link=b3 if self.down is None else None)
 
 
 class ResNet(nn.Module):

@@ -42,8 +42,23 @@ STATS = {"hip_fwd": 0, "aten_fwd": 0, "hip_wgrad": 0, "aten_wgrad": 0, "hip_dgra
          # a residual BatchNorm that holds a nn.Bn3Link: fused 1x1 backwards that applied its backward on load, and
          # apply passes (bn_bwd_apply) run for it instead, by its own backward or by the linked convolution's when it
          # could not take the deferred form
-         "bn3_onload": 0, "bn3_apply": 0}
-ROUTES = collections.Counter()  # data-gradient route name -> times executed
+         "bn3_onload": 0, "bn3_apply": 0,
+         # a downsample block's two BatchNorms (nn.bn_act_dual) holding two nn.Bn3Links: backwards that deferred both
+         # apply halves, apply passes run for a deferred half after all, and launches of the fused 1x1 backward's
+         # final form (the downsample convolution's; with or without the downsample BatchNorm's backward on load)
+         "dual_onload": 0, "dual_apply": 0, "fused_final": 0}
+# data-gradient route name -> times executed. The names name the data gradient's contract (what it accumulates onto,
+# which sums it takes), not the kernel: the fused 1x1 backward's final form is counted under the name _plan_dgrad gives
+# its data gradient ("tile_final_sums"), the kernel that ran in STATS["fused_final"].
+ROUTES = collections.Counter()
+
+
+def dual_onload_on() -> bool:
+    """K8S_AMD_DUAL_ONLOAD=0 (read per call: A/B, tests): a downsample block's two BatchNorms run their dual apply
+    pass and its downsample convolution's backward stays on its two kernels. K8S_AMD_BN3_ONLOAD=0 and
+    K8S_AMD_BWD1X1_FUSED=0 switch it off as well."""
+    return all(os.environ.get(k, "1") != "0"
+               for k in ("K8S_AMD_DUAL_ONLOAD", "K8S_AMD_BN3_ONLOAD", "K8S_AMD_BWD1X1_FUSED"))
 
 # (Round 5 built weight gradients on a second HIP stream -- each conv's dW kernel forked off the compute stream to
 # overlap the data gradient and BatchNorm passes after it. The streams co-ran, but the HBM-bound kernels stretched:
@@ -364,14 +379,25 @@ def _dgrad_strided_hip(C_, gy, w, stride, padding, H, W, addend=None, bn_link=No
     return dx
 
 
-def _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link):
+def _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok=True):
     """Which family forms a convolution backward's data gradient: "fused_1x1" (both gradients and the input
-    BatchNorm + ReLU's backward sums in one pass over gy and x, bwd1x1_fused.hip), "stride1" (``_plan_dgrad``),
-    "strided" (``_plan_dgrad_strided``) or "aten". Launches and allocates nothing. K8S_AMD_BWD1X1_FUSED=0 (read per
-    call: A/B, tests) keeps a normalize-on-load 1x1 convolution's two gradients on their two kernels. The fused family
-    is one route, "fused_1x1", in both of its forms; the launches that also apply the output BatchNorm's backward on
-    load (``conv_bwd``'s ``bn3``) are counted in ``STATS["bn3_onload"]``."""
+    BatchNorm + ReLU's backward sums in one pass over gy and x, bwd1x1_fused.hip), "fused_final" (the same kernel's
+    final form), "stride1" (``_plan_dgrad``), "strided" (``_plan_dgrad_strided``) or "aten". Launches and allocates
+    nothing. K8S_AMD_BWD1X1_FUSED=0 (read per call: A/B, tests) keeps a normalize-on-load 1x1 convolution's two
+    gradients on their two kernels. The fused family is one route, "fused_1x1", in both of its forms; the launches that
+    also apply the output BatchNorm's backward on load (``conv_bwd``'s ``bn3``) are counted in
+    ``STATS["bn3_onload"]``.
+    "fused_final": a (C, K) = (64, 256) 1x1 convolution reading a stored x (no xform) whose data gradient is the
+    second into x -- it accumulates onto the contiguous tensor ``addend`` -- and takes the sums of a pool-kind link
+    covering x (ResNet's stage-1 downsample convolution): both gradients and the sums in one pass, the contract of
+    ``_plan_dgrad``'s "tile_final_sums" for the data gradient. ``dw_ok``: the weight gradient is still to be formed,
+    into an fp32 slot. ``dual_onload_on()`` switches it."""
     K, R, S, C = w.shape
+    if (xform is None and dw_ok and torch.is_tensor(addend) and addend.is_contiguous() and addend.shape == x.shape
+            and R == 1 and S == 1 and stride == 1 and padding == 0 and dual_onload_on()
+            and _link_kind(bn_link, x.shape) == "pool" and _hip(gy, x, w, addend) and gy.is_contiguous()
+            and x.is_contiguous() and C_.bwd1x1_final_ok(gy.numel() // K, C, K)):
+        return "fused_final"
     if (xform is not None and addend is None and R == 1 and S == 1 and stride == 1 and padding == 0
             and os.environ.get("K8S_AMD_BWD1X1_FUSED", "1") != "0" and _link_kind(bn_link, x.shape) == "relu"
             and bn_link.x.data_ptr() == x.data_ptr() and gy.is_contiguous() and x.is_contiguous()
@@ -404,14 +430,17 @@ def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None
     that normalised input. ``x_sub``: a 1x1 / pad-0 convolution's input already subsampled by its stride
     (``nn._Conv2dNHWC`` with ``subsample_ok``): the weight gradient runs as the stride-1 product on it; ``x`` then only gives dx's shape.
     ``bn3``: a filled ``nn.Bn3Link`` -- the residual BatchNorm that read this convolution's output deferred its apply
-    pass, so ``gy`` may be that BatchNorm's incoming dy and not yet the gradient of the output. The fused 1x1 family
-    applies it on load when the link covers ``gy`` (``STATS["bn3_onload"]``); in every other case the apply pass runs
-    here first, on the ``gy`` received."""
+    pass, so ``gy`` may be that BatchNorm's incoming dy and not yet the gradient of the output. The fused 1x1 family,
+    in either form, applies it on load when the link covers ``gy`` (``STATS["bn3_onload"]`` / ``["fused_final"]``);
+    in every other case the apply pass runs here first, on the ``gy`` received (``STATS["bn3_apply"]``, or
+    ``["dual_apply"]`` for a half of a downsample block's two BatchNorms)."""
     K, R, S, C = w.shape
     C_ = _load() if gy.is_cuda else None
+    dw_ok = p is not None and x_sub is None and p.grad.dtype == torch.float32
     if bn3 is not None and not (need_dx and bn3.covers(gy)
-                                and _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link) == "fused_1x1"):
-        STATS["bn3_apply"] += 1
+                                and _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok)
+                                in ("fused_1x1", "fused_final")):
+        STATS["dual_apply" if bn3.dual else "bn3_apply"] += 1
         gy = C_.bn_bwd_apply(gy.contiguous(), bn3.x3, bn3.mask, bn3.params)
         bn3 = None
     if x_sub is not None:
@@ -426,7 +455,20 @@ def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None
     if addend is not None and not torch.is_tensor(addend) and not (
             hip and stride == 1 and K % 8 == 0 and C % 8 == 0):
         addend = addend.materialize()  # only the stride-1 dgrad on our kernels takes the (dy, mask) pair
-    family = _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link) if need_dx else None
+    family = _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok) if need_dx else None
+    if family == "fused_final":
+        ROUTES[_plan_dgrad(C_, gy, w, padding, addend, bn_link)] += 1  # the data gradient's contract: tile_final_sums
+        STATS["fused_final"] += 1
+        STATS["hip_wgrad"] += 1
+        STATS["hip_dgrad"] += 1
+        sums = _bn_sums(C_, bn_link, C, gy.device)
+        onload = {} if bn3 is None else {"x3": bn3.x3.view(-1, K), "mask": bn3.mask, "params": bn3.params}
+        C_.bwd1x1_fused(gy.view(-1, K), x.view(-1, C), w.view(K, C), None, None, None, None, None, p.grad.view(K, C),
+                        sums, p.written, addend=addend.view(-1, C), winner_x=bn_link.x.view(-1, C),
+                        winner_bits=bn_link.mask.view(-1), winner_mean=bn_link.mean, **onload)
+        _slot_written(p)
+        bn_link.deposit(sums, None, addend)
+        return addend
     if family == "fused_1x1":
         ROUTES[family] += 1
         STATS["bn3_onload"] += bn3 is not None

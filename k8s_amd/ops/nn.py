@@ -223,11 +223,17 @@ class Bn3Link:
     [sc | B | D] table -- leaves (x3, mask, params) and the identity of dy here (``fill``) and returns dy itself as
     x3's gradient: no apply pass, no dx3 tensor. The convolution's backward takes the link (``take``) and hands it to
     ``ops.conv.conv_bwd``, which applies the table on load if the gradient it received is that dy, unchanged
-    (``covers``), and otherwise runs the apply pass on what it received."""
-    __slots__ = ("y_key", "x3", "mask", "params", "dy_key")
+    (``covers``), and otherwise runs the apply pass on what it received.
+
+    A stage-1 entry block holds two: one joins bn3 to conv3 as above, the other the downsample BatchNorm to the
+    downsample convolution (``conv2d_nhwc(..., bn3_link=l)``, whose backward is then the fused kernel's final form),
+    both BatchNorms running as one (``bn_act_dual(..., bn3_link=, bn3_link_r=)``). That backward defers both halves or
+    neither (``dual``: which counter an apply pass run for the link after all is counted in)."""
+    __slots__ = ("y_key", "x3", "mask", "params", "dy_key", "dual")
 
     def __init__(self):
         self.y_key = self.x3 = self.mask = self.params = self.dy_key = None
+        self.dual = False
 
     def offer(self, y):
         """The convolution's forward: its backward will be the fused family's for an output of this shape."""
@@ -236,8 +242,8 @@ class Bn3Link:
     def offered(self, x) -> bool:
         return self.y_key == (x.data_ptr(), tuple(x.shape))
 
-    def fill(self, dy, x3, mask, params):
-        self.x3, self.mask, self.params, self.dy_key = x3, mask, params, BnStatLink._key(dy)
+    def fill(self, dy, x3, mask, params, dual=False):
+        self.x3, self.mask, self.params, self.dy_key, self.dual = x3, mask, params, BnStatLink._key(dy), dual
 
     def covers(self, t) -> bool:
         return self.dy_key == BnStatLink._key(t)
@@ -247,14 +253,14 @@ class Bn3Link:
         if self.params is None:
             return None
         out = Bn3Link()
-        out.x3, out.mask, out.params, out.dy_key = self.x3, self.mask, self.params, self.dy_key
+        out.x3, out.mask, out.params, out.dy_key, out.dual = self.x3, self.mask, self.params, self.dy_key, self.dual
         self.x3 = self.mask = self.params = self.dy_key = None
         return out
 
 
 class _Conv2dNHWC(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, anchor, p, stride, padding, with_stats, link=None, bn_link=None):
+    def forward(ctx, x, anchor, p, stride, padding, with_stats, link=None, bn_link=None, bn3_link=None):
         impl = _conv_impl()
         w = p.weight if x.dtype == p.weight.dtype else p.master.to(x.dtype)
         sums = None
@@ -272,6 +278,17 @@ class _Conv2dNHWC(torch.autograd.Function):
         ctx.save_for_backward(x, xs)
         ctx.p, ctx.stride, ctx.padding, ctx.link, ctx.bn_link = p, stride, padding, link, bn_link
         ctx.x_requires_grad = x.requires_grad
+        # the backward will be the fused kernel's final form (ops.conv._plan_bwd "fused_final", but for what only the
+        # backward knows: which of x's two readers runs second): it can take the output BatchNorm's apply pass
+        ctx.bn3_link = None
+        K_, R, S, C = w.shape
+        if (bn3_link is not None and BN_BSTATS and R == 1 and S == 1 and stride == 1 and padding == 0 and xs is None
+                and link is not None and link.shared and x.requires_grad and x.is_contiguous()
+                and bn_link is not None and bn_link.kind == "pool" and bn_link.x.shape == x.shape
+                and impl._hip(x, w) and impl.dual_onload_on() and p.grad.dtype == torch.float32
+                and _C().bwd1x1_final_ok(x.numel() // C, C, K_)):
+            bn3_link.offer(y)
+            ctx.bn3_link = bn3_link
         if sums is not None:
             ctx.mark_non_differentiable(sums)
         # the statistics output never gets a gradient: without this autograd materialises a zeros_like(sums) for
@@ -286,28 +303,30 @@ class _Conv2dNHWC(torch.autograd.Function):
         impl = _conv_impl()
         w = p.weight if x.dtype == p.weight.dtype else p.master.to(x.dtype)
         gy = gy.contiguous()
+        bn3 = ctx.bn3_link.take() if ctx.bn3_link is not None else None
         addend = None
         if ctx.link is not None:
             addend, ctx.link.grad = ctx.link.grad, None
             if addend is None and ctx.link.shared and ctx.x_requires_grad:  # first of the two readers of x
                 ctx.link.grad = impl.conv_bwd(gy, x, w, ctx.stride, ctx.padding, True, p, x_sub=xs,
-                                              bn_link=ctx.bn_link)
-                return None, None, None, None, None, None, None, None
+                                              bn_link=ctx.bn_link, bn3=bn3)
+                return None, None, None, None, None, None, None, None, None
         dx = impl.conv_bwd(gy, x, w, ctx.stride, ctx.padding, ctx.x_requires_grad, p, addend=addend, x_sub=xs,
-                           bn_link=ctx.bn_link)
-        return dx, None, None, None, None, None, None, None
+                           bn_link=ctx.bn_link, bn3=bn3)
+        return dx, None, None, None, None, None, None, None, None
 
 
 def conv2d_nhwc(x: torch.Tensor, p, stride: int = 1, padding: int = 0, with_stats: bool = False,
-                grad_link: "GradLink" = None):
+                grad_link: "GradLink" = None, bn3_link: "Bn3Link" = None):
     """NHWC convolution with KRSC weight ``p`` (no bias).
 
     With ``with_stats`` returns ``(y, sums)``: ``sums`` = fp32 [2, K] per-channel sum / sum of squares of y
     accumulated in the conv epilogue (None when the layer runs on the fallback path) -- the following
     ``batch_norm_act(..., sums=sums)`` then needs no statistics pass. ``grad_link``: a gradient for x
-    deposited there by a later-backward node (``batch_norm_act(res_link=...)``) is added to dx in the dgrad."""
+    deposited there by a later-backward node (``batch_norm_act(res_link=...)``) is added to dx in the dgrad.
+    ``bn3_link``: a Bn3Link shared with the BatchNorm that is y's only reader (``bn_act_dual(..., bn3_link_r=)``)."""
     bn_link = getattr(x, "_k8s_bnstat", None)
-    y, sums = _Conv2dNHWC.apply(x, p.store.anchor, p, stride, padding, with_stats, grad_link, bn_link)
+    y, sums = _Conv2dNHWC.apply(x, p.store.anchor, p, stride, padding, with_stats, grad_link, bn_link, bn3_link)
     return (y, sums) if with_stats else y
 
 
@@ -1147,7 +1166,7 @@ class _BnActDual(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, sums, xr, sums_r, anchor, pg, pb, run_mean, run_var, pgr, pbr, run_mean_r, run_var_r,
-                momentum, eps, stat_link=None):
+                momentum, eps, stat_link=None, bn3_link=None, bn3_link_r=None):
         x, xr = x.contiguous(), xr.contiguous()
         y, mean, invstd, mask, mean_r, invstd_r = _C().bn_fwd_from_sums_dual(
             x, sums, pg.master, pb.master, run_mean, run_var, xr, sums_r, pgr.master, pbr.master, run_mean_r,
@@ -1157,6 +1176,11 @@ class _BnActDual(torch.autograd.Function):
         ctx.stat_link = stat_link
         if stat_link is not None:
             stat_link.fill_dual(x, mask, mean, xr, mean_r, pg.store)
+        # both producing convolutions take their half of the apply pass into their backwards (two Bn3Links): both
+        # or neither
+        ctx.bn3_links = None
+        if (bn3_link is not None and bn3_link_r is not None and bn3_link.offered(x) and bn3_link_r.offered(xr)):
+            ctx.bn3_links = (bn3_link, bn3_link_r)
         return y
 
     @staticmethod
@@ -1168,7 +1192,19 @@ class _BnActDual(torch.autograd.Function):
         dg, db, finish = _bn_param_grads(pg, pb, x.device)
         dgr, dbr, finish_r = _bn_param_grads(pgr, pbr, x.device)
         pre = ctx.stat_link.take(dy) if ctx.stat_link is not None else None
-        if pre is not None and pre[1] is not None:  # both reductions came with dy (BnStatLink)
+        if pre is not None and pre[1] is None:
+            pre = None
+        if ctx.bn3_links is not None and _conv_impl().dual_onload_on():
+            # the first half only: each input's producer applies its table as it loads dy (Bn3Link)
+            params, params_r = C_.bn_bwd_dual_params(dy, mask, x, mean, invstd, pg.master, pb.master, dg, db,
+                                                     pre[0] if pre is not None else None, xr, mean_r, invstd_r,
+                                                     pgr.master, pbr.master, dgr, dbr,
+                                                     pre[1] if pre is not None else None)
+            ctx.bn3_links[0].fill(dy, x, mask, params, dual=True)
+            ctx.bn3_links[1].fill(dy, xr, mask, params_r, dual=True)
+            _conv_impl().STATS["dual_onload"] += 1
+            dx = dxr = dy
+        elif pre is not None:  # both reductions came with dy (BnStatLink)
             dx, dxr = C_.bn_bwd_dual_from_sums(dy, mask, x, mean, invstd, pg.master, pb.master, dg, db, pre[0], xr,
                                                mean_r, invstd_r, pgr.master, pbr.master, dgr, dbr, pre[1])
         else:
@@ -1177,12 +1213,14 @@ class _BnActDual(torch.autograd.Function):
                                      pgr.master, pbr.master, dgr, dbr)
         finish()
         finish_r()
-        return (dx, None, dxr) + (None,) * 13
+        return (dx, None, dxr) + (None,) * 15
 
 
-def bn_act_dual(t, bn, tr, bn_r):
+def bn_act_dual(t, bn, tr, bn_r, bn3_link=None, bn3_link_r=None):
     """``relu(bn(t) + bn_r(tr))`` for ``t`` / ``tr`` = (conv output, epilogue sums) pairs and training-mode
-    BatchNorms (models/resnet.BN); None when the fused kernel does not apply (caller runs the separate BNs)."""
+    BatchNorms (models/resnet.BN); None when the fused kernel does not apply (caller runs the separate BNs).
+    ``bn3_link`` / ``bn3_link_r``: the Bn3Links given to the convolutions that produced ``t`` and ``tr``, whose only
+    reader this is."""
     if not BN_DUAL or not (isinstance(t, tuple) and isinstance(tr, tuple)):
         return None
     (x, sums), (xr, sums_r) = t, tr
@@ -1192,7 +1230,7 @@ def bn_act_dual(t, bn, tr, bn_r):
     link = BnStatLink() if BN_BSTATS else None
     y = _BnActDual.apply(x, sums, xr, sums_r, bn.gamma.store.anchor, bn.gamma, bn.beta, bn.running_mean,
                          bn.running_var, bn_r.gamma, bn_r.beta, bn_r.running_mean, bn_r.running_var, bn.momentum,
-                         bn.eps, link)
+                         bn.eps, link, bn3_link, bn3_link_r)
     if link is not None:
         y._k8s_bnstat = link
     return y
