@@ -4,14 +4,19 @@
     B  dropout 0.1    the DROP forms: mask bits regenerated from (seed, step, site, row, col), nothing stored
 
 (a) the whole training step of ``bert_base`` (forward, backward, Adam) at ``--batch`` x ``--seq``;
-(b) per kernel at BERT's shapes: attention forward + backward (packed QKV gradient) at B x 12 heads x S, and add &
-    LayerNorm forward + backward at [B * S, 768] -- each without and with dropout.
+(b) per kernel at BERT's shapes: attention forward + backward (packed QKV gradient) at B x 12 heads x S -- the
+    one-block backward at S <= 128, the three-kernel backward above (S a multiple of 64) -- and add & LayerNorm forward
+    + backward at [B * S, 768] -- each without and with dropout.
 
 Both paths run in one process, alternating A / B per sample; a sample is at least ``--min-sec`` of device time measured
 with device events. One JSON line per sample and a summary line per comparison (ms, B / A, each path's own
 sample-to-sample spread) go to ``--out``.
 
     python benchmarks/dropout_step.py [--batch 1024] [--seq 128] [--samples 3] [--only step|kernels] [--out FILE]
+                                      [--tag NAME]
+
+``--only`` appends to ``--out``, and ``--tag`` marks every record of the run, so runs of two builds (this tree and the
+one it is compared with) can share one file.
 """
 from __future__ import annotations
 
@@ -35,6 +40,7 @@ def main(argv=None) -> int:
     ap.add_argument("--min-sec", type=float, default=1.0)
     ap.add_argument("--only", choices=["step", "kernels"], default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dropout_ab.jsonl"))
+    ap.add_argument("--tag", default=None)
     a = ap.parse_args(argv)
 
     import torch
@@ -64,6 +70,8 @@ def main(argv=None) -> int:
     f = open(a.out, "a" if a.only else "w")
 
     def emit(rec):
+        if a.tag:
+            rec = {"tag": a.tag, **rec}
         line = json.dumps(rec)
         print(line, flush=True)
         f.write(line + "\n")
@@ -176,7 +184,7 @@ def main(argv=None) -> int:
             return step
 
         compare("bert_base_step", {"A": step_of(None), "B": step_of(a.p)}, {"batch": B, "seq": S, "tokens": B * S})
-        # counted after the timed steps: both must be empty / zero at seq 128
+        # counted after the timed steps: both must be empty / zero at the fused shapes (seq <= 128 or a multiple of 64)
         emit({"what": "bert_base_step_fallbacks", "gemm_fallbacks": dict(G.FALLBACKS),
               "dropout_fallbacks": A.DROPOUT_FALLBACKS})
     f.close()

@@ -40,15 +40,16 @@ long fill_qkv(Args& a, const Tensor& q, const Tensor& k, const Tensor& v, bool c
   return D;
 }
 
-// drop_state (optional): dropout on the probabilities, one-block shapes only (flash_bwd_one_block, D = 64)
+// drop_state (optional): dropout on the probabilities, for the shapes of flash_dropout_fused (D = 64: the one-block
+// form, or Sq and Sk multiples of 64)
 std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, bool causal, OptTensor kv_lens, double scale,
                               OptTensor drop_state, int64_t drop_thr, double drop_scale, int64_t drop_site) {
   AttnFwdArgs a;
   const long D = fill_qkv(a, q, k, v, causal, kv_lens, scale);
   const long B = a.B, Sq = a.Sq, Hq = a.Hq, Sk = a.Sk, Hkv = a.Hkv;
   if (drop_state) {
-    TORCH_CHECK(k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, 1),
-                "attention dropout needs a one-block shape (flash_bwd_one_block)");
+    TORCH_CHECK(k8s_amd::flash_dropout_fused((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, 1),
+                "attention dropout needs a flash_dropout_fused shape (D = 64: one-block, or Sq, Sk multiples of 64)");
     a.drop = drop_args(*drop_state, drop_thr, drop_scale, drop_site);
   }
   auto o = torch::empty({B, Sq, Hq, D}, q.options());
@@ -87,11 +88,17 @@ std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o,
     TORCH_CHECK(dqkv && one_block, "dbias needs the packed gradient and a one-block shape (flash_bwd_one_block)");
     check_channel_f32(*dbias, Wp, "dbias");
   }
-  if (drop_state) {
-    TORCH_CHECK(one_block, "attention dropout needs a one-block shape (flash_bwd_one_block)");
-    a.drop = drop_args(*drop_state, drop_thr, drop_scale, drop_site);
-  }
   auto delta = torch::empty({B, Hq, ld}, q.options().dtype(at::kFloat));
+  Tensor rowkey;  // the three-kernel form's dropout row keys, rows padded like delta's
+  if (drop_state) {
+    TORCH_CHECK(k8s_amd::flash_dropout_fused((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, a.dkv_split),
+                "attention dropout needs a flash_dropout_fused shape (D = 64: one-block, or Sq, Sk multiples of 64)");
+    a.drop = drop_args(*drop_state, drop_thr, drop_scale, drop_site);
+    if (!one_block) {
+      rowkey = torch::empty({B, Hq, ld}, q.options().dtype(at::kInt));
+      a.rowkey = reinterpret_cast<uint32_t*>(rowkey.data_ptr<int>());
+    }
+  }
   Tensor dq, dk, dv;
   if (dqkv) {
     auto g = dqkv->view({B, Sq, Hq + 2 * Hkv, D});
@@ -138,6 +145,13 @@ void bind_attention(pybind11::module_& m) {
           return k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv,
                                               k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal));
         }, "whether flash_bwd runs as the one-block short-sequence kernel (which can also emit the packed bias gradient)");
+  m.def("flash_dropout_fused", [](int64_t D, int64_t Sq, int64_t Sk, int64_t Hq, int64_t Hkv, bool causal, int64_t B) {
+          return k8s_amd::flash_dropout_fused((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv,
+                                              k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal));
+        }, "whether flash_fwd / flash_bwd take dropout on the probabilities for this shape");
+  m.def("flash_dkv_splits", [](int64_t B, int64_t Sq, int64_t Sk, int64_t Hkv, bool causal) {
+          return k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal);
+        }, "chunks per key block of the dK/dV kernel (above 1: fp32 partials and a reduce pass)");
 }
 
 }  // namespace k8s_amd::binding

@@ -37,6 +37,10 @@
 //   dQ in a second kernel shaped like the forward (per query block: S^T, dP^T recomputed, dQ^T += K^T dS^T),
 //   so no fp32 atomics; delta = rowsum(dO * O) is a tiny kernel ahead of both. lse / delta rows are padded
 //   to a multiple of 64 so a query tile's 256 B of each can be staged by one global_load_lds.
+//   Dropout on the probabilities (DROP forms, D = 64, flash_dropout_fused): with P~ = keep ? P : 0 and the forward's
+//   O = scale * P~ V, dV^T += dO^T P~ (scaled where the fp32 sum leaves) and dS = P (keep ? scale * dP : 0 - delta);
+//   delta is unchanged, since O carries the dropped, scaled probabilities. The keep test takes the absolute query row
+//   and key; the queries' row keys come from a table written beside delta (flash_rowkey_kernel).
 #include <algorithm>
 #include <stdexcept>
 #include <type_traits>
@@ -115,8 +119,10 @@ __device__ __forceinline__ const uint16_t* kh_src(const uint16_t* base, long rst
 // PV product, and the scale is folded into the epilogue's 1 / l.
 template <int D, int TILE, int NB = 2, int QS = 2, bool DROP = false>
 // (DROP on the one-tile form: 2 blocks per CU -- the mask's integer temporaries beside the 128-key score tile do not
-// fit the 168 registers of 3)
-__global__ void __launch_bounds__(FA_THREADS, NB == 1 && !DROP ? (QS == 1 ? 4 : 3) : 2) flash_fwd_kernel(AttnFwdArgs a) {
+// fit the 168 registers of 3. On 64-key tiles they do: bounded to 3 blocks per CU like the plain form, which left
+// alone took 174 registers)
+__global__ void __launch_bounds__(FA_THREADS, NB == 1 && !DROP ? (QS == 1 ? 4 : 3) : (DROP && TILE == 64 ? 3 : 2))
+flash_fwd_kernel(AttnFwdArgs a) {
   constexpr int BM = 64 * QS;  // queries per block
   constexpr int FA_BN = TILE;  // keys per iteration
   constexpr int NI = FA_BN / 16;       // 16-key subtiles
@@ -368,16 +374,35 @@ __global__ void __launch_bounds__(256) flash_delta_kernel(const uint16_t* o, lon
   if (row < R && part == 0) delta[((long)b * Hq + h) * ld + q] = acc;
 }
 
+// Dropout on the three-kernel backward: rowkey[b, h, q] = drop_rowkey(row (b * Hq + h) * Sq + q), rows of stride
+// lse_ld like lse / delta, launched beside the delta kernel. A dK/dV lane holds one key and 4 * NQ queries, so it
+// cannot carry Philox keys in registers as the forward does: it stages the tile's keys from this table with
+// lse | delta. The kernel reads the device [seed, step] pair itself, so a captured graph draws the new step's keys on
+// every replay.
+__global__ void __launch_bounds__(256) flash_rowkey_kernel(uint32_t* rowkey, DropArgs drop, long rows, int Sq,
+                                                          long ld) {
+  const long row = (long)blockIdx.x * 256 + threadIdx.x;  // (b * Hq + h) * Sq + q
+  if (row >= rows) return;
+  const long bh = row / Sq;
+  rowkey[bh * ld + (row - bh * Sq)] = drop_rowkey(drop, (uint64_t)row);
+}
+
 // ---- dK, dV: one block = 64 keys of one KV head (wave w: keys k0 + 16w .. +15, K/V fragments in VGPRs),
 // looping over every (query head of the GQA group, 64-query tile); Q / dO / lse / delta tiles double-buffered
 // in LDS through global_load_lds. Lane layout of S, dP, P, dS: key = li, query = 16*qs + 4*g + r.
-template <int D, int TILE>
+// DROP: the forward's dropout (flash_bwd_short_kernel's math): the tile's row keys are staged behind lse | delta (at
+// TILE 64 a third 256-B piece of the same copy; at TILE 128, where lse | delta fill the 1 KB, a second copy into 1 KB
+// more -- a whole wave's 64 x 16 B, which also keeps the stages 1 KB aligned), P~ = keep ? P : 0 feeds dV,
+// dS = P (scale * keep * dP - delta) feeds dK, and dV takes drop.scale where the fp32 accumulator leaves (the bf16
+// copy-out here, or flash_dkv_reduce_kernel behind the split partials).
+template <int D, int TILE, bool DROP = false>
 __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArgs a) {
   constexpr int ND = D / 16, NK = D / 32;
   constexpr int FB_BM = TILE;              // queries per iteration
   constexpr int NQ = FB_BM / 16;           // 16-query subtiles
   constexpr int TQ = FB_BM * D * 2;        // Q / dO tile bytes
-  constexpr int STAGE = 2 * TQ + 1024;     // Q | dO | lse (256 B) delta (256 B) pad
+  constexpr bool RK2 = DROP && FB_BM * 12 > 1024;  // row keys by a second copy
+  constexpr int STAGE = 2 * TQ + 1024 + (RK2 ? 1024 : 0);  // Q | dO | lse delta [rowkey] (FB_BM words each) pad
   __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, g = lane >> 4, li = lane & 15;
   const int wid_u = __builtin_amdgcn_readfirstlane(wid);
@@ -458,12 +483,18 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
           glds16(kh_src(dop, a.sds, FB_BM, q0, a.Sq, s), base + TQ + wb);
         }
       }
+      constexpr int L4 = FB_BM / 4;  // lanes per 4-float row piece
+      const long row = ((long)b * a.Hq + h) * a.lse_ld + q0;
       if (wid_u == 0) {  // lse | delta of the tile's queries (rows padded to lse_ld, so never out of bounds)
-        constexpr int L4 = FB_BM / 4;  // lanes per 4-float row piece
-        const long row = ((long)b * a.Hq + h) * a.lse_ld + q0;
-        const float* src = lane < L4 ? a.lse + row + lane * 4
-                                     : (lane < 2 * L4 ? a.delta + row + (lane - L4) * 4 : a.lse + row);
+        const void* src = lane < L4 ? a.lse + row + lane * 4
+                                    : (lane < 2 * L4 ? a.delta + row + (lane - L4) * 4 : a.lse + row);
+        if constexpr (DROP && !RK2) {  // | rowkey, rows padded alike
+          if (lane >= 2 * L4 && lane < 3 * L4) src = a.rowkey + row + (lane - 2 * L4) * 4;
+        }
         glds16(src, base + 2 * TQ);
+      }
+      if constexpr (RK2) {  // (lanes past L4 copy the same keys again into the pad)
+        if (wid_u == 1) glds16(a.rowkey + row + (lane & (L4 - 1)) * 4, base + 2 * TQ + 1024);
       }
     };
     int hh = hk * rep + it0 / per_head, qt = qt0 + it0 % per_head;
@@ -514,11 +545,22 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
             d4[r] = ok ? d4[r] : 0.f;
           }
         }
+        if constexpr (DROP) {
+          const uint32_t* rk4 = reinterpret_cast<const uint32_t*>(tl + 2 * FB_BM) + qs * 16 + g * 4;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = fexp2(sv[qs][r] * a.scale_log2 - l4[r]);
-          sv[qs][r] = p;
-          dp[qs][r] = p * (dp[qs][r] - d4[r]);
+          for (int r = 0; r < 4; ++r) {
+            const float p = fexp2(sv[qs][r] * a.scale_log2 - l4[r]);
+            const bool keep = drop_keep(rk4[r], (uint32_t)key, a.drop.thr);
+            sv[qs][r] = keep ? p : 0.f;
+            dp[qs][r] = p * ((keep ? dp[qs][r] * a.drop.scale : 0.f) - d4[r]);
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float p = fexp2(sv[qs][r] * a.scale_log2 - l4[r]);
+            sv[qs][r] = p;
+            dp[qs][r] = p * (dp[qs][r] - d4[r]);
+          }
         }
       }
       // ---- dV^T += dO^T P, dK^T += Q^T dS   (k = queries in the permuted order of the accumulators)
@@ -563,7 +605,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         x[r] = (short)f2bf(dka[d][r] * a.scale);
-        y[r] = (short)f2bf(dva[d][r]);
+        y[r] = (short)f2bf(DROP ? dva[d][r] * a.drop.scale : dva[d][r]);
       }
       *reinterpret_cast<bf16x4_t*>(dkp + d * 16 + g * 4) = x;
       *reinterpret_cast<bf16x4_t*>(dvp + d * 16 + g * 4) = y;
@@ -572,7 +614,8 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
 }
 
 // sum of the dK / dV chunk partials (fp32), dK scaled, written as bf16 at the gradient strides; 8 columns per thread
-template <int D>
+// (DROP: dV takes the dropout scale here, where its fp32 sum leaves)
+template <int D, bool DROP = false>
 __global__ void __launch_bounds__(256) flash_dkv_reduce_kernel(AttnBwdArgs a) {
   constexpr int CPR = D / 8;  // 8-column pieces per row
   const long rows = (long)a.B * a.Hkv * a.Sk;
@@ -598,8 +641,8 @@ __global__ void __launch_bounds__(256) flash_dkv_reduce_kernel(AttnBwdArgs a) {
   for (int r = 0; r < 4; ++r) {
     xk[r] = (short)f2bf(k0[r] * a.scale);
     xk[4 + r] = (short)f2bf(k1[r] * a.scale);
-    xv[r] = (short)f2bf(v0[r]);
-    xv[4 + r] = (short)f2bf(v1[r]);
+    xv[r] = (short)f2bf(DROP ? v0[r] * a.drop.scale : v0[r]);
+    xv[4 + r] = (short)f2bf(DROP ? v1[r] * a.drop.scale : v1[r]);
   }
   *reinterpret_cast<bf16x8_t*>(a.dk + b * a.sgkb + key * a.sgks + hk * a.sgkh + c) = xk;
   *reinterpret_cast<bf16x8_t*>(a.dv + b * a.sgvb + key * a.sgvs + hk * a.sgvh + c) = xv;
@@ -609,7 +652,8 @@ __global__ void __launch_bounds__(256) flash_dkv_reduce_kernel(AttnBwdArgs a) {
 // double-buffered in LDS, S^T = K Q^T and dP^T = V dO^T recomputed (lane: query = li, keys 4g+r), and
 // dQ^T += K^T dS^T with dS^T consumed in place (permuted k) and K^T read transposed from the K tile.
 // No atomics: each block owns its queries.
-template <int D, int TILE, int QS>
+// DROP: the same dS as the dK/dV kernel; a lane's QS row keys come from the row-key table next to lse / delta.
+template <int D, int TILE, int QS, bool DROP = false>
 __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 : 2) flash_bwd_dq_kernel(AttnBwdArgs a) {
   constexpr int ND = D / 16, NK = D / 32;
   constexpr int FB_BN = TILE;  // keys per iteration
@@ -644,6 +688,7 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
   // query of set qs on this lane: q0w + 16 qs + li
   mfma_bf16x8 qf[QS][NK], df[QS][NK];
   float lq[QS], dq_[QS];
+  uint32_t rk[QS];  // (DROP)
   const long lrow = ((long)b * a.Hq + h) * a.lse_ld;
 #pragma unroll
   for (int qs = 0; qs < QS; ++qs) {
@@ -660,6 +705,8 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
     }
     lq[qs] = qi < a.Sq ? a.lse[lrow + qi] : INFINITY;
     dq_[qs] = qi < a.Sq ? a.delta[lrow + qi] : 0.f;
+    rk[qs] = 0;
+    if constexpr (DROP) rk[qs] = qi < a.Sq ? a.rowkey[lrow + qi] : 0u;
   }
 
   f32x4_t acc[QS][ND];
@@ -749,7 +796,12 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float p = fexp2(s[i][qs][r] * a.scale_log2 - lq[qs]);
-            dp[i][qs][r] = p * (dp[i][qs][r] - dq_[qs]);
+            if constexpr (DROP) {
+              const bool keep = drop_keep(rk[qs], (uint32_t)(key0 + i * 16 + g * 4 + r), a.drop.thr);
+              dp[i][qs][r] = p * ((keep ? dp[i][qs][r] * a.drop.scale : 0.f) - dq_[qs]);
+            } else {
+              dp[i][qs][r] = p * (dp[i][qs][r] - dq_[qs]);
+            }
           }
 #pragma unroll
       for (int s2 = 0; s2 < NI / 2; ++s2) {
@@ -1064,6 +1116,14 @@ bool flash_bwd_one_block(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split) 
   return on && D == 64 && Sq > 0 && Sk > 0 && Sq <= FS_S && Sk <= FS_S && Hq == Hkv && dkv_split == 1;
 }
 
+// Dropout on the probabilities is fused for the one-block shapes and, in the multi-tile forward and the three-kernel
+// backward, for D = 64 with Sq and Sk multiples of 64 (BERT's 128 / 256 / 384 / 512; key ends inside a tile still
+// come from kv_lens and causal diagonals). Other lengths above 128 and D = 128 run the reference composition, counted.
+bool flash_dropout_fused(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split) {
+  if (flash_bwd_one_block(D, Sq, Sk, Hq, Hkv, dkv_split)) return true;
+  return D == 64 && Sq > 0 && Sk > 0 && Sq % 64 == 0 && Sk % 64 == 0 && Hkv > 0 && Hq % Hkv == 0;
+}
+
 // =============================================================================== launchers
 // D = 64 with long sequences: 128-wide key / query steps (same MFMA work per barrier as D = 128)
 static bool big_tile(int D, int S) { return D == 64 && S >= 1024; }
@@ -1095,9 +1155,12 @@ static bool fwd_one_tile() {
 void launch_flash_fwd(const AttnFwdArgs& a, int D, hipStream_t st) {
   const int nqb = (a.Sq + FA_BM - 1) / FA_BM;
   const dim3 grid(nqb * a.Hq * a.B), blk(FA_THREADS);
-  if (a.drop.state) {  // the shapes of the one-block backward only (checked by the caller: flash_bwd_one_block)
-    if (D != 64 || a.Sq > FS_S || a.Sk > FS_S) throw std::runtime_error("flash_fwd: dropout needs a one-block shape");
-    if (fwd_one_tile()) hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 1, 2, true>), grid, blk, 0, st, a);
+  if (a.drop.state) {  // the DROP form of what the plain dispatch below picks at D = 64
+    if (!flash_dropout_fused(D, a.Sq, a.Sk, a.Hq, a.Hkv, 1))
+      throw std::runtime_error("flash_fwd: dropout needs a shape of flash_dropout_fused");
+    if (big_tile(D, a.Sk)) hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 2, 2, true>), grid, blk, 0, st, a);
+    else if (a.Sk <= 128 && fwd_one_tile())
+      hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 1, 2, true>), grid, blk, 0, st, a);
     else hipLaunchKernelGGL((flash_fwd_kernel<64, 64, 2, 2, true>), grid, blk, 0, st, a);
     return;
   }
@@ -1105,6 +1168,33 @@ void launch_flash_fwd(const AttnFwdArgs& a, int D, hipStream_t st) {
   else if (big_tile(D, a.Sk)) hipLaunchKernelGGL((flash_fwd_kernel<64, 128>), grid, blk, 0, st, a);
   else if (a.Sk <= 128 && fwd_one_tile()) hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 1>), grid, blk, 0, st, a);
   else hipLaunchKernelGGL((flash_fwd_kernel<64, 64>), grid, blk, 0, st, a);
+}
+
+// the three-kernel backward with dropout (D = 64): the row-key table beside delta, then the DROP forms of what the
+// plain dispatch in launch_flash_bwd picks
+static void launch_flash_bwd_drop(const AttnBwdArgs& a, const uint16_t* o, long sob, long sos, long soh,
+                                  hipStream_t st) {
+  const long R = (long)a.B * a.Sq * a.Hq;
+  hipLaunchKernelGGL(flash_delta_kernel<64>, dim3((unsigned)((R * 8 + 255) / 256)), dim3(256), 0, st, o, sob, sos, soh,
+                     a.dO, a.sdb, a.sds, a.sdh, a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
+  hipLaunchKernelGGL(flash_rowkey_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, a.rowkey, a.drop, R,
+                     a.Sq, a.lse_ld);
+  const dim3 gkv(((a.Sk + FB_BN - 1) / FB_BN) * a.Hkv * a.B * a.dkv_split), blk(FA_THREADS);
+  const bool big = big_tile(64, a.Sq);
+  const bool qs2 = !big && (long)((a.Sq + 127) / 128) * a.Hq * a.B >= 2L * planner_cus();
+  const dim3 gq(((a.Sq + (qs2 ? 127 : 63)) / (qs2 ? 128 : 64)) * a.Hq * a.B);
+  if (big) {
+    hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 128, true>), gkv, blk, 0, st, a);
+    hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 128, 1, true>), gq, blk, 0, st, a);
+  } else {
+    hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 64, true>), gkv, blk, 0, st, a);
+    if (qs2) hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 2, true>), gq, blk, 0, st, a);
+    else hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 1, true>), gq, blk, 0, st, a);
+  }
+  if (a.dkv_split > 1) {
+    const long n = (long)a.B * a.Hkv * a.Sk * 8;
+    hipLaunchKernelGGL((flash_dkv_reduce_kernel<64, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+  }
 }
 
 void launch_flash_bwd(const AttnBwdArgs& a, int D, const uint16_t* o, long sob, long sos, long soh,
@@ -1120,7 +1210,12 @@ void launch_flash_bwd(const AttnBwdArgs& a, int D, const uint16_t* o, long sob, 
     }
     return;
   }
-  if (a.drop.state) throw std::runtime_error("flash_bwd: dropout needs a one-block shape");
+  if (a.drop.state) {
+    if (!flash_dropout_fused(D, a.Sq, a.Sk, a.Hq, a.Hkv, a.dkv_split) || !a.rowkey)
+      throw std::runtime_error("flash_bwd: dropout needs a shape of flash_dropout_fused and the row-key workspace");
+    launch_flash_bwd_drop(a, o, sob, sos, soh, st);
+    return;
+  }
   const long R = (long)a.B * a.Sq * a.Hq;
   const int lpr = D / 8;
   const dim3 dgrid((unsigned)((R * lpr + 255) / 256));

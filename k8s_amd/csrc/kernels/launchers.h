@@ -335,7 +335,7 @@ struct AttnFwdArgs {
   long lse_ld;         // row stride of lse (Sq rounded up to 64)
   int B, Sq, Sk, Hq, Hkv, causal;
   float scale_log2;
-  // dropout on the probabilities (one-block shapes only, flash_bwd_one_block): row = (b * Hq + h) * Sq + q, col = key
+  // dropout on the probabilities (the shapes of flash_dropout_fused): row = (b * Hq + h) * Sq + q, col = key
   DropArgs drop;
 };
 struct AttnBwdArgs {
@@ -359,10 +359,16 @@ struct AttnBwdArgs {
   float* cpart = nullptr;
   int cpart_ld = 0;
   DropArgs drop;  // as the forward's
+  // dropout on the three-kernel form: the queries' row keys, [B, Hq, lse_ld] scratch next to delta (written by the
+  // delta kernel from the device [seed, step] pair, read by the dK/dV and dQ kernels)
+  uint32_t* rowkey = nullptr;
 };
 int flash_dkv_splits(int B, int Sq, int Sk, int Hkv, int causal);
 // the whole backward of one (batch, head) in one block (flash_bwd_short_kernel) applies to this shape
 bool flash_bwd_one_block(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split);
+// dropout on the probabilities is fused for this shape: the one-block form, or the long form (multi-tile forward and
+// three-kernel backward) at D = 64 with Sq and Sk multiples of 64
+bool flash_dropout_fused(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split);
 // ResNet stem BatchNorm + ReLU + 3x3 / s2 / p1 max pool, fused (batchnorm.hip): forward from the conv's epilogue sums
 // (params = fp32 [2][C] scale | shift, idx = winner byte per pooled element); backward into dx of the conv output
 // (params = fp32 [4][C] workspace, work = pool_bn_workspace_floats(C))

@@ -6,8 +6,10 @@
 //   keep   = h >= thr,  thr = min(floor(p * 2^32 + 0.5), 2^32 - 1)
 //
 // Philox quality applies once per row (wave-uniform in the norm kernels, two calls per lane in the attention forward, a
-// 128-entry LDS table in the one-block attention backward); each element then costs ~10 integer VALU operations in
-// whichever axis order the kernel holds its elements. ops/reference.py dropout_keep is the same definition in torch.
+// 128-entry LDS table in the one-block attention backward; in the three-kernel attention backward flash_rowkey_kernel
+// writes a [B, Hq, Sq] table beside delta, which the dK/dV kernel stages per query tile with lse | delta and the dQ
+// kernel reads once per lane); each element then costs ~10 integer VALU operations in whichever axis order the kernel
+// holds its elements. ops/reference.py dropout_keep is the same definition in torch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

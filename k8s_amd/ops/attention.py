@@ -11,9 +11,10 @@ dims other than 64/128 and CPU tensors use an explicit matmul/softmax
 reference (no SDPA dispatch, so no Triton-built kernels run).
 
 ``dropout=(p, DropoutState, site)`` drops attention probabilities with the counter generator of
-``csrc/kernels/rng.h`` (row = (b * Hq + h) * Sq + q, col = key): fused into the forward and the one-block backward
-for the shapes that backward takes (head_dim 64, Sq, Sk <= 128, Hq == Hkv); any other GPU shape runs the reference
-composition with the same mask, counted in ``DROPOUT_FALLBACKS`` and warned about once.
+``csrc/kernels/rng.h`` (row = (b * Hq + h) * Sq + q, col = key): fused into the forward and the backward for the
+shapes of ``flash_dropout_fused`` -- head_dim 64 and either the one-block backward's shapes (Sq, Sk <= 128, Hq == Hkv)
+or Sq and Sk multiples of 64 (the multi-tile forward and the three-kernel backward); any other GPU shape runs the
+reference composition with the same mask, counted in ``DROPOUT_FALLBACKS`` and warned about once.
 """
 from __future__ import annotations
 
@@ -33,8 +34,9 @@ DROPOUT_FALLBACKS = 0
 def _dropout_fallback(q, k):
     global DROPOUT_FALLBACKS
     if DROPOUT_FALLBACKS == 0:
-        warnings.warn("k8s_amd attention: dropout on q %s / k %s is outside the one-block kernels' shape contract "
-                      "(head_dim 64, Sq, Sk <= 128, Hq == Hkv); using the reference composition"
+        warnings.warn("k8s_amd attention: dropout on q %s / k %s is outside the fused kernels' shape contract "
+                      "(head_dim 64; Sq, Sk <= 128 with Hq == Hkv, or Sq and Sk multiples of 64); using the reference "
+                      "composition"
                       % (tuple(q.shape), tuple(k.shape)))
     DROPOUT_FALLBACKS += 1
 
@@ -46,11 +48,12 @@ def _drop_spec(dropout):
 
 
 def _drop_fused(q, k, v, causal) -> bool:
-    """The fused dropout path takes this call: the flash kernels' operand contract and a one-block backward shape."""
-    if not (_flash_ok(q, k, v) and q.shape[-1] == 64):
+    """The fused dropout path takes this call: the flash kernels' operand contract and a ``flash_dropout_fused``
+    shape."""
+    if not _flash_ok(q, k, v):
         return False
     B, Sq, Hq, D = q.shape
-    return bool(_load().flash_bwd_one_block(D, Sq, k.shape[1], Hq, k.shape[2], causal, B))
+    return bool(_load().flash_dropout_fused(D, Sq, k.shape[1], Hq, k.shape[2], causal, B))
 
 
 def _flash_ok(q, k, v) -> bool:
@@ -74,7 +77,7 @@ def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] =
     s = torch.matmul(qh, kh.transpose(-1, -2)) * scale
     Sk = k.shape[1]
     if causal:
-        mask = torch.ones(S, Sk, dtype=torch.bool, device=q.device).triu(1)
+        mask = torch.ones(S, Sk, dtype=torch.bool, device=q.device).triu(1 + Sk - S)  # bottom-right aligned
         s = s.masked_fill(mask, float("-inf"))
     if kv_lens is not None:
         keymask = torch.arange(Sk, device=q.device)[None, :] >= kv_lens[:, None].to(q.device)
@@ -229,8 +232,9 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
     since those would see the rotated values; ``tests/test_attention_gpu.py`` pins in place == copy bitwise.
     ``rope_applied``: q / k already rotated by the projection's epilogue (``ops.nn.linear_rope``); the backward still
     returns the gradient of the UN-rotated projection output (dqkv rotated back), which is what that linear's backward
-    takes. ``dropout`` = (p, DropoutState, site): dropout on the probabilities, fused on the one-block shapes (see the
-    module docstring); other shapes take the split + ``attention`` composition, which counts the fallback."""
+    takes. ``dropout`` = (p, DropoutState, site): dropout on the probabilities, fused on the ``flash_dropout_fused``
+    shapes (see the module docstring; the bias gradient stays a one-block feature); other shapes take the split +
+    ``attention`` composition, which counts the fallback."""
     D = head_dim
     scale = scale or 1.0 / math.sqrt(D)
     W = (heads + 2 * kv_heads) * D
@@ -238,7 +242,7 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
     fused = qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128) and qkv.shape[-1] == W and \
         W % 8 == 0 and qkv.is_contiguous()
     if fused and drop is not None:
-        fused = D == 64 and bool(_load().flash_bwd_one_block(D, S, S, heads, kv_heads, causal, B))
+        fused = bool(_load().flash_dropout_fused(D, S, S, heads, kv_heads, causal, B))
     if fused:
         pos, table = rope if rope is not None else (None, None)
         return _FlashQKV.apply(qkv, B, S, heads, kv_heads, D, causal, kv_lens, scale, pos, table, bias_link,
