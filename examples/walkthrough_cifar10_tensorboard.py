@@ -13,7 +13,10 @@ it is Done. This is the same flow on one box, with every piece real:
 4. the job polled to ``phase: Done``, then the loss curve and the evaluation accuracy (``eval/top1``, from the
    trainer's ``--eval-every``) read back through TensorBoard's HTTP API.
 
-    python examples/walkthrough_cifar10_tensorboard.py [--steps 100] [--gpus 0]
+    python examples/walkthrough_cifar10_tensorboard.py [--steps 100] [--gpus 0] [--dataset toy]
+
+``--dataset toy`` writes the toy dataset (``k8s_amd.tools.make_dataset --toy``: ten noisy 40x40 classes) into the job's
+directory and trains on it with ``--data-dir``: ``eval/top1`` is then the accuracy on its held-out split, and it rises.
 
 Prints a JSON summary (job state, TensorBoard URL, runs/tags, the loss and eval/top1 series) and exits 0 on success.
 """
@@ -33,13 +36,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from k8s_amd.fakeapi.cluster import LocalCluster  # noqa: E402
 
 
-def manifest(name: str, logdir: str, steps: int, gpu: bool) -> dict:
+def manifest(name: str, logdir: str, steps: int, gpu: bool, data_dir: str = None) -> dict:
     container = {"name": "tensorflow", "image": "k8s-amd/trainer:rocm7-gfx950",
                  "args": ["--model", "resnet_tiny", "--steps", str(steps), "--log-every", "5", "--logdir", logdir,
                           # accuracy on the (fixed, synthetic) training batch every 10 steps and after the last one:
                           # the eval/loss, eval/top1 and eval/top5 series next to the loss curve
                           "--eval-every", "10", "--eval-data", "train"],
                  "volumeMounts": [{"name": "logs", "mountPath": logdir}]}
+    if data_dir:  # a dataset under the mounted logDir: train on its train split, evaluate the whole val split
+        container["args"] = container["args"][:-2] + ["--data-dir", data_dir, "--batch", "32", "--lr", "0.02",
+                                                      "--eval-batches", "8"]
     if gpu:
         container["resources"] = {"limits": {"amd.com/gpu": 1}}
     else:
@@ -78,11 +84,18 @@ def tensorboard_url(c: LocalCluster, job: str, ns: str = "default", timeout: flo
 
 
 def run(steps: int = 100, gpus=None, job: str = "cifar10-resnet", logdir: str = None, timeout: float = 900.0,
-        verbose: bool = True) -> dict:
+        verbose: bool = True, dataset: str = None) -> dict:
     logdir = logdir or tempfile.mkdtemp(prefix="k8s_amd_tb_")
     say = print if verbose else (lambda *a, **k: None)
+    data_dir = None
+    if dataset == "toy":
+        from k8s_amd.tools.make_dataset import make_toy
+
+        data_dir = os.path.join(logdir, "dataset")
+        make_toy(data_dir)
+        say("wrote the toy dataset to %s" % data_dir)
     with LocalCluster(gpus=gpus or []) as c:
-        c.create(manifest(job, logdir, steps, bool(gpus)))
+        c.create(manifest(job, logdir, steps, bool(gpus), data_dir))
         say("submitted TfJob %s (logDir %s)" % (job, logdir))
         tb = tensorboard_url(c, job)
         say("TensorBoard: %s" % tb)
@@ -118,9 +131,11 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--gpus", default="", help="GPU ids for the kubelet (empty: train on the CPU)")
     ap.add_argument("--timeout", type=float, default=900.0)
+    ap.add_argument("--dataset", default=None, choices=["toy"],
+                    help="train on a generated dataset instead of synthetic batches")
     a = ap.parse_args(argv)
     gpus = [int(x) for x in a.gpus.split(",") if x != ""]
-    out = run(a.steps, gpus, timeout=a.timeout)
+    out = run(a.steps, gpus, timeout=a.timeout, dataset=a.dataset)
     print(json.dumps(out))
     return 0 if out["state"] == "Succeeded" and out["loss_points"] > 0 else 1
 

@@ -428,6 +428,15 @@ void launch_stem_wgrad(const uint16_t* xs, const uint16_t* dy, float* ws, float*
                        hipStream_t st);
 void launch_stem_dw_s2d(const float* dw4, int K, int R, int Cw, float* dw7, hipStream_t st);
 
+// ---- augment.hip: a dataset batch in one pass -- gather by the int32 table [N][6] (src index, y0, x0, h, w, flip),
+// crop or bilinear resize to S x S, flip, bf16(fmaf(u8, a_c, b_c)), written as the stem's input ([N][S][S][8], or
+// with s2d the [N][S/2+3][S/2+3][16] image of launch_stem_s2d_input at pad 3). src uint8 [M][Hs][Ws][3].
+struct AugNorm {
+  float a[3], b[3];  // 1 / std_c, -mean_c / std_c
+};
+void launch_augment(const uint8_t* src, const int* table, int N, int M, int Hs, int Ws, int S, const AugNorm& nm,
+                    bool s2d, uint16_t* out, hipStream_t st);
+
 // ---- NHWC max pooling (pool.hip): idx = winning window position per output element (uint8)
 void launch_subsample_nhwc(const uint16_t* x, uint16_t* y, int N, int H, int W, int C, int s, hipStream_t st);
 void launch_maxpool_fwd(const uint16_t* x, uint16_t* y, uint8_t* idx, int N, int H, int W, int C, int Ho, int Wo,

@@ -2,8 +2,11 @@
 
 Every workload the trainer (``python -m k8s_amd.trainer``) and the benches
 can run, at the exact BASELINE.json shapes plus small variants for CPU tests.
-Data is synthetic (random images / token ids of the named shape): the
-reference's workloads are external TF programs and there is no dataset access.
+Data is synthetic by default (random images / token ids of the named shape): the
+reference's workloads are external TF programs. The ResNet workloads can also
+read a dataset directory (``build(..., data=...)``, ``k8s_amd.data``): batches
+then come from its ``train`` split through the fused augmentation kernel and
+held-out batches from its ``val`` split.
 """
 from __future__ import annotations
 
@@ -36,6 +39,8 @@ class Workload:
     eval_batch: Optional[Callable] = None
     # eval_state() -> the flat tensor an evaluation pass shares between ranks (ResNet: the folded BatchNorms), or None
     eval_state: Optional[Callable] = None
+    # close() releases what the batches hold (a dataset loader's background thread); None: nothing to release
+    close: Optional[Callable] = None
 
 
 MODELS = ("resnet50", "resnet_tiny", "bert_base", "bert_tiny", "llama3_8b", "llama_1b", "llama_tiny")
@@ -59,14 +64,82 @@ def _plain_eval_forward(model, x):
         model.train(was)
 
 
+def _resnet_evaluate(model):
+    """``Workload.evaluate`` of a ResNet: the sums of one batch (rows labelled -100 are not counted)."""
+    def evaluate(b, folded=None):
+        with torch.no_grad():
+            logits = model.forward_infer(b[0], folded) if EVAL_FOLDED else _plain_eval_forward(model, b[0])
+            loss, rank = K.xent_eval(logits, b[1])
+            return {"loss_sum": loss.double().sum(), "count": (b[1] != -100).sum(),
+                    "top1": (rank < 1).sum(), "top5": (rank < 5).sum()}
+
+    return evaluate
+
+
+def dataset_plan(name: str, device, batch: int, image: Optional[int], data: Dict, need_val: bool = False):
+    """(dataset, Loader keyword arguments, description) of ``build(name, ..., data=data)``, with every check of the
+    configuration made (``DataError``): what the trainer's ``start`` event reports before the model is built."""
+    from k8s_amd.data import open_dataset, sampler
+    from k8s_amd.data.loader import is_resident
+
+    if name not in ("resnet50", "resnet_tiny"):
+        raise ValueError("a dataset directory can be read by the ResNet models only, not %r" % name)
+    ds = open_dataset(data["dir"], need=("train", "val") if need_val else ("train",))
+    kw = dict(image=image, augment=data.get("augment", "crop"), crop_pad=data.get("crop_pad", 4),
+              seed=data.get("seed", 0), rank=data.get("rank", 0), world=data.get("world", 1),
+              resident_gb=data.get("resident_gb", 4.0))
+    tr = ds.split("train")
+    Hs, Ws = (int(v) for v in tr.images.shape[1:3])
+    if not image:  # crop / none: the source size; a resize has no natural size, so the model's preset
+        kw["image"] = (224 if name == "resnet50" else 32) if kw["augment"] == "rrc" else min(Hs, Ws)
+    sampler.check_geometry(kw["augment"], Hs, Ws, kw["image"], kw["crop_pad"])
+    info = {"dir": data["dir"], "train": int(tr.images.shape[0]),
+            "val": int(ds.splits["val"].images.shape[0]) if "val" in ds.splits else 0, "source": [Hs, Ws],
+            "image": kw["image"], "augment": kw["augment"],
+            "resident": is_resident(tr.nbytes, kw["resident_gb"], torch.device(device)),
+            "steps_per_epoch": sampler.steps_per_epoch(int(tr.images.shape[0]), batch, kw["world"])}
+    return ds, kw, info
+
+
+def _resnet_on_dataset(name, store, device, batch, image, seed, grad_dtype, pad_to, data) -> Workload:
+    """A ResNet workload whose batches come from a dataset directory (see ``build``)."""
+    from k8s_amd.data.loader import Loader
+    from k8s_amd.models.resnet import resnet50, resnet_tiny
+
+    ds, kw, info = dataset_plan(name, device, batch, image, dict(data, seed=data.get("seed", seed)))
+    train = Loader(ds, "train", device, batch, train=True, **kw)  # raises DataError before the model is built
+    model = (resnet50 if name == "resnet50" else resnet_tiny)(store, ds.classes)
+    model = model.finalize(device, grad_dtype=grad_dtype, seed=seed, pad_to=pad_to)
+    evals = {}
+
+    def eval_batch(i, batch_=None):
+        n = batch_ or batch
+        if n not in evals:
+            evals[n] = Loader(ds, "val", device, n, train=False, **dict(kw, image=train.S))
+        return evals[n].batch(i)
+
+    def close():
+        for ld in [train] + list(evals.values()):
+            ld.close()
+
+    return Workload(name, model, store, train.batch, lambda b: K.cross_entropy(model(b[0]), b[1]), batch, "images",
+                    "sgd", 0.1, {"image": train.S, "classes": ds.classes, "data": info, "loader": train},
+                    evaluate=_resnet_evaluate(model), eval_batch=eval_batch, eval_state=lambda: model.fold_bn()[0], close=close)
+
+
 def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optional[int] = None,
           seed: int = 0, grad_dtype=torch.float32, fixed_batch: bool = True, pad_to: int = 64,
           data_seed: Optional[int] = None, mlm_every_token: bool = False, dropout: Optional[float] = None,
-          dropout_seed: Optional[int] = None) -> Workload:
+          dropout_seed: Optional[int] = None, data: Optional[Dict] = None) -> Workload:
     """Construct ``name`` on ``device`` with per-rank ``batch``. ``fixed_batch`` reuses one synthetic batch
     (what a throughput benchmark wants); otherwise every step draws a new one. ``dropout`` (BERT only): the hidden
     and attention-probability dropout of the training forward, seeded by ``dropout_seed`` (default ``seed``);
-    evaluation runs without it."""
+    evaluation runs without it. ``data`` (ResNet only): train on a dataset directory instead of synthetic batches --
+    ``{"dir", "augment", "crop_pad", "resident_gb", "seed", "rank", "world"}`` (``k8s_amd.data.loader.Loader``'s
+    arguments; only ``dir`` is required); ``classes`` then comes from the dataset's meta.json, ``batch(t)`` is batch
+    ``t`` of the ``train`` split and ``eval_batch(i)`` batch ``i`` of the ``val`` split."""
+    if data is not None and name not in ("resnet50", "resnet_tiny"):
+        raise ValueError("a dataset directory can be read by the ResNet models only, not %r" % name)
     if dropout and name not in ("bert_base", "bert_tiny"):
         raise ValueError("dropout is implemented for the BERT models only, not %r" % name)
     device = torch.device(device)
@@ -125,6 +198,8 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
         from k8s_amd.models.resnet import resnet50, resnet_tiny
 
         ncls = 1000 if name == "resnet50" else 10
+        if data is not None:
+            return _resnet_on_dataset(name, store, device, batch, image, seed, grad_dtype, pad_to, data)
         image = image or (224 if name == "resnet50" else 32)
         model = (resnet50(store, ncls) if name == "resnet50" else resnet_tiny(store, ncls))
         model = model.finalize(device, grad_dtype=grad_dtype, seed=seed, pad_to=pad_to)
@@ -133,15 +208,8 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
             x = torch.randn(n, image, image, 3, device=device, generator=g).to(dtype)
             return model.prepare_input(x).contiguous(), torch.randint(0, ncls, (n,), device=device, generator=g)
 
-        def evaluate(b, folded=None):
-            with torch.no_grad():
-                logits = model.forward_infer(b[0], folded) if EVAL_FOLDED else _plain_eval_forward(model, b[0])
-                loss, rank = K.xent_eval(logits, b[1])
-                return {"loss_sum": loss.double().sum(), "count": (b[1] != -100).sum(),
-                        "top1": (rank < 1).sum(), "top5": (rank < 5).sum()}
-
         return Workload(name, model, store, cached(make), lambda b: K.cross_entropy(model(b[0]), b[1]), batch,
-                        "images", "sgd", 0.1, {"image": image, "classes": ncls}, evaluate=evaluate,
+                        "images", "sgd", 0.1, {"image": image, "classes": ncls}, evaluate=_resnet_evaluate(model),
                         eval_batch=heldout(make), eval_state=lambda: model.fold_bn()[0])
 
     if name in ("bert_base", "bert_tiny"):

@@ -393,3 +393,56 @@ def lamb(p, m1, m2, pbf, r, lr, b1, b2, eps, w, step):
     p.sub_(lr * r * lamb_u(p, m1, m2, b1, b2, eps, w, step))
     if pbf is not None:
         pbf.copy_(p)
+
+
+# --------------------------------------------------------------------------- dataset augmentation (ops/data.py)
+def s2d_input(x8, pad: int = 3):
+    """[N, H, W, >= 4] -> [N, (H+2 pad)/2, (W+2 pad)/2, 16]: ``stem_s2d_input`` (channels 0..3 of every 2x2 block)."""
+    N, H, W = x8.shape[:3]
+    p = torch.nn.functional.pad(x8[..., :4], (0, 0, pad, pad, pad, pad))
+    Hs, Ws = (H + 2 * pad) // 2, (W + 2 * pad) // 2
+    return p.reshape(N, Hs, 2, Ws, 2, 4).permute(0, 1, 3, 2, 4, 5).reshape(N, Hs, Ws, 16).contiguous()
+
+
+def augment(src, table, a, b, S: int, layout: str = "nhwc8"):
+    """The definition of ``ops.data.augment`` in float64, rounded once to fp32 and once to bf16 (the CPU path and the
+    GPU kernel's oracle). ``src`` uint8 [M, Hs, Ws, 3]; ``table`` int32 [N, 6] rows (index, y0, x0, h, w, flip);
+    ``a``, ``b``: the fp32 values 1 / std_c and -mean_c / std_c. Output element (n, i, j, c), jj = S-1-j when flipped:
+    a row with h == w == S copies source pixel (y0+i, x0+jj), ``u8 * a_c + b_c`` (exact in float64, so the fp32
+    rounding is fmaf's), 0 outside the source; any other row resizes its box bilinearly to S x S (half-pixel centres,
+    indices clamped to the box) first. ``layout``: "nhwc8" [N, S, S, 8] or "s2d" [N, S/2+3, S/2+3, 16]; bf16."""
+    src = torch.as_tensor(src)
+    table = torch.as_tensor(table).cpu()
+    M, Hs, Ws = src.shape[:3]
+    N = table.shape[0]
+    a64 = torch.tensor([float(v) for v in a], dtype=torch.float32).double()
+    b64 = torch.tensor([float(v) for v in b], dtype=torch.float32).double()
+    out = torch.zeros(N, S, S, 8, dtype=torch.float64)
+    for n, (idx, y0, x0, h, w, flip) in enumerate(table.tolist()):
+        if not (0 <= idx < M and h >= 1 and w >= 1 and flip in (0, 1)):
+            raise ValueError("table row %d: bad index, box or flip" % n)
+        if h == S and w == S:
+            ys, ye, xs, xe = max(y0, 0), min(y0 + S, Hs), max(x0, 0), min(x0 + S, Ws)
+            img = torch.zeros(S, S, 3, dtype=torch.float64)
+            if ye > ys and xe > xs:
+                img[ys - y0:ye - y0, xs - x0:xe - x0] = src[idx, ys:ye, xs:xe].double() * a64 + b64
+        else:
+            if y0 < 0 or x0 < 0 or y0 + h > Hs or x0 + w > Ws:
+                raise ValueError("table row %d: resized box leaves the source" % n)
+            box = src[idx, y0:y0 + h, x0:x0 + w].double()
+            fy = ((torch.arange(S, dtype=torch.float64) + 0.5) * (h / S) - 0.5).clamp_(min=0)
+            fx = ((torch.arange(S, dtype=torch.float64) + 0.5) * (w / S) - 0.5).clamp_(min=0)
+            iy0 = fy.floor().long().clamp_(max=h - 1)
+            ix0 = fx.floor().long().clamp_(max=w - 1)
+            iy1, ix1 = (iy0 + 1).clamp_(max=h - 1), (ix0 + 1).clamp_(max=w - 1)
+            ly, lx = (fy - iy0).view(S, 1, 1), (fx - ix0).view(1, S, 1)
+            top = (1 - lx) * box[iy0][:, ix0] + lx * box[iy0][:, ix1]
+            bot = (1 - lx) * box[iy1][:, ix0] + lx * box[iy1][:, ix1]
+            img = ((1 - ly) * top + ly * bot) * a64 + b64
+        out[n, :, :, :3] = img.flip(1) if flip else img
+    out = out.float().to(torch.bfloat16)
+    if layout == "nhwc8":
+        return out
+    if layout != "s2d" or S % 2:
+        raise ValueError("layout must be 'nhwc8' or 's2d' (even S), got %r with S = %d" % (layout, S))
+    return s2d_input(out, 3)

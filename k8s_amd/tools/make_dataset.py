@@ -1,0 +1,103 @@
+"""Write a dataset directory in the trainer's format (``k8s_amd.data.dataset``). Nothing is downloaded.
+
+    python -m k8s_amd.tools.make_dataset --out DIR --toy [--seed 0] [--train 2048] [--val 256] [--classes 10]
+                                                   [--size 40]
+    python -m k8s_amd.tools.make_dataset --out DIR --cifar10-batches DIR_WITH_PICKLES
+
+``--toy``: a learnable set that is a pure function of its seed. Class k is a fixed random 5x5x3 uint8 prototype
+(numpy Philox key 7, the same for every seed) upscaled to ``--size`` (x8 to 40x40 by default, nearest cell at other
+sizes); Gaussian noise of sigma 48 is added and the result clipped to uint8; labels are uniform. meta: mean 127.5, std 64.
+
+``--cifar10-batches``: the CIFAR-10 "python version" pickles (``data_batch_1..5`` -> train, ``test_batch`` -> val; keys
+``data`` [10000, 3072] CHW uint8 and ``labels``) converted to NHWC, with CIFAR-10's per-channel mean and std.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import pickle
+import sys
+
+import numpy as np
+
+from k8s_amd.data.dataset import write_dataset
+
+TOY_PROTO_KEY, TOY_SIGMA = 7, 48.0
+CIFAR10_MEAN, CIFAR10_STD = [125.3, 123.0, 113.9], [63.0, 62.1, 66.7]
+
+
+def toy_prototypes(classes: int) -> np.ndarray:
+    """uint8 [classes, 5, 5, 3]: the first ``classes`` prototypes of the one fixed stream."""
+    g = np.random.Generator(np.random.Philox(key=TOY_PROTO_KEY))
+    return g.integers(0, 256, size=(classes, 5, 5, 3), dtype=np.uint8)
+
+
+def toy_split(seed: int, which: int, n: int, classes: int, size: int = 40):
+    """(uint8 images [n, size, size, 3], int64 labels [n]) of split number ``which`` for ``seed``."""
+    if size < 5:
+        raise ValueError("--size must be at least 5 (the prototypes are 5x5)")
+    g = np.random.Generator(np.random.Philox(np.random.SeedSequence([0x70F, int(seed), int(which)])))
+    labels = g.integers(0, classes, size=n, dtype=np.int64)
+    cell = np.arange(size) * 5 // size  # nearest prototype cell: x8 blocks at the default 40
+    up = toy_prototypes(classes)[:, cell][:, :, cell]
+    images = np.empty((n, size, size, 3), dtype=np.uint8)
+    for at in range(0, n, 256):  # bounded temporaries at large sizes
+        lab = labels[at:at + 256]
+        noise = g.normal(0.0, TOY_SIGMA, size=(len(lab), size, size, 3))
+        images[at:at + 256] = np.clip(np.rint(up[lab].astype(np.float64) + noise), 0, 255).astype(np.uint8)
+    return images, labels
+
+
+def make_toy(out: str, seed: int = 0, train: int = 2048, val: int = 256, classes: int = 10, size: int = 40) -> None:
+    write_dataset(out, classes, [127.5] * 3, [64.0] * 3,
+                  {"train": toy_split(seed, 0, train, classes, size), "val": toy_split(seed, 1, val, classes, size)})
+
+
+def read_cifar_batch(path: str):
+    with open(path, "rb") as f:
+        d = pickle.load(f, encoding="bytes")
+    get = lambda k: d[k] if k in d else d[k.encode()]  # noqa: E731 -- the original pickles have bytes keys
+    data = np.asarray(get("data"), dtype=np.uint8)
+    if data.ndim != 2 or data.shape[1] != 3072:
+        raise ValueError("%s: data must be [n, 3072]" % path)
+    return data.reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1), np.asarray(get("labels"), dtype=np.int64)
+
+
+def make_cifar10(out: str, src: str) -> None:
+    train = [os.path.join(src, "data_batch_%d" % i) for i in range(1, 6)]
+    train = [p for p in train if os.path.isfile(p)]
+    test = os.path.join(src, "test_batch")
+    if not train or not os.path.isfile(test):
+        raise FileNotFoundError("%s must hold data_batch_1..5 and test_batch" % src)
+    parts = [read_cifar_batch(p) for p in train]
+    splits = {"train": (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])),
+              "val": read_cifar_batch(test)}
+    write_dataset(out, 10, CIFAR10_MEAN, CIFAR10_STD, splits)
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m k8s_amd.tools.make_dataset", description=__doc__.split("\n")[0])
+    ap.add_argument("--out", required=True)
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--toy", action="store_true")
+    src.add_argument("--cifar10-batches", default=None, metavar="DIR")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--train", type=int, default=2048)
+    ap.add_argument("--val", type=int, default=256)
+    ap.add_argument("--classes", type=int, default=10)
+    ap.add_argument("--size", type=int, default=40)
+    a = ap.parse_args(argv)
+    try:
+        if a.toy:
+            make_toy(a.out, a.seed, a.train, a.val, a.classes, a.size)
+        else:
+            make_cifar10(a.out, a.cifar10_batches)
+    except (ValueError, OSError) as e:
+        print("error: %s" % e, file=sys.stderr)
+        return 1
+    print(a.out)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -20,6 +20,9 @@ process exit code (`/root/reference/pkg/trainer/training.go:45-73`):
   replica and it resumes from the latest checkpoint;
 * evaluation (``--eval-every N`` / ``--eval-only``): forward-only passes over held-out synthetic batches or the
   fixed training batch, an ``eval`` event (loss, top-1 / top-5 or perplexity) and ``eval/*`` TensorBoard scalars;
+* data: synthetic batches of the model's shape, or for the ResNet models ``--data-dir``: a dataset directory
+  (``k8s_amd.data``) whose ``train`` split feeds the fused augmentation kernel and whose ``val`` split is the
+  held-out evaluation data;
 * outputs (chief only): ``<logdir>/events.out.tfevents.*`` (TensorBoard),
   ``<logdir>/metrics.jsonl`` (one JSON record per logged step, plus
   ``start`` / ``step0`` / ``done`` events with wall-clock times so the
@@ -105,6 +108,16 @@ def parse(argv=None):
                          "recipe uses 0.1); masks are a function of (--seed, rank, step), so a resumed or graphed run "
                          "draws the same ones")
     ap.add_argument("--fresh-batches", action="store_true", help="draw a new synthetic batch every step")
+    ap.add_argument("--data-dir", default="",
+                    help="ResNet: train on this dataset directory (k8s_amd.tools.make_dataset writes the format) "
+                         "instead of synthetic batches; --eval-data heldout then reads its val split")
+    ap.add_argument("--augment", default="crop", choices=["crop", "rrc", "none"],
+                    help="--data-dir: random crop of the zero-padded source + flip, random-resized crop + flip, or "
+                         "the centred crop")
+    ap.add_argument("--crop-pad", type=int, default=4, help="--augment crop: zero padding around the source")
+    ap.add_argument("--data-resident-gb", type=float, default=4.0,
+                    help="--data-dir: a split up to this many GiB is uploaded once; a larger one is streamed batch "
+                         "by batch by a background thread (0: always streamed)")
     ap.add_argument("--accum-steps", type=int, default=1,
                     help="gradient accumulation: micro-batches of --batch per optimizer step (global batch = batch x "
                          "world x N). A step stays an optimizer step everywhere (--steps, warmup, logging, "
@@ -315,13 +328,7 @@ def _restore(a, w, opt, dev, chief: bool, world: int, metrics, psv=None, svc=Non
 
 def train(a) -> int:
     from k8s_amd.models.registry import build
-    from k8s_amd.ops.optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD
     from k8s_amd.parallel import dist as kdist
-    from k8s_amd.parallel.ddp import GradReducer
-    from k8s_amd.parallel.ps import ShardedParameterService
-    from k8s_amd.trainer.schedule import lr_at
-    from k8s_amd.utils import checkpoint as ckpt
-    from k8s_amd.utils.trace import Tracer, Watchdog
 
     t_start = time.time()
     t_proc = _process_start_time()
@@ -346,6 +353,12 @@ def train(a) -> int:
         config_error = "--dropout must be in [0, 1)"
     elif a.dropout > 0 and not a.model.startswith("bert"):
         config_error = "--dropout is implemented for the BERT models only, not %s" % a.model
+    elif a.data_dir and not a.model.startswith("resnet"):
+        config_error = "--data-dir holds images: it can be read by the ResNet models only, not %s" % a.model
+    elif a.data_dir and a.graph:
+        config_error = "--data-dir cannot be combined with --graph (a data step is not captured)"
+    elif a.data_dir and a.eval_data == "train":
+        config_error = "--data-dir evaluates its val split: not with --eval-data train"
     if config_error:
         print("error: %s" % config_error, file=sys.stderr, flush=True)
         return EXIT_PERMANENT
@@ -374,17 +387,50 @@ def train(a) -> int:
     zero = a.zero == "1"
     sharded = a.strategy == "ps" or (zero and world > 1)
     comm = a.grad_comm if a.grad_comm != "auto" else "fp32"
+    data = None
+    if a.data_dir:  # every check of the data configuration, before the model is built and the start event written
+        from k8s_amd.data import DataError
+        from k8s_amd.models.registry import dataset_plan
+
+        data = {"dir": a.data_dir, "augment": a.augment, "crop_pad": a.crop_pad, "resident_gb": a.data_resident_gb,
+                "seed": a.seed, "rank": rank, "world": world}
+        try:
+            data_info = dataset_plan(a.model, dev, batch, a.image, data, need_val=evaluating)[2]
+        except DataError as e:
+            print("error: %s" % e, file=sys.stderr, flush=True)
+            kdist.destroy()
+            return EXIT_PERMANENT
     metrics = _Metrics(a.logdir, chief)
     metrics.event(event="start", rank=rank, world=world, role=info.role, model=a.model, strategy=a.strategy,
                   device=str(dev), start_time=t_start, process_start_time=t_proc, zero1=bool(sharded and world > 1), grad_comm=comm,
                   optimizer=opt_name, lr_schedule=a.lr_schedule, batch=batch, dropout=a.dropout,
-                  accum_steps=a.accum_steps, global_batch=batch * world * a.accum_steps)
+                  accum_steps=a.accum_steps, global_batch=batch * world * a.accum_steps,
+                  **({"data": data_info} if data else {}))
 
     # the sharded parameter service needs the flat buffers divisible into world equal 64-aligned shards
     w = build(a.model, dev, batch, seq=a.seq, image=a.image, seed=a.seed, fixed_batch=not a.fresh_batches,
               pad_to=world * ALIGN if sharded else ALIGN, data_seed=a.seed * 7919 + rank,
               mlm_every_token=a.mlm_head == "every-token", dropout=a.dropout or None,
-              dropout_seed=a.seed * 7919 + rank)
+              dropout_seed=a.seed * 7919 + rank, data=data)
+    try:
+        return _train(a, w, info, dev, use_cuda, batch, opt_name, sharded, comm, metrics, tf_config, t_start)
+    finally:
+        if w.close is not None:  # the data loader's background thread, on every way out
+            w.close()
+
+
+def _train(a, w, info, dev, use_cuda, batch, opt_name, sharded, comm, metrics, tf_config, t_start) -> int:
+    from k8s_amd.ops.optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD
+    from k8s_amd.parallel import dist as kdist
+    from k8s_amd.parallel.ddp import GradReducer
+    from k8s_amd.parallel.ps import ShardedParameterService
+    from k8s_amd.trainer.schedule import lr_at
+    from k8s_amd.utils import checkpoint as ckpt
+    from k8s_amd.utils.trace import Tracer, Watchdog
+
+    rank, world = max(info.rank, 0), info.world_size
+    chief = rank == 0
+    epoch_steps = (w.meta.get("data") or {}).get("steps_per_epoch")
     lr = a.lr if a.lr is not None else w.lr
     if opt_name in ("sgd", "lars"):
         wd = 5e-5 if a.weight_decay is None else a.weight_decay
@@ -624,6 +670,8 @@ def train(a) -> int:
                     # lars / lamb: the per-tensor trust ratios of the latest step over the decaying slots (identical
                     # on every rank: they come from the all-reduced sums)
                     trust = (opt.trust_ratio_stats() if chief and opt_name in ("lars", "lamb") else None) or {}
+                    if epoch_steps:  # the epoch of the step's first batch
+                        extra["epoch"] = step * micro // epoch_steps
                     metrics.event(event="step", step=step, loss=loss_v, lr=cur_lr,
                                   **{"%s_per_sec" % w.unit: round(rate, 2)}, **extra, **trust)
                     metrics.scalars(step, {"loss": loss_v, "%s_per_sec" % w.unit: rate, "learning_rate": cur_lr,
@@ -658,6 +706,7 @@ def train(a) -> int:
     metrics.event(event="done", steps=a.steps, loss=loss_v, elapsed=time.time() - t_start, rank=rank,
                   weights_sum=float(w.store.master.double().sum().item()), gemm_fallbacks=dict(kgemm.FALLBACKS),
                   dropout_fallbacks=kattn.DROPOUT_FALLBACKS,
+                  **({"data": w.meta["loader"].info()} if "loader" in w.meta else {}),
                   peak_mem_gb=(round(torch.cuda.max_memory_allocated(w.store.master.device) / 2**30, 1)
                                if w.store.master.is_cuda else None))
     metrics.close()
