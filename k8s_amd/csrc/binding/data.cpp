@@ -1,4 +1,5 @@
-// Dataset entry points of k8s_amd._C: the fused augmentation kernel (kernels/augment.hip).
+// Dataset entry points of k8s_amd._C: the fused augmentation kernel (kernels/augment.hip) and the token batch kernels
+// (kernels/token_batch.hip).
 #include <string>
 
 #include "binding/common.h"
@@ -59,9 +60,88 @@ Tensor augment(Tensor src, Tensor table, std::vector<double> a, std::vector<doub
   return out;
 }
 
+long g_token_launches = 0;  // mlm_batch + causal_batch kernel launches, counted like g_augment_launches
+
+// The token array of a split: int32, or uint16 data passed as an int16 view (read unsigned). Returns true for uint16.
+bool check_token_src(const Tensor& src) {
+  check_cuda(src, "src");
+  TORCH_CHECK(src.scalar_type() == at::kInt || src.scalar_type() == at::kShort,
+              "src has dtype ", src.scalar_type(), ", expected int32 or (uint16 data viewed as) int16");
+  TORCH_CHECK(src.dim() == 1 && src.size(0) >= 1, "src must be a 1-D token array");
+  return src.scalar_type() == at::kShort;
+}
+
+void check_host_i64(const Tensor& t, int64_t cols, const char* name) {
+  TORCH_CHECK(t.device().is_cpu(), name, " must be a CPU tensor (it is validated on the host, then uploaded)");
+  check_dtype(t, at::kLong, name);
+  TORCH_CHECK(t.is_contiguous() && t.size(0) >= 1 && (cols ? t.dim() == 2 && t.size(1) == cols : t.dim() == 1), name,
+              " must be a contiguous int64 [N", cols ? ", 6]" : "]");
+}
+
+// src: the tokens on the GPU; table int64 [N, 6] on the host, rows (a0, la, b0, lb, n, ord); special (pad, cls, sep,
+// mask). Every row is validated here before anything is allocated or launched; then the table is uploaded through
+// pinned memory and the kernel (which clamps once more) runs on the current stream.
+std::vector<Tensor> mlm_batch(Tensor src, Tensor table, int64_t S, int64_t P, int64_t vocab,
+                              std::vector<int64_t> special, int64_t seed, int64_t stream) {
+  const bool u16 = check_token_src(src);
+  TORCH_CHECK(vocab >= 2 && vocab <= 0x7fffffffLL, "vocab must be in [2, 2^31 - 1], got ", vocab);
+  TORCH_CHECK(!u16 || vocab <= 65536, "uint16 tokens need vocab <= 65536, got ", vocab);
+  check_host_i64(table, 6, "table");
+  TORCH_CHECK(S >= 1 && S <= 512, "S must be in [1, 512], got ", S);
+  TORCH_CHECK(P >= 1 && P <= S, "P must be in [1, S], got ", P);
+  TORCH_CHECK(stream >= 0 && stream < (1 << 20), "stream out of range");
+  TORCH_CHECK(special.size() == 4, "special must be (pad, cls, sep, mask)");
+  for (int64_t v : special) TORCH_CHECK(v >= 0 && v < vocab, "special id ", v, " outside [0, vocab = ", vocab, ")");
+  const int64_t T = src.size(0), N = table.size(0);
+  TORCH_CHECK(N < (1L << 22), "mlm_batch: too many rows in one call");
+  const int64_t* t = table.data_ptr<int64_t>();
+  for (int64_t r = 0; r < N; ++r, t += 6) {
+    const int64_t a0 = t[0], la = t[1], b0 = t[2], lb = t[3], n = t[4], ord = t[5];
+    TORCH_CHECK(la >= 1 && lb >= 1 && la <= S && lb <= S && la + lb + 3 <= S, "table row ", r, ": lengths ", la, " + ",
+                lb, " + 3 must fit S = ", S, " with both segments non-empty");
+    TORCH_CHECK(a0 >= 0 && a0 <= T - la && b0 >= 0 && b0 <= T - lb, "table row ", r, ": a segment leaves the ", T,
+                " tokens of src");
+    TORCH_CHECK(n >= 1 && n <= P && n <= la + lb, "table row ", r, ": n = ", n, " must be in [1, min(P, la + lb)]");
+    TORCH_CHECK(ord >= 0, "table row ", r, ": negative ordinal");
+  }
+  const k8s_amd::TokSpecial sp{(int)special[0], (int)special[1], (int)special[2], (int)special[3]};
+  auto dtable = table.pin_memory().to(src.device(), /*non_blocking=*/true);
+  auto opt = src.options().dtype(at::kLong);
+  auto ids = torch::empty({N, S}, opt), types = torch::empty({N, S}, opt);
+  auto labels = torch::empty({N, P}, opt), positions = torch::empty({N, P}, opt);
+  ++g_token_launches;
+  launch_mlm_batch(src.data_ptr(), u16, T, dtable.data_ptr<int64_t>(), (int)N, (int)S, (int)P, (uint32_t)vocab, sp,
+                   (uint64_t)seed, (int)stream, ids.data_ptr<int64_t>(), types.data_ptr<int64_t>(),
+                   labels.data_ptr<int64_t>(), positions.data_ptr<int64_t>(), cur_stream());
+  return {ids, types, labels, positions};
+}
+
+// starts int64 [N] on the host: ids = src[start : start + S], labels = src[start + 1 : start + S + 1].
+std::vector<Tensor> causal_batch(Tensor src, Tensor starts, int64_t S) {
+  const bool u16 = check_token_src(src);
+  check_host_i64(starts, 0, "starts");
+  const int64_t T = src.size(0), N = starts.size(0);
+  TORCH_CHECK(S >= 1 && S < (1L << 24) && N * S < (1L << 31), "causal_batch: S or N * S out of range");
+  const int64_t* s = starts.data_ptr<int64_t>();
+  for (int64_t r = 0; r < N; ++r)
+    TORCH_CHECK(s[r] >= 0 && s[r] <= T - S - 1, "starts row ", r, ": window [", s[r], ", + ", S, " + 1) leaves the ", T,
+                " tokens of src");
+  auto dstarts = starts.pin_memory().to(src.device(), /*non_blocking=*/true);
+  auto opt = src.options().dtype(at::kLong);
+  auto ids = torch::empty({N, S}, opt), labels = torch::empty({N, S}, opt);
+  ++g_token_launches;
+  launch_causal_batch(src.data_ptr(), u16, T, dstarts.data_ptr<int64_t>(), (int)N, (int)S, ids.data_ptr<int64_t>(),
+                      labels.data_ptr<int64_t>(), cur_stream());
+  return {ids, labels};
+}
+
 }  // namespace
 
 void bind_data(pybind11::module_& m) {
+  m.def("mlm_batch", &mlm_batch, "src"_a, "table"_a, "S"_a, "P"_a, "vocab"_a, "special"_a, "seed"_a, "stream"_a = 0,
+        "assemble a BERT pretraining batch (ids, token types, MLM labels and positions) from a token array");
+  m.def("causal_batch", &causal_batch, "src"_a, "starts"_a, "S"_a, "gather causal-LM windows (ids, shifted labels)");
+  m.def("token_launches", [] { return g_token_launches; }, "token batch kernels launched by this process");
   m.def("augment", &augment, "src"_a, "table"_a, "a"_a, "b"_a, "S"_a, "layout"_a,
         "gather + crop / resize + flip + normalise a uint8 batch into the stem's bf16 input");
   m.def("augment_launches", [] { return g_augment_launches; }, "augment kernels launched by this process");

@@ -437,6 +437,19 @@ struct AugNorm {
 void launch_augment(const uint8_t* src, const int* table, int N, int M, int Hs, int Ws, int S, const AugNorm& nm,
                     bool s2d, uint16_t* out, hipStream_t st);
 
+// ---- token_batch.hip: a token batch in one launch. src: the token array, uint16 (u16) or int32 [Tn]; all outputs
+// int64. mlm_batch: table int64 [N][6] rows (a0, la, b0, lb, n, ord) -> ids / types [N][S], labels / positions
+// [N][P] of a BERT pretraining batch (1 <= P <= S <= 512); causal_batch: starts int64 [N] -> ids = src[start + j],
+// labels = src[start + j + 1], [N][S]. Every source index is clamped into [0, Tn).
+struct TokSpecial {
+  int pad, cls, sep, mask;
+};
+void launch_mlm_batch(const void* src, bool u16, long Tn, const long* table, int N, int S, int P, uint32_t vocab,
+                      const TokSpecial& sp, uint64_t seed, int stream, long* ids, long* types, long* labels,
+                      long* positions, hipStream_t st);
+void launch_causal_batch(const void* src, bool u16, long Tn, const long* starts, int N, int S, long* ids, long* labels,
+                         hipStream_t st);
+
 // ---- NHWC max pooling (pool.hip): idx = winning window position per output element (uint8)
 void launch_subsample_nhwc(const uint16_t* x, uint16_t* y, int N, int H, int W, int C, int s, hipStream_t st);
 void launch_maxpool_fwd(const uint16_t* x, uint16_t* y, uint8_t* idx, int N, int H, int W, int C, int Ho, int Wo,

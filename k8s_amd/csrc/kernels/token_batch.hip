@@ -1,0 +1,182 @@
+// Token batch assembly: a whole BERT pretraining batch (mlm_batch_kernel) or a causal-LM batch (causal_batch_kernel)
+// from the token array and a small host table, in one launch. Integer arithmetic only: ops/reference.py mlm_batch /
+// causal_batch are the same definitions in torch and match bit for bit.
+//
+// src    uint16 or int32 [T]   the split's tokens (or one staged batch of them)
+// table  int64 [N][6]          per sample (a0, la, b0, lb, n, ord), drawn on the host (data/token_sampler.py)
+//
+// Sample row, position j, L = la + lb + 3:
+//   tok[j]  = cls (0) | src[a0 + j - 1] (1 .. la) | sep (la + 1) | src[b0 + j - la - 2] (la + 2 .. la + lb + 1)
+//             | sep (L - 1) | pad (L ..)
+//   type[j] = 1 for la + 2 <= j <= L - 1, else 0
+//   keys    : philox_rowkey(seed, 0, 3 * stream + {0, 1, 2}, ord) = ksel, kdec, krep; G = 0x9E3779B1
+//   score[j]= mix32(ksel ^ j G); the n candidates (A and B positions) with the smallest (score, j) are selected;
+//             a selected j's slot = selected positions below it: positions[slot] = j, labels[slot] = tok[j];
+//             slots >= n: position 0, label -100
+//   id[j]   = selected: u = mix32(kdec ^ j G) < 0.8 2^32 ? mask : u < 0.9 2^32 ? umulhi(mix32(krep ^ j G), vocab)
+//             : tok[j]; unselected: tok[j]
+//
+// One wave per sample, four samples per 256-thread block. Lane l holds positions l, l + 64, ... (at most 8 at
+// S <= 512), so a segment's token loads and the int64 stores are consecutive across the wave. The three Philox calls
+// are wave-uniform. Scores go to the wave's LDS row; each lane then ranks its positions in one loop over the
+// candidates of that row -- every lane reads the same address, a broadcast -- S^2 / 64 compares per lane. Slots
+// come from one __ballot per 64-position chunk and __popcll of the lower lanes and the earlier chunks. Stores: the
+// unused slots get their defaults, the selected lanes scatter theirs; plain vector stores, no atomics.
+//
+// Every source index is clamped into [0, T) and every length into the row here as well as validated on the host: no
+// table content reads outside src or writes outside the outputs.
+#include <stdexcept>
+
+#include "common.h"
+#include "launchers.h"
+#include "rng.h"
+
+namespace k8s_amd {
+
+constexpr int kTokMaxS = 512, kTokChunks = kTokMaxS / 64;
+constexpr uint32_t kTokG = 0x9E3779B1u;
+constexpr uint32_t kTokMask80 = 3435973837u;  // floor(0.8 * 2^32 + 0.5)
+constexpr uint32_t kTokMask90 = 3865470566u;  // floor(0.9 * 2^32 + 0.5)
+
+__device__ __forceinline__ long tok_clamp(long v, long hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+template <typename T>
+__device__ __forceinline__ int tok_load(const T* __restrict__ src, long i, long Tn) {
+  return (int)src[tok_clamp(i, Tn - 1)];  // uint16_t widens unsigned
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) mlm_batch_kernel(const T* __restrict__ src, long Tn,
+                                                        const long* __restrict__ table, int N, int S, int P,
+                                                        uint32_t vocab, TokSpecial sp, uint64_t seed, int stream,
+                                                        long* __restrict__ ids, long* __restrict__ types,
+                                                        long* __restrict__ labels, long* __restrict__ positions) {
+  __shared__ uint32_t score_lds[4][kTokMaxS];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int sample = blockIdx.x * 4 + wave;
+  const bool live = sample < N;  // wave-uniform; a dead wave still meets the barrier
+  const long* row = table + (long)(live ? sample : 0) * 6;
+  const long a0 = row[0], b0 = row[2];
+  const int la = (int)tok_clamp(row[1], S), lb = (int)tok_clamp(row[3], S - la);
+  const int n = (int)tok_clamp(row[4], P);
+  const uint64_t ord = (uint64_t)row[5];
+  const int L = la + lb + 3;
+  const uint32_t ksel = philox_rowkey(seed, 0, 3u * stream + 0u, ord);
+  const uint32_t kdec = philox_rowkey(seed, 0, 3u * stream + 1u, ord);
+  const uint32_t krep = philox_rowkey(seed, 0, 3u * stream + 2u, ord);
+  uint32_t* score = score_lds[wave];
+
+  int tok[kTokChunks];
+  uint32_t sc[kTokChunks];
+  bool cand[kTokChunks];
+#pragma unroll
+  for (int c = 0; c < kTokChunks; ++c) {
+    const int j = c * 64 + lane;
+    const bool inA = j >= 1 && j <= la, inB = j >= la + 2 && j <= la + lb + 1;
+    int t = sp.pad;
+    if (j < S) {  // wave-uniform per chunk except in the last one
+      if (inA) t = tok_load(src, a0 + j - 1, Tn);
+      if (inB) t = tok_load(src, b0 + j - la - 2, Tn);
+    }
+    if (j == 0) t = sp.cls;
+    if (j == la + 1 || j == L - 1) t = sp.sep;
+    tok[c] = t;
+    cand[c] = (inA || inB) && j < S;
+    sc[c] = drop_mix32(ksel ^ ((uint32_t)j * kTokG));
+    if (j < S) score[j] = sc[c];
+  }
+  __syncthreads();
+
+  // rank[c] = candidates k with (score[k], k) < (score[j], j): two runs of k, the A and the B positions
+  int rank[kTokChunks];
+#pragma unroll
+  for (int c = 0; c < kTokChunks; ++c) rank[c] = 0;
+  const int endA = min(la, S - 1), endB = min(la + lb + 1, S - 1);
+  for (int k = 1; k <= endB; ++k) {
+    if (k == endA + 1) {  // skip [SEP] between the runs (and everything past a clamped A)
+      k = la + 1;
+      continue;
+    }
+    const uint32_t s = score[k];
+#pragma unroll
+    for (int c = 0; c < kTokChunks; ++c) {
+      const int j = c * 64 + lane;
+      rank[c] += (s < sc[c] || (s == sc[c] && k < j)) ? 1 : 0;
+    }
+  }
+
+  int base = 0;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  long* lab = labels + (long)sample * P;
+  long* pos = positions + (long)sample * P;
+#pragma unroll
+  for (int c = 0; c < kTokChunks; ++c) {
+    const int j = c * 64 + lane;
+    const bool sel = cand[c] && rank[c] < n;
+    const unsigned long long bal = __ballot(sel);
+    const int slot = base + __popcll(bal & below);
+    base += __popcll(bal);
+    int id = tok[c];
+    if (sel) {
+      const uint32_t jg = (uint32_t)j * kTokG;
+      const uint32_t u = drop_mix32(kdec ^ jg);
+      if (u < kTokMask80)
+        id = sp.mask;
+      else if (u < kTokMask90)
+        id = (int)__umulhi(drop_mix32(krep ^ jg), vocab);
+      if (live && slot < P) {
+        lab[slot] = tok[c];
+        pos[slot] = j;
+      }
+    }
+    if (live && j < S) {
+      ids[(long)sample * S + j] = id;
+      types[(long)sample * S + j] = (j >= la + 2 && j <= L - 1) ? 1 : 0;
+    }
+  }
+  if (live)
+    for (int p = base + lane; p < P; p += 64) {  // the slots no selected position took
+      lab[p] = -100;
+      pos[p] = 0;
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) causal_batch_kernel(const T* __restrict__ src, long Tn,
+                                                           const long* __restrict__ starts, int S, int total,
+                                                           long* __restrict__ ids, long* __restrict__ labels) {
+  const int e = blockIdx.x * 256 + threadIdx.x;  // output element (n, j)
+  if (e >= total) return;
+  const long at = starts[e / S] + e % S;
+  ids[e] = tok_load(src, at, Tn);
+  labels[e] = tok_load(src, at + 1, Tn);
+}
+
+void launch_mlm_batch(const void* src, bool u16, long Tn, const long* table, int N, int S, int P, uint32_t vocab,
+                      const TokSpecial& sp, uint64_t seed, int stream, long* ids, long* types, long* labels,
+                      long* positions, hipStream_t st) {
+  if (N < 1 || Tn < 1 || S < 1 || S > kTokMaxS || P < 1 || P > S || vocab < 2 || stream < 0)
+    throw std::runtime_error("mlm_batch: bad shape");
+  const dim3 grid(cdiv(N, 4)), block(256);
+  if (u16)
+    hipLaunchKernelGGL(mlm_batch_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)src, Tn, table, N, S, P, vocab,
+                       sp, seed, stream, ids, types, labels, positions);
+  else
+    hipLaunchKernelGGL(mlm_batch_kernel<int>, grid, block, 0, st, (const int*)src, Tn, table, N, S, P, vocab, sp, seed,
+                       stream, ids, types, labels, positions);
+}
+
+void launch_causal_batch(const void* src, bool u16, long Tn, const long* starts, int N, int S, long* ids, long* labels,
+                         hipStream_t st) {
+  const long total = (long)N * S;
+  if (N < 1 || Tn < 1 || S < 1 || total >= (1L << 31)) throw std::runtime_error("causal_batch: bad shape");
+  const dim3 grid(cdiv(total, 256)), block(256);
+  if (u16)
+    hipLaunchKernelGGL(causal_batch_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)src, Tn, starts, S,
+                       (int)total, ids, labels);
+  else
+    hipLaunchKernelGGL(causal_batch_kernel<int>, grid, block, 0, st, (const int*)src, Tn, starts, S, (int)total, ids,
+                       labels);
+}
+
+}  // namespace k8s_amd

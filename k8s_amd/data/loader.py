@@ -33,11 +33,14 @@ class _Streamer:
     """The background gather + upload of streamed mode. ``get(key, rows)`` returns the device buffer that holds the
     source rows of request ``key`` and starts on ``next_key``; ``done(slot)`` marks the buffer's consumer launched."""
 
-    def __init__(self, images: np.ndarray, n: int, device, rows_of):
+    def __init__(self, images: np.ndarray, n: int, device, rows_of, gather=None, shape=None, dtype=torch.uint8):
+        """``gather(rows, out)`` (default: ``np.take`` of ``images``' rows) fills the pinned numpy buffer ``out`` of
+        ``shape`` (default: ``n`` source images) from what ``rows_of(key)`` returned."""
         self.images, self.rows_of, self.device = images, rows_of, device
-        shape = (n,) + tuple(images.shape[1:])
-        self.pinned = [torch.empty(shape, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self.staged = [torch.empty(shape, dtype=torch.uint8, device=device) for _ in range(2)]
+        self.gather = gather or (lambda rows, out: np.take(self.images, rows, axis=0, out=out, mode="clip"))
+        shape = shape or ((n,) + tuple(images.shape[1:]))
+        self.pinned = [torch.empty(shape, dtype=dtype).pin_memory() for _ in range(2)]
+        self.staged = [torch.empty(shape, dtype=dtype, device=device) for _ in range(2)]
         self.copied = [torch.cuda.Event() for _ in range(2)]
         self.consumed = [torch.cuda.Event() for _ in range(2)]
         self.stream = torch.cuda.Stream(device)
@@ -51,9 +54,9 @@ class _Streamer:
         rows = self.rows_of(key)
         self.copied[slot].synchronize()  # the pinned buffer's previous upload has left it
         t0 = time.perf_counter()
-        np.take(self.images, rows, axis=0, out=self.pinned[slot].numpy(), mode="clip")
+        self.gather(rows, self.pinned[slot].numpy())
         self.gather_s += time.perf_counter() - t0
-        self.gather_bytes += self.pinned[slot].numel()
+        self.gather_bytes += self.pinned[slot].numel() * self.pinned[slot].element_size()
         with torch.cuda.stream(self.stream):
             self.stream.wait_event(self.consumed[slot])  # the kernel that read this device buffer last
             self.staged[slot].copy_(self.pinned[slot], non_blocking=True)

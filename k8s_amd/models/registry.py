@@ -3,10 +3,12 @@
 Every workload the trainer (``python -m k8s_amd.trainer``) and the benches
 can run, at the exact BASELINE.json shapes plus small variants for CPU tests.
 Data is synthetic by default (random images / token ids of the named shape): the
-reference's workloads are external TF programs. The ResNet workloads can also
-read a dataset directory (``build(..., data=...)``, ``k8s_amd.data``): batches
-then come from its ``train`` split through the fused augmentation kernel and
-held-out batches from its ``val`` split.
+reference's workloads are external TF programs. Every workload can also read a
+dataset directory (``build(..., data=...)``, ``k8s_amd.data``): batches then
+come from its ``train`` split through a fused batch kernel (augmentation for
+the ResNet models and an image directory; MLM or causal batch assembly for the
+BERT and Llama models and a token directory) and held-out batches from its
+``val`` split.
 """
 from __future__ import annotations
 
@@ -79,11 +81,10 @@ def _resnet_evaluate(model):
 def dataset_plan(name: str, device, batch: int, image: Optional[int], data: Dict, need_val: bool = False):
     """(dataset, Loader keyword arguments, description) of ``build(name, ..., data=data)``, with every check of the
     configuration made (``DataError``): what the trainer's ``start`` event reports before the model is built."""
-    from k8s_amd.data import open_dataset, sampler
+    from k8s_amd.data import dataset_kind, open_dataset, sampler
     from k8s_amd.data.loader import is_resident
 
-    if name not in ("resnet50", "resnet_tiny"):
-        raise ValueError("a dataset directory can be read by the ResNet models only, not %r" % name)
+    check_data_kind(name, dataset_kind(data["dir"]))
     ds = open_dataset(data["dir"], need=("train", "val") if need_val else ("train",))
     kw = dict(image=image, augment=data.get("augment", "crop"), crop_pad=data.get("crop_pad", 4),
               seed=data.get("seed", 0), rank=data.get("rank", 0), world=data.get("world", 1),
@@ -99,6 +100,99 @@ def dataset_plan(name: str, device, batch: int, image: Optional[int], data: Dict
             "resident": is_resident(tr.nbytes, kw["resident_gb"], torch.device(device)),
             "steps_per_epoch": sampler.steps_per_epoch(int(tr.images.shape[0]), batch, kw["world"])}
     return ds, kw, info
+
+
+def check_data_kind(name: str, kind: str) -> None:
+    """An image directory feeds the ResNet models and a token directory the BERT and Llama models, nothing else."""
+    if name not in MODELS:
+        raise ValueError("unknown model %r (choose from %s)" % (name, ", ".join(MODELS)))
+    images = name in ("resnet50", "resnet_tiny")
+    if kind == "images" and not images:
+        raise ValueError("an image dataset directory can be read by the ResNet models only, not %r" % name)
+    if kind == "tokens" and images:
+        raise ValueError("a token dataset directory can be read by the BERT and Llama models only, not %r" % name)
+
+
+def token_config(name: str):
+    if name in ("bert_base", "bert_tiny"):
+        from k8s_amd.models import bert as M
+
+        return M.BERT_BASE if name == "bert_base" else M.BERT_TINY
+    from k8s_amd.models import llama as M
+
+    return {"llama3_8b": M.LLAMA3_8B, "llama_1b": M.LLAMA_1B, "llama_tiny": M.LLAMA_TINY}[name]
+
+
+def default_seq(name: str) -> int:
+    return {"bert_base": 128, "bert_tiny": 32, "llama_tiny": 64}.get(name, 4096)
+
+
+def token_dataset_plan(name: str, device, batch: int, seq: Optional[int], data: Dict, need_val: bool = False,
+                       mlm_every_token: bool = False):
+    """``dataset_plan`` for the BERT and Llama models and a token directory: (dataset, TokenLoader keyword arguments,
+    description), with every check of the configuration made (``DataError``)."""
+    from k8s_amd.data import DataError, dataset_kind, open_token_dataset
+    from k8s_amd.data import token_sampler as ts
+    from k8s_amd.data.loader import is_resident
+    from k8s_amd.ops.reference import MLM_MAX_SEQ
+
+    check_data_kind(name, dataset_kind(data["dir"]))
+    bert = name.startswith("bert")
+    cfg = token_config(name)
+    seq = int(seq or default_seq(name))
+    if seq > cfg.max_position or (bert and seq > MLM_MAX_SEQ):
+        raise DataError("--seq %d exceeds %s" % (seq, "the model's max_position = %d" % cfg.max_position
+                                                 if seq > cfg.max_position else
+                                                 "the %d positions the MLM batch kernel assembles" % MLM_MAX_SEQ))
+    if bert and mlm_every_token:
+        raise DataError("a token dataset yields the masked-position format: not with --mlm-head every-token")
+    ds = open_token_dataset(data["dir"], need=("train", "val") if need_val else ("train",), pairs=bert)
+    if ds.vocab > cfg.vocab_size:
+        raise DataError("dataset %s: vocab = %d exceeds %s's vocab_size = %d" % (ds.path, ds.vocab, name,
+                                                                                cfg.vocab_size))
+    kw = dict(seq=seq, kind="bert" if bert else "llama", max_predictions=cfg.max_predictions if bert else 1,
+              seed=data.get("seed", 0), rank=data.get("rank", 0), world=data.get("world", 1),
+              resident_gb=data.get("resident_gb", 4.0))
+    tr = ds.split("train")
+    if bert:
+        ts.check_seq(seq, kw["max_predictions"])
+        items, what = tr.G, "segments"
+    else:
+        items, what = ts.windows(tr.T, seq), "windows of %d tokens" % seq
+    E = ts.steps_per_epoch(items, batch, kw["world"], what)
+    pad_fraction = 0.0
+    if bert:  # the first epoch's first batch, from the host table alone
+        idx, ords = ts.train_items(kw["seed"], 0, kw["rank"], kw["world"], batch, items)
+        lens = ts.pair_rows(tr.segments, tr.docs, idx, ords, kw["seed"], seq, kw["max_predictions"])[2]
+        pad_fraction = round(float(1.0 - lens.mean() / seq), 4)
+    size = lambda sp: {"tokens": sp.T, "segments": sp.G, "documents": sp.D}  # noqa: E731
+    info = {"dir": data["dir"], "kind": "tokens", "vocab": ds.vocab, "train": size(tr),
+            "val": size(ds.splits["val"]) if "val" in ds.splits else None, "seq": seq,
+            "resident": is_resident(tr.nbytes, kw["resident_gb"], torch.device(device)), "steps_per_epoch": E,
+            "pad_fraction": pad_fraction}
+    return ds, kw, info
+
+
+def _token_loaders(name, device, batch, seq, seed, data, mlm_every_token):
+    """(training TokenLoader, eval_batch, close, description) of a token model on a dataset directory."""
+    from k8s_amd.data.token_loader import TokenLoader
+
+    ds, kw, info = token_dataset_plan(name, device, batch, seq, dict(data, seed=data.get("seed", seed)),
+                                      mlm_every_token=mlm_every_token)
+    train = TokenLoader(ds, "train", device, batch, train=True, **kw)
+    evals = {}
+
+    def eval_batch(i, batch_=None):
+        n = batch_ or batch
+        if n not in evals:
+            evals[n] = TokenLoader(ds, "val", device, n, train=False, **kw)
+        return evals[n].batch(i)
+
+    def close():
+        for ld in [train] + list(evals.values()):
+            ld.close()
+
+    return train, eval_batch, close, info
 
 
 def _resnet_on_dataset(name, store, device, batch, image, seed, grad_dtype, pad_to, data) -> Workload:
@@ -134,12 +228,15 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
     """Construct ``name`` on ``device`` with per-rank ``batch``. ``fixed_batch`` reuses one synthetic batch
     (what a throughput benchmark wants); otherwise every step draws a new one. ``dropout`` (BERT only): the hidden
     and attention-probability dropout of the training forward, seeded by ``dropout_seed`` (default ``seed``);
-    evaluation runs without it. ``data`` (ResNet only): train on a dataset directory instead of synthetic batches --
+    evaluation runs without it. ``data``: train on a dataset directory instead of synthetic batches --
     ``{"dir", "augment", "crop_pad", "resident_gb", "seed", "rank", "world"}`` (``k8s_amd.data.loader.Loader``'s
-    arguments; only ``dir`` is required); ``classes`` then comes from the dataset's meta.json, ``batch(t)`` is batch
-    ``t`` of the ``train`` split and ``eval_batch(i)`` batch ``i`` of the ``val`` split."""
-    if data is not None and name not in ("resnet50", "resnet_tiny"):
-        raise ValueError("a dataset directory can be read by the ResNet models only, not %r" % name)
+    arguments, or without the two augmentation keys ``TokenLoader``'s; only ``dir`` is required). The directory's
+    kind must fit the model: images for ResNet (``classes`` then comes from its meta.json), tokens for BERT and Llama.
+    ``batch(t)`` is batch ``t`` of the ``train`` split and ``eval_batch(i)`` batch ``i`` of the ``val`` split."""
+    if data is not None:
+        from k8s_amd.data import dataset_kind
+
+        check_data_kind(name, dataset_kind(data["dir"]))
     if dropout and name not in ("bert_base", "bert_tiny"):
         raise ValueError("dropout is implemented for the BERT models only, not %r" % name)
     device = torch.device(device)
@@ -169,7 +266,10 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
             try:
                 with torch.no_grad():
                     count = (labels_of(b) != -100).sum()
-                    return {"loss_sum": loss_of(b).double() * count.double(), "count": count}
+                    # a batch without a labelled row (past the end of a held-out split) adds exactly nothing,
+                    # whatever its mean over no rows is
+                    total = loss_of(b).double() * count.double()
+                    return {"loss_sum": torch.where(count > 0, total, torch.zeros_like(total)), "count": count}
             finally:
                 if model is not None:
                     model.train(was)
@@ -222,9 +322,16 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
             cfg = dataclasses.replace(cfg, max_predictions=0)
         if dropout:
             cfg = dataclasses.replace(cfg, hidden_dropout=float(dropout), attention_dropout=float(dropout))
-        seq = seq or (128 if name == "bert_base" else 32)
+        seq = seq or default_seq(name)
+        if data is not None:  # raises DataError before the model is built
+            train, eval_batch, close, info = _token_loaders(name, device, batch, seq, seed, data, mlm_every_token)
         model = M.BertForPreTraining(store, cfg).finalize(device, grad_dtype=grad_dtype, seed=seed, pad_to=pad_to)
         model.drop_state = K.DropoutState(seed if dropout_seed is None else dropout_seed, device)
+        if data is not None:  # batches are (ids, types, labels, nsp, positions, kv_lens): forward's positional order
+            return Workload(name, model, store, train.batch, lambda b: model(*b, dtype=dtype)[0], batch * seq,
+                            "tokens", "adam", 1e-4, {"seq": seq, "data": info, "loader": train},
+                            evaluate=token_eval(lambda b: model(*b, dtype=dtype)[0], lambda b: b[2], model),
+                            eval_batch=eval_batch, close=close)
 
         def make(n=batch, g=gen):
             return M.synthetic_batch(cfg, n, seq, device, generator=g)
@@ -238,8 +345,15 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
         from k8s_amd.models import llama as M
 
         cfg = {"llama3_8b": M.LLAMA3_8B, "llama_1b": M.LLAMA_1B, "llama_tiny": M.LLAMA_TINY}[name]
-        seq = seq or (4096 if name != "llama_tiny" else 64)
+        seq = seq or default_seq(name)
+        if data is not None:
+            train, eval_batch, close, info = _token_loaders(name, device, batch, seq, seed, data, False)
         model = M.LlamaForCausalLM(store, cfg).finalize(device, grad_dtype=grad_dtype, seed=seed, pad_to=pad_to)
+        if data is not None:
+            return Workload(name, model, store, train.batch, lambda b: model(*b, dtype=dtype), batch * seq, "tokens",
+                            "adam", 3e-4, {"seq": seq, "data": info, "loader": train},
+                            evaluate=token_eval(lambda b: model(*b, dtype=dtype), lambda b: b[1]),
+                            eval_batch=eval_batch, close=close)
 
         def make(n=batch, g=gen):
             return M.synthetic_batch(cfg, n, seq, device, generator=g)

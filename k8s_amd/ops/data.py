@@ -1,9 +1,14 @@
-"""Dataset ops: the fused batch-assembly kernel (``csrc/kernels/augment.hip``).
+"""Dataset ops: the fused batch-assembly kernels (``csrc/kernels/augment.hip``, ``csrc/kernels/token_batch.hip``).
 
 ``augment`` turns N rows of an int32 table into the stem's input in one pass over the output: gather the source image,
 crop (zero padded) or resize (bilinear) to S x S, flip, normalise, round to bf16 and lay out as "nhwc8" or as the
 space-to-depth image "s2d" that ``stem_conv_s2d`` reads. A uint8 ``src`` on the GPU runs the HIP kernel; one on the
 host runs ``ops.reference.augment``, the same definition in torch (float64), which is also the kernel's oracle.
+
+``mlm_batch`` turns N rows of an int64 table into a BERT pretraining batch in one launch: ``[CLS] A [SEP] B [SEP] pad``,
+token types, exactly ``n`` masked positions drawn without replacement from a counter generator, the 80 / 10 / 10 rule
+and the compacted [N, P] labels and positions. ``causal_batch`` gathers causal-LM windows. Both are integer
+arithmetic: the GPU kernels match ``ops.reference.mlm_batch`` / ``causal_batch`` (the CPU path) bit for bit.
 """
 from __future__ import annotations
 
@@ -34,3 +39,36 @@ def augment(src: torch.Tensor, table: torch.Tensor, a, b, S: int, layout: str = 
     if src.is_cuda:
         return _load_ext().augment(src, table, [float(v) for v in a], [float(v) for v in b], int(S), layout)
     return ref.augment(src, table, a, b, int(S), layout)
+
+
+def token_launches() -> int:
+    """Token batch kernels (``mlm_batch``, ``causal_batch``) this process has launched (a rejected call launches
+    none)."""
+    return int(_load_ext().token_launches())
+
+
+def _seed64(seed: int) -> int:
+    """Any 64-bit seed as the int64 with the same bits."""
+    v = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def mlm_batch(src: torch.Tensor, table: torch.Tensor, S: int, P: int, vocab: int, special, seed: int,
+              stream: int = 0):
+    """``src``: the 1-D token array, int32 or uint16 data as an int16 view (read unsigned); ``table`` int64 [N, 6] on
+    the host, rows (a0, la, b0, lb, n, ord); ``special`` = (pad, cls, sep, mask); ``stream``: 0 training, 1
+    evaluation (separate generator sites). Returns (ids [N, S], token_types [N, S], labels [N, P], positions [N, P]),
+    int64 on ``src``'s device. The GPU binding validates every table row on the host before anything is launched and
+    raises on the first bad one."""
+    if src.is_cuda:
+        return tuple(_load_ext().mlm_batch(src, table, int(S), int(P), int(vocab), [int(v) for v in special],
+                                           _seed64(seed), int(stream)))
+    return ref.mlm_batch(src, table, int(S), int(P), int(vocab), special, _seed64(seed), int(stream))
+
+
+def causal_batch(src: torch.Tensor, starts: torch.Tensor, S: int):
+    """``starts`` int64 [N] on the host: (ids, labels) int64 [N, S] with ids = src[start : start + S] and labels the
+    same window one token later; ``0 <= start`` and ``start + S + 1 <= len(src)`` are checked before the launch."""
+    if src.is_cuda:
+        return tuple(_load_ext().causal_batch(src, starts, int(S)))
+    return ref.causal_batch(src, starts, int(S))

@@ -446,3 +446,114 @@ def augment(src, table, a, b, S: int, layout: str = "nhwc8"):
     if layout != "s2d" or S % 2:
         raise ValueError("layout must be 'nhwc8' or 's2d' (even S), got %r with S = %d" % (layout, S))
     return s2d_input(out, 3)
+
+
+# --------------------------------------------------------------------------- token batches (ops/data.py)
+#   tok / type: [CLS] A [SEP] B [SEP] pad; keys = philox rowkey(seed, step 0, site 3 * stream + {0, 1, 2}, row ord)
+#   score[j] = mix32(ksel ^ (j * G)); the n candidates with the smallest (score, j) are selected
+#   id[j] = u < 0.8 2^32 ? mask : u < 0.9 2^32 ? (mix32(krep ^ j G) * vocab) >> 32 : tok[j], u = mix32(kdec ^ j G)
+TOKEN_G = 0x9E3779B1
+MLM_MASK_THR = 3435973837   # floor(0.8 * 2^32 + 0.5)
+MLM_RANDOM_THR = 3865470566  # floor(0.9 * 2^32 + 0.5)
+MLM_MAX_SEQ = 512
+
+
+def _mix32(x):
+    x = x ^ (x >> 16)
+    x = _mul32(x, 0x7FEB352D)
+    x = x ^ (x >> 15)
+    x = _mul32(x, 0x846CA68B)
+    return x ^ (x >> 16)
+
+
+def _token_values(src, idx):
+    """int64 tokens ``src[idx]``: ``src`` int32 / int64, or uint16 data (numpy uint16 or an int16 view, read
+    unsigned)."""
+    v = src[idx].to(torch.int64)
+    return v & 0xFFFF if src.dtype == torch.int16 else v
+
+
+def mlm_keys(seed: int, stream: int, ords):
+    """(ksel, kdec, krep): int64 tensors of 32-bit values, ``ords``' shape."""
+    return tuple(dropout_rowkey((seed, 0), 3 * int(stream) + i, ords) for i in range(3))
+
+
+def mlm_scores(seed: int, stream: int, ords, S: int):
+    """Selection scores [len(ords), S] (32-bit values in int64) of the positions 0 .. S - 1."""
+    ords = torch.as_tensor(ords, dtype=torch.int64)
+    jg = _mul32(torch.arange(S, dtype=torch.int64, device=ords.device), TOKEN_G)
+    return _mix32(mlm_keys(seed, stream, ords)[0].unsqueeze(1) ^ jg)
+
+
+def check_mlm_table(table, T: int, S: int, P: int, vocab: int, special, u16: bool = False) -> None:
+    """The checks of the GPU binding, on the host; raises ValueError on the first bad row."""
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 6 or table.shape[0] < 1:
+        raise ValueError("table must be int64 [N, 6]")
+    if not 1 <= S <= MLM_MAX_SEQ or not 1 <= P <= S:
+        raise ValueError("S must be in [1, %d] and P in [1, S], got S = %d, P = %d" % (MLM_MAX_SEQ, S, P))
+    if not 2 <= vocab <= 2 ** 31 - 1 or (u16 and vocab > 65536):
+        raise ValueError("vocab must be in [2, 2^31 - 1] (uint16 tokens: <= 65536), got %d" % vocab)
+    if len(special) != 4 or any(not 0 <= int(v) < vocab for v in special):
+        raise ValueError("special must be four ids (pad, cls, sep, mask) below vocab")
+    a0, la, b0, lb, n, ord_ = table.unbind(1)
+    bad = ((la < 1) | (lb < 1) | (la > S) | (lb > S) | (la + lb + 3 > S) | (a0 < 0) | (a0 > T - la) | (b0 < 0)
+           | (b0 > T - lb) | (n < 1) | (n > P) | (n > la + lb) | (ord_ < 0))
+    if bool(bad.any()):
+        r = int(bad.nonzero()[0])
+        raise ValueError("table row %d: %s is not a valid (a0, la, b0, lb, n, ord) for T = %d, S = %d, P = %d"
+                         % (r, tuple(table[r].tolist()), T, S, P))
+
+
+def mlm_batch(src, table, S: int, P: int, vocab: int, special, seed: int, stream: int = 0):
+    """The definition of ``ops.data.mlm_batch`` in torch integer ops (the CPU path and the GPU kernel's oracle; it
+    runs on ``src``'s device). ``src``: the 1-D token array; ``table`` int64 [N, 6] rows (a0, la, b0, lb, n, ord);
+    ``special`` = (pad, cls, sep, mask). Returns (ids [N, S], token_types [N, S], labels [N, P], positions [N, P]),
+    int64."""
+    src = torch.as_tensor(src)
+    table = torch.as_tensor(table)
+    S, P, vocab = int(S), int(P), int(vocab)
+    T = int(src.shape[0])
+    check_mlm_table(table.cpu(), T, S, P, vocab, special, u16=src.dtype == torch.int16)
+    dev = src.device
+    pad, cls, sep, mask = (int(v) for v in special)
+    a0, la, b0, lb, n, ord_ = (c.unsqueeze(1) for c in table.to(dev).unbind(1))
+    N = table.shape[0]
+    j = torch.arange(S, dtype=torch.int64, device=dev).unsqueeze(0)
+    L = la + lb + 3
+    in_a, in_b = (j >= 1) & (j <= la), (j >= la + 2) & (j <= la + lb + 1)
+    cand = in_a | in_b
+    idx = torch.where(in_a, a0 + j - 1, torch.where(in_b, b0 + j - la - 2, torch.zeros_like(j))).clamp_(0, T - 1)
+    tok = torch.where(cand, _token_values(src, idx), torch.full_like(idx, pad))
+    tok = torch.where(j == 0, torch.full_like(tok, cls), tok)
+    tok = torch.where((j == la + 1) | (j == L - 1), torch.full_like(tok, sep), tok)
+    types = ((j >= la + 2) & (j <= L - 1)).to(torch.int64)
+    ksel, kdec, krep = mlm_keys(seed, stream, ord_)
+    jg = _mul32(j, TOKEN_G)
+    # rank among the candidates by (score, j): the key is unique per position, so one sort gives it
+    key = torch.where(cand, _mix32(ksel ^ jg) * 1024 + j, torch.full_like(idx, 1 << 62))
+    rank = torch.empty_like(key)
+    rank.scatter_(1, key.argsort(dim=1), j.expand(N, S).contiguous())
+    sel = cand & (rank < n)
+    slot = sel.to(torch.int64).cumsum(1) - 1
+    labels = torch.full((N, P), -100, dtype=torch.int64, device=dev)
+    positions = torch.zeros((N, P), dtype=torch.int64, device=dev)
+    rows = torch.arange(N, device=dev).unsqueeze(1).expand(N, S)[sel]
+    labels[rows, slot[sel]] = tok[sel]
+    positions[rows, slot[sel]] = j.expand(N, S)[sel]
+    u = _mix32(kdec ^ jg)
+    rep = (_mix32(krep ^ jg) * vocab) >> 32
+    masked = torch.where(u < MLM_MASK_THR, torch.full_like(tok, mask), torch.where(u < MLM_RANDOM_THR, rep, tok))
+    return torch.where(sel, masked, tok), types, labels, positions
+
+
+def causal_batch(src, starts, S: int):
+    """The definition of ``ops.data.causal_batch``: ids = src[start + j], labels = src[start + j + 1], int64 [N, S]."""
+    src = torch.as_tensor(src)
+    starts = torch.as_tensor(starts)
+    S, T = int(S), int(src.shape[0])
+    if starts.dtype != torch.int64 or starts.dim() != 1 or starts.shape[0] < 1 or S < 1:
+        raise ValueError("starts must be int64 [N] and S positive")
+    if bool(((starts < 0) | (starts > T - S - 1)).any()):
+        raise ValueError("a window [start, start + %d + 1) leaves the %d tokens of src" % (S, T))
+    at = starts.to(src.device).unsqueeze(1) + torch.arange(S, dtype=torch.int64, device=src.device)
+    return _token_values(src, at), _token_values(src, at + 1)

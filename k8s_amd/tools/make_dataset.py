@@ -3,10 +3,18 @@
     python -m k8s_amd.tools.make_dataset --out DIR --toy [--seed 0] [--train 2048] [--val 256] [--classes 10]
                                                    [--size 40]
     python -m k8s_amd.tools.make_dataset --out DIR --cifar10-batches DIR_WITH_PICKLES
+    python -m k8s_amd.tools.make_dataset --out DIR --toy-tokens [--seed 0] [--train-docs 512] [--val-docs 64]
+                                                   [--vocab 512]
 
 ``--toy``: a learnable set that is a pure function of its seed. Class k is a fixed random 5x5x3 uint8 prototype
 (numpy Philox key 7, the same for every seed) upscaled to ``--size`` (x8 to 40x40 by default, nearest cell at other
 sizes); Gaussian noise of sigma 48 is added and the result clipped to uint8; labels are uniform. meta: mean 127.5, std 64.
+
+``--toy-tokens``: a learnable token set (``k8s_amd.data.tokens``) that is a pure function of its seed, for the BERT
+and Llama models. Specials pad 0, cls 1, sep 2, mask 3; 8 topics, topic k owning the ids 8 + 63 k .. 8 + 63 k + 62. A
+document draws one topic, 2 to 6 segments and 4 to 12 tokens per segment; a segment's first token is uniform in the
+topic's slice and each later one is ``base + (5 * prev_off + 1) mod 63`` with probability 0.9, else uniform in the
+slice.
 
 ``--cifar10-batches``: the CIFAR-10 "python version" pickles (``data_batch_1..5`` -> train, ``test_batch`` -> val; keys
 ``data`` [10000, 3072] CHW uint8 and ``labels``) converted to NHWC, with CIFAR-10's per-channel mean and std.
@@ -21,6 +29,7 @@ import sys
 import numpy as np
 
 from k8s_amd.data.dataset import write_dataset
+from k8s_amd.data.tokens import write_token_dataset
 
 TOY_PROTO_KEY, TOY_SIGMA = 7, 48.0
 CIFAR10_MEAN, CIFAR10_STD = [125.3, 123.0, 113.9], [63.0, 62.1, 66.7]
@@ -53,6 +62,39 @@ def make_toy(out: str, seed: int = 0, train: int = 2048, val: int = 256, classes
                   {"train": toy_split(seed, 0, train, classes, size), "val": toy_split(seed, 1, val, classes, size)})
 
 
+TOY_TOPICS, TOY_SLICE, TOY_FIRST_ID = 8, 63, 8
+TOY_SPECIAL = {"pad": 0, "cls": 1, "sep": 2, "mask": 3}
+
+
+def toy_token_split(seed: int, which: int, documents: int):
+    """(tokens int64 [T], segments int64 [G + 1], docs int64 [D + 1]) of split number ``which`` for ``seed``."""
+    g = np.random.Generator(np.random.Philox(np.random.SeedSequence([0x70F7, int(seed), int(which)])))
+    tokens, segments, docs = [], [0], [0]
+    for _ in range(documents):
+        base = TOY_FIRST_ID + TOY_SLICE * int(g.integers(0, TOY_TOPICS))
+        for _ in range(int(g.integers(2, 7))):
+            n = int(g.integers(4, 13))
+            follow, fresh = g.random(n) < 0.9, g.integers(0, TOY_SLICE, size=n)
+            off = int(fresh[0])
+            tokens.append(base + off)
+            for i in range(1, n):
+                off = (5 * off + 1) % TOY_SLICE if follow[i] else int(fresh[i])
+                tokens.append(base + off)
+            segments.append(len(tokens))
+        docs.append(len(segments) - 1)
+    return np.asarray(tokens, dtype=np.int64), np.asarray(segments, dtype=np.int64), np.asarray(docs, dtype=np.int64)
+
+
+def make_toy_tokens(out: str, seed: int = 0, train_docs: int = 512, val_docs: int = 64, vocab: int = 512) -> None:
+    if vocab < TOY_FIRST_ID + TOY_TOPICS * TOY_SLICE:
+        raise ValueError("--vocab must be at least %d (8 specials and reserved ids, 8 topics of 63 ids)"
+                         % (TOY_FIRST_ID + TOY_TOPICS * TOY_SLICE))
+    if train_docs < 2 or val_docs < 2:
+        raise ValueError("--train-docs and --val-docs must be at least 2 (sentence pairs need another document)")
+    write_token_dataset(out, vocab, {"train": toy_token_split(seed, 0, train_docs),
+                                     "val": toy_token_split(seed, 1, val_docs)}, TOY_SPECIAL)
+
+
 def read_cifar_batch(path: str):
     with open(path, "rb") as f:
         d = pickle.load(f, encoding="bytes")
@@ -81,14 +123,20 @@ def main(argv=None) -> int:
     src = ap.add_mutually_exclusive_group(required=True)
     src.add_argument("--toy", action="store_true")
     src.add_argument("--cifar10-batches", default=None, metavar="DIR")
+    src.add_argument("--toy-tokens", action="store_true", help="a learnable token set for the BERT and Llama models")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--train", type=int, default=2048)
     ap.add_argument("--val", type=int, default=256)
     ap.add_argument("--classes", type=int, default=10)
     ap.add_argument("--size", type=int, default=40)
+    ap.add_argument("--train-docs", type=int, default=512)
+    ap.add_argument("--val-docs", type=int, default=64)
+    ap.add_argument("--vocab", type=int, default=512)
     a = ap.parse_args(argv)
     try:
-        if a.toy:
+        if a.toy_tokens:
+            make_toy_tokens(a.out, a.seed, a.train_docs, a.val_docs, a.vocab)
+        elif a.toy:
             make_toy(a.out, a.seed, a.train, a.val, a.classes, a.size)
         else:
             make_cifar10(a.out, a.cifar10_batches)

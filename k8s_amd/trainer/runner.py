@@ -20,9 +20,9 @@ process exit code (`/root/reference/pkg/trainer/training.go:45-73`):
   replica and it resumes from the latest checkpoint;
 * evaluation (``--eval-every N`` / ``--eval-only``): forward-only passes over held-out synthetic batches or the
   fixed training batch, an ``eval`` event (loss, top-1 / top-5 or perplexity) and ``eval/*`` TensorBoard scalars;
-* data: synthetic batches of the model's shape, or for the ResNet models ``--data-dir``: a dataset directory
-  (``k8s_amd.data``) whose ``train`` split feeds the fused augmentation kernel and whose ``val`` split is the
-  held-out evaluation data;
+* data: synthetic batches of the model's shape, or ``--data-dir``: a dataset directory (``k8s_amd.data``; images for
+  the ResNet models, tokens for BERT and Llama) whose ``train`` split feeds the fused augmentation / token batch
+  kernel and whose ``val`` split is the held-out evaluation data;
 * outputs (chief only): ``<logdir>/events.out.tfevents.*`` (TensorBoard),
   ``<logdir>/metrics.jsonl`` (one JSON record per logged step, plus
   ``start`` / ``step0`` / ``done`` events with wall-clock times so the
@@ -109,12 +109,14 @@ def parse(argv=None):
                          "draws the same ones")
     ap.add_argument("--fresh-batches", action="store_true", help="draw a new synthetic batch every step")
     ap.add_argument("--data-dir", default="",
-                    help="ResNet: train on this dataset directory (k8s_amd.tools.make_dataset writes the format) "
+                    help="train on this dataset directory (k8s_amd.tools.make_dataset writes the formats: images "
+                         "for the ResNet models, tokens for BERT and Llama) "
                          "instead of synthetic batches; --eval-data heldout then reads its val split")
-    ap.add_argument("--augment", default="crop", choices=["crop", "rrc", "none"],
+    ap.add_argument("--augment", default=None, choices=["crop", "rrc", "none"],
                     help="--data-dir: random crop of the zero-padded source + flip, random-resized crop + flip, or "
                          "the centred crop")
-    ap.add_argument("--crop-pad", type=int, default=4, help="--augment crop: zero padding around the source")
+    ap.add_argument("--crop-pad", type=int, default=None,
+                    help="--augment crop: zero padding around the source (default 4)")
     ap.add_argument("--data-resident-gb", type=float, default=4.0,
                     help="--data-dir: a split up to this many GiB is uploaded once; a larger one is streamed batch "
                          "by batch by a background thread (0: always streamed)")
@@ -353,8 +355,9 @@ def train(a) -> int:
         config_error = "--dropout must be in [0, 1)"
     elif a.dropout > 0 and not a.model.startswith("bert"):
         config_error = "--dropout is implemented for the BERT models only, not %s" % a.model
-    elif a.data_dir and not a.model.startswith("resnet"):
-        config_error = "--data-dir holds images: it can be read by the ResNet models only, not %s" % a.model
+    elif a.data_dir and not a.model.startswith("resnet") and (a.augment is not None or a.crop_pad is not None
+                                                              or a.image is not None):
+        config_error = "--augment, --crop-pad and --image describe images: not with the token model %s" % a.model
     elif a.data_dir and a.graph:
         config_error = "--data-dir cannot be combined with --graph (a data step is not captured)"
     elif a.data_dir and a.eval_data == "train":
@@ -389,14 +392,17 @@ def train(a) -> int:
     comm = a.grad_comm if a.grad_comm != "auto" else "fp32"
     data = None
     if a.data_dir:  # every check of the data configuration, before the model is built and the start event written
-        from k8s_amd.data import DataError
-        from k8s_amd.models.registry import dataset_plan
+        from k8s_amd.models.registry import dataset_plan, token_dataset_plan
 
-        data = {"dir": a.data_dir, "augment": a.augment, "crop_pad": a.crop_pad, "resident_gb": a.data_resident_gb,
-                "seed": a.seed, "rank": rank, "world": world}
+        data = {"dir": a.data_dir, "resident_gb": a.data_resident_gb, "seed": a.seed, "rank": rank, "world": world}
         try:
-            data_info = dataset_plan(a.model, dev, batch, a.image, data, need_val=evaluating)[2]
-        except DataError as e:
+            if a.model.startswith("resnet"):
+                data.update(augment=a.augment or "crop", crop_pad=4 if a.crop_pad is None else a.crop_pad)
+                data_info = dataset_plan(a.model, dev, batch, a.image, data, need_val=evaluating)[2]
+            else:
+                data_info = token_dataset_plan(a.model, dev, batch, a.seq, data, need_val=evaluating,
+                                               mlm_every_token=a.mlm_head == "every-token")[2]
+        except ValueError as e:  # DataError, or a directory of the other kind
             print("error: %s" % e, file=sys.stderr, flush=True)
             kdist.destroy()
             return EXIT_PERMANENT
