@@ -19,6 +19,21 @@ const int* kv_lens_ptr(const OptTensor& kv_lens, long B) {
   return kv_lens->data_ptr<int>();
 }
 
+// doc_lo / doc_hi (optional, both or neither): the document-boundary mask of causal self-attention, int32 [B, Sq].
+// The kernels clamp what the tables hold; here only what the host can see is checked.
+template <class Args>
+void fill_doc(Args& a, const OptTensor& doc_lo, const OptTensor& doc_hi, bool with_lens, bool with_drop) {
+  if (!doc_lo && !doc_hi) return;
+  TORCH_CHECK(doc_lo && doc_hi, "doc_lo and doc_hi must be given together");
+  TORCH_CHECK(a.causal && a.Sq == a.Sk, "a document mask is defined for causal self-attention (Sq == Sk) only");
+  TORCH_CHECK(!with_lens && !with_drop, "a document mask cannot be combined with kv_lens or dropout");
+  for (const Tensor* t : {&*doc_lo, &*doc_hi})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous() && t->dim() == 2 &&
+                    t->size(0) == a.B && t->size(1) == a.Sq, "doc_lo / doc_hi must be int32 GPU tensors [B, Sq]");
+  a.doc_lo = doc_lo->data_ptr<int>();
+  a.doc_hi = doc_hi->data_ptr<int>();
+}
+
 // what AttnFwdArgs and AttnBwdArgs share: q / k / v [B, S, H, D] with their strides, the shape, the softmax scale and
 // kv_lens. Returns the head dim D.
 template <class Args>
@@ -43,10 +58,12 @@ long fill_qkv(Args& a, const Tensor& q, const Tensor& k, const Tensor& v, bool c
 // drop_state (optional): dropout on the probabilities, for the shapes of flash_dropout_fused (D = 64: the one-block
 // form, or Sq and Sk multiples of 64)
 std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, bool causal, OptTensor kv_lens, double scale,
-                              OptTensor drop_state, int64_t drop_thr, double drop_scale, int64_t drop_site) {
+                              OptTensor drop_state, int64_t drop_thr, double drop_scale, int64_t drop_site,
+                              OptTensor doc_lo, OptTensor doc_hi) {
   AttnFwdArgs a;
   const long D = fill_qkv(a, q, k, v, causal, kv_lens, scale);
   const long B = a.B, Sq = a.Sq, Hq = a.Hq, Sk = a.Sk, Hkv = a.Hkv;
+  fill_doc(a, doc_lo, doc_hi, kv_lens.has_value(), drop_state.has_value());
   if (drop_state) {
     TORCH_CHECK(k8s_amd::flash_dropout_fused((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, 1),
                 "attention dropout needs a flash_dropout_fused shape (D = 64: one-block, or Sq, Sk multiples of 64)");
@@ -66,10 +83,12 @@ std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, bool causal, OptTens
 // (Hq + Hkv)*D): the fused projection's gradient is written in place, no concatenation afterwards.
 std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal,
                               OptTensor kv_lens, double scale, OptTensor dqkv, OptTensor dbias, OptTensor drop_state,
-                              int64_t drop_thr, double drop_scale, int64_t drop_site) {
+                              int64_t drop_thr, double drop_scale, int64_t drop_site, OptTensor doc_lo,
+                              OptTensor doc_hi) {
   AttnBwdArgs a;
   const long D = fill_qkv(a, q, k, v, causal, kv_lens, scale);
   const long B = a.B, Sq = a.Sq, Hq = a.Hq, Sk = a.Sk, Hkv = a.Hkv;
+  fill_doc(a, doc_lo, doc_hi, kv_lens.has_value(), drop_state.has_value());
   check_attn_operand(o, "o", D); check_attn_operand(dO, "dO", D);
   TORCH_CHECK(dO.sizes() == q.sizes() && o.sizes() == q.sizes(), "dO / o must match q");
   check_cuda(lse, "lse"); check_dtype(lse, at::kFloat, "lse");
@@ -78,13 +97,16 @@ std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o,
               "lse must be the [B, Hq, round_up(Sq, 128)] tensor flash_fwd returned");
   const long Wp = (Hq + 2 * Hkv) * D;  // the packed QKV projection's width
   a.dkv_split = k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal);
-  const bool one_block = k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, a.dkv_split);
+  // (a document mask always takes the three-kernel form)
+  const bool one_block = !a.doc_lo &&
+                         k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, a.dkv_split);
   if (dqkv) {
     TORCH_CHECK(Sq == Sk, "packed QKV gradient needs self-attention (Sq == Sk)");
     check_cuda(*dqkv, "dqkv"); check_dtype(*dqkv, at::kBFloat16, "dqkv");
     TORCH_CHECK(dqkv->numel() == B * Sq * Wp, "dqkv must be contiguous [B*S, (Hq+2*Hkv)*D]");
   }
   if (dbias) {  // the packed projection's bias gradient from the one-block kernel's column partials
+    TORCH_CHECK(!a.doc_lo, "dbias is not available with a document mask (no one-block form)");
     TORCH_CHECK(dqkv && one_block, "dbias needs the packed gradient and a one-block shape (flash_bwd_one_block)");
     check_channel_f32(*dbias, Wp, "dbias");
   }
@@ -137,10 +159,10 @@ std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o,
 
 void bind_attention(pybind11::module_& m) {
   m.def("flash_fwd", &flash_fwd, "q"_a, "k"_a, "v"_a, "causal"_a, "kv_lens"_a, "scale"_a, "drop_state"_a = py::none(),
-        "drop_thr"_a = 0, "drop_scale"_a = 1.0, "drop_site"_a = 0);
+        "drop_thr"_a = 0, "drop_scale"_a = 1.0, "drop_site"_a = 0, "doc_lo"_a = py::none(), "doc_hi"_a = py::none());
   m.def("flash_bwd", &flash_bwd, "dO"_a, "q"_a, "k"_a, "v"_a, "o"_a, "lse"_a, "causal"_a, "kv_lens"_a, "scale"_a,
         "dqkv"_a = py::none(), "dbias"_a = py::none(), "drop_state"_a = py::none(), "drop_thr"_a = 0,
-        "drop_scale"_a = 1.0, "drop_site"_a = 0);
+        "drop_scale"_a = 1.0, "drop_site"_a = 0, "doc_lo"_a = py::none(), "doc_hi"_a = py::none());
   m.def("flash_bwd_one_block", [](int64_t D, int64_t Sq, int64_t Sk, int64_t Hq, int64_t Hkv, bool causal, int64_t B) {
           return k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv,
                                               k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal));

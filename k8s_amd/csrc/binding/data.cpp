@@ -135,9 +135,48 @@ std::vector<Tensor> causal_batch(Tensor src, Tensor starts, int64_t S) {
   return {ids, labels};
 }
 
+// causal_batch with document boundaries. starts index src (the rebased offsets of a streamed batch), abs_starts are the
+// same windows' positions in the split, both int64 [N] on the host; doc_tok int64 [D + 1] on the GPU, the documents'
+// token offsets (checked by the caller when it uploaded them: the host never reads device data here); split_tokens is
+// their last entry, the split's length. Returns ids, labels (int64) and lo, hi, pos (int32), all [N, S].
+std::vector<Tensor> causal_doc_batch(Tensor src, Tensor starts, Tensor abs_starts, Tensor doc_tok, int64_t S,
+                                     int64_t split_tokens) {
+  const bool u16 = check_token_src(src);
+  check_host_i64(starts, 0, "starts");
+  check_host_i64(abs_starts, 0, "abs_starts");
+  const int64_t T = src.size(0), N = starts.size(0);
+  TORCH_CHECK(abs_starts.size(0) == N, "starts and abs_starts must have the same length");
+  check_cuda(doc_tok, "doc_tok");
+  check_dtype(doc_tok, at::kLong, "doc_tok");
+  TORCH_CHECK(doc_tok.dim() == 1 && doc_tok.size(0) >= 2 && doc_tok.size(0) < (1L << 31) && doc_tok.is_contiguous() &&
+                  doc_tok.device() == src.device(), "doc_tok must be a contiguous int64 [D + 1] on src's device");
+  TORCH_CHECK(S >= 1 && S < (1L << 24) && N * S < (1L << 31), "causal_doc_batch: S or N * S out of range");
+  const int64_t* s = starts.data_ptr<int64_t>();
+  const int64_t* ab = abs_starts.data_ptr<int64_t>();
+  for (int64_t r = 0; r < N; ++r) {
+    TORCH_CHECK(s[r] >= 0 && s[r] <= T - S - 1, "starts row ", r, ": window [", s[r], ", + ", S, " + 1) leaves the ", T,
+                " tokens of src");
+    TORCH_CHECK(ab[r] >= 0 && ab[r] <= split_tokens - S - 1, "abs_starts row ", r, ": window [", ab[r], ", + ", S,
+                " + 1) leaves the ", split_tokens, " tokens of the split");
+  }
+  auto both = torch::stack({starts, abs_starts}).contiguous();  // one upload: [2, N]
+  auto dboth = both.pin_memory().to(src.device(), /*non_blocking=*/true);
+  auto opt = src.options().dtype(at::kLong), opt32 = src.options().dtype(at::kInt);
+  auto ids = torch::empty({N, S}, opt), labels = torch::empty({N, S}, opt);
+  auto lo = torch::empty({N, S}, opt32), hi = torch::empty({N, S}, opt32), pos = torch::empty({N, S}, opt32);
+  ++g_token_launches;
+  launch_causal_doc_batch(src.data_ptr(), u16, T, dboth.data_ptr<int64_t>(), dboth.data_ptr<int64_t>() + N,
+                          doc_tok.data_ptr<int64_t>(), doc_tok.size(0) - 1, (int)N, (int)S, ids.data_ptr<int64_t>(),
+                          labels.data_ptr<int64_t>(), lo.data_ptr<int>(), hi.data_ptr<int>(), pos.data_ptr<int>(),
+                          cur_stream());
+  return {ids, labels, lo, hi, pos};
+}
+
 }  // namespace
 
 void bind_data(pybind11::module_& m) {
+  m.def("causal_doc_batch", &causal_doc_batch, "src"_a, "starts"_a, "abs_starts"_a, "doc_tok"_a, "S"_a,
+        "split_tokens"_a, "gather causal-LM windows with their document bounds, positions and boundary-aware labels");
   m.def("mlm_batch", &mlm_batch, "src"_a, "table"_a, "S"_a, "P"_a, "vocab"_a, "special"_a, "seed"_a, "stream"_a = 0,
         "assemble a BERT pretraining batch (ids, token types, MLM labels and positions) from a token array");
   m.def("causal_batch", &causal_batch, "src"_a, "starts"_a, "S"_a, "gather causal-LM windows (ids, shifted labels)");

@@ -117,11 +117,18 @@ __device__ __forceinline__ const uint16_t* kh_src(const uint16_t* base, long rst
 // DROP: dropout on the probabilities (rng.h; row = (b * Hq + h) * Sq + query, col = key). The lane's QS rowkeys are
 // computed once; after the row sum (l keeps the undropped sum) each probability is kept or zeroed on its way into the
 // PV product, and the scale is folded into the epilogue's 1 / l.
-template <int D, int TILE, int NB = 2, int QS = 2, bool DROP = false>
+// DOC: document-boundary mask inside the causal triangle (query i sees the keys doc_lo[i] <= j <= i; NB = 2 forms).
+// The tables ascend along the row, so the block's smallest lo is that of its first query and its largest that of its
+// last valid one: the key tiles start at the first one's tile, the tiles below the second are masked, and a wave
+// skips a tile that ends at or below the lo of its first query. Every lo is clamped into [0, query] before use, so no
+// table content moves a trip count outside [0, ntiles] or an address outside the tensors.
+template <int D, int TILE, int NB = 2, int QS = 2, bool DROP = false, bool DOC = false>
 // (DROP on the one-tile form: 2 blocks per CU -- the mask's integer temporaries beside the 128-key score tile do not
 // fit the 168 registers of 3. On 64-key tiles they do: bounded to 3 blocks per CU like the plain form, which left
 // alone took 174 registers)
-__global__ void __launch_bounds__(FA_THREADS, NB == 1 && !DROP ? (QS == 1 ? 4 : 3) : (DROP && TILE == 64 ? 3 : 2))
+// (DOC on 64-key tiles at D = 64: bounded to the 3 blocks per CU the plain form reaches; left alone it took 194)
+__global__ void __launch_bounds__(FA_THREADS, NB == 1 && !DROP ? (QS == 1 ? 4 : 3)
+                                                               : ((DROP || (DOC && D == 64)) && TILE == 64 ? 3 : 2))
 flash_fwd_kernel(AttnFwdArgs a) {
   constexpr int BM = 64 * QS;  // queries per block
   constexpr int FA_BN = TILE;  // keys per iteration
@@ -147,6 +154,23 @@ flash_fwd_kernel(AttnFwdArgs a) {
   int kv_stop = kv_end;
   if (a.causal) kv_stop = min(kv_stop, q0 + BM + off);
   const int ntiles = kv_stop > 0 ? (kv_stop + FA_BN - 1) / FA_BN : 0;
+  // (DOC) first key tile of the block, end of its leading masked tiles, lo of the wave's first and last query
+  // (block- / wave-uniform: scalar loads), lo of the lane's queries
+  int t0 = 0, tlo = 0, lo_w0 = 0, lo_w1 = 0, lo_q[QS];
+  if constexpr (DOC) {
+    const int* lop = a.doc_lo + (long)b * a.Sq;
+    const int qe = a.Sq - 1;
+    auto lo_of = [&](int qi) {
+      const int qc = min(qi, qe);
+      return max(0, min(lop[qc], qc));
+    };
+    t0 = lo_of(q0) / FA_BN;  // q0 < kv_stop, so t0 < ntiles
+    tlo = min((lo_of(q0 + BM - 1) + FA_BN - 1) / FA_BN, ntiles);
+    lo_w0 = lo_of(q0w);
+    lo_w1 = lo_of(q0w + 16 * QS - 1);
+#pragma unroll
+    for (int qs = 0; qs < QS; ++qs) lo_q[qs] = lo_of(q0w + qs * 16 + li);
+  }
 
   const uint16_t* qp = a.q + (long)b * a.sqb + (long)h * a.sqh;
   const uint16_t* kp = a.k + (long)b * a.skb + (long)hk * a.skh;
@@ -213,21 +237,48 @@ flash_fwd_kernel(AttnFwdArgs a) {
     }
   };
 
+  // (DOC) the block's tiles [t0, ntiles) are the masked leading tiles [t0, tl) some query's document starts past, the
+  // mask-free tiles [tl, tf) and the masked diagonal tiles [tf, ntiles); tl = tf when lo_max lies past the diagonal
+  // limit and every tile is masked. They run mask-free first, then leading, then diagonal: the plain form's two loops
+  // in its order. (In key order -- masked, mask-free, masked -- the masked body's per-lane values stayed live across
+  // the mask-free loop and the D = 128 form spilled 22 to 52 registers.) seq(i) is the i-th tile to run.
+  int doc_tl = 0, doc_tf = 0;
+  auto seq = [&](int i) {
+    const int nf = doc_tf - doc_tl, nl = doc_tl - t0;
+    return i < nf ? doc_tl + i : (i - nf < nl ? t0 + (i - nf) : doc_tf + (i - nf - nl));
+  };
   if (ntiles > 0) {
-    stage(0, 0);
+    if constexpr (DOC) {
+      int tfull_ = max(0, q0 + 1) / FA_BN;  // (causal self-attention: the main loop's tfull)
+      tfull_ = min(tfull_, ntiles);
+      doc_tl = min(max(tlo, t0), ntiles);
+      doc_tf = max(doc_tl, tfull_);
+      stage(0, seq(0) * FA_BN);
+    } else {
+      stage(0, 0);
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
   // one key tile; MASKED: causal / key-length masking and whole-tile skips (only the block's last tiles need it,
   // so the main loop carries no masking code -- as one loop, the compiler if-converted the mask selects into every
   // tile)
-  auto tile = [&](const int t, auto masked_tag) {
+  // (DOC: the tiles run out of order: tile t is the ti-th of the block's doc_n to run, and the buffers alternate in ti.
+  // Passing the buffer and the next tile in as two values instead made the compiler wait for the prefetch, vmcnt(0),
+  // in front of every tile's first LDS read: profiles/doc_mask_static.md)
+  const int doc_n = ntiles - t0;
+  auto tile = [&](const int t, auto masked_tag, const int ti = 0) {
     constexpr bool MASKED = decltype(masked_tag)::value;
-    const int cur = NB > 1 ? (t & 1) : 0, key0 = t * FA_BN;
-    if (NB > 1 && t + 1 < ntiles) stage(cur ^ 1, key0 + FA_BN);
+    const int cur = DOC ? (ti & 1) : (NB > 1 ? (t & 1) : 0), key0 = t * FA_BN;
+    if constexpr (DOC) {
+      if (ti + 1 < doc_n) stage(cur ^ 1, seq(ti + 1) * FA_BN);
+    } else {
+      if (NB > 1 && t + 1 < ntiles) stage(cur ^ 1, key0 + FA_BN);
+    }
     const char* tk = smem + cur * 2 * KT;
     const char* tv = tk + KT;
-    const bool skip = MASKED && a.causal && key0 > q0w + 16 * QS - 1 + off;  // whole tile masked for this wave
+    bool skip = MASKED && a.causal && key0 > q0w + 16 * QS - 1 + off;  // whole tile masked for this wave
+    if constexpr (DOC && MASKED) skip = skip || key0 + FA_BN <= lo_w0;  // (every query's document starts past it)
     if (!skip) {
       // ---- S^T = K Q^T
       f32x4_t s[NI][QS];
@@ -245,7 +296,8 @@ flash_fwd_kernel(AttnFwdArgs a) {
         }
       }
       // ---- online softmax (per query column = lane & 15)
-      const bool need_mask = MASKED && ((key0 + FA_BN > kv_end) || (a.causal && key0 + FA_BN - 1 > q0w + off));
+      bool need_mask = MASKED && ((key0 + FA_BN > kv_end) || (a.causal && key0 + FA_BN - 1 > q0w + off));
+      if constexpr (DOC && MASKED) need_mask = need_mask || key0 < lo_w1;
 #pragma unroll
       for (int qs = 0; qs < QS; ++qs) {
         const int qi = q0w + qs * 16 + li;
@@ -255,7 +307,11 @@ flash_fwd_kernel(AttnFwdArgs a) {
 #pragma unroll
           for (int i = 0; i < NI; ++i)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) s[i][qs][r] = key0 + i * 16 + g * 4 + r > klim ? -INFINITY : s[i][qs][r];
+            for (int r = 0; r < 4; ++r) {
+              const int key = key0 + i * 16 + g * 4 + r;
+              if constexpr (DOC) s[i][qs][r] = key > klim || key < lo_q[qs] ? -INFINITY : s[i][qs][r];
+              else s[i][qs][r] = key > klim ? -INFINITY : s[i][qs][r];
+            }
         }
         float mx = -INFINITY;
 #pragma unroll
@@ -319,9 +375,16 @@ flash_fwd_kernel(AttnFwdArgs a) {
   int tfull = kv_end / FA_BN;
   if (a.causal) tfull = min(tfull, max(0, q0 + off + 1) / FA_BN);
   tfull = min(tfull, ntiles);
-  int t = 0;
-  for (; t < tfull; ++t) tile(t, std::false_type{});
-  for (; t < ntiles; ++t) tile(t, std::true_type{});
+  if constexpr (DOC) {
+    const int nf = doc_tf - doc_tl;
+    int i = 0;
+    for (; i < nf; ++i) tile(seq(i), std::false_type{}, i);
+    for (; i < doc_n; ++i) tile(seq(i), std::true_type{}, i);
+  } else {
+    int t = 0;
+    for (; t < tfull; ++t) tile(t, std::false_type{});
+    for (; t < ntiles; ++t) tile(t, std::true_type{});
+  }
 
   // ---- epilogue: O = O^T / l, lse2 = m + log2(l)
   uint16_t* op = a.o + (long)b * a.sob + (long)h * a.soh;
@@ -395,7 +458,10 @@ __global__ void __launch_bounds__(256) flash_rowkey_kernel(uint32_t* rowkey, Dro
 // more -- a whole wave's 64 x 16 B, which also keeps the stages 1 KB aligned), P~ = keep ? P : 0 feeds dV,
 // dS = P (scale * keep * dP - delta) feeds dK, and dV takes drop.scale where the fp32 accumulator leaves (the bf16
 // copy-out here, or flash_dkv_reduce_kernel behind the split partials).
-template <int D, int TILE, bool DROP = false>
+// DOC: the document mask (key j is seen by the queries j <= i < doc_hi[j]; hi ascends along the row): the query walk
+// of a key block ends at the tile holding the last query of its last valid key's document, and the lane's hi, clamped
+// into [key + 1, Sq], joins the mask test.
+template <int D, int TILE, bool DROP = false, bool DOC = false>
 __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArgs a) {
   constexpr int ND = D / 16, NK = D / 32;
   constexpr int FB_BM = TILE;              // queries per iteration
@@ -429,7 +495,18 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
   for (int i = 0; i < ND; ++i) dka[i] = dva[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int qt0 = a.causal ? max(0, k0 - off) / FB_BM : 0;
-  const int nqt = (a.Sq + FB_BM - 1) / FB_BM;
+  int nqt = (a.Sq + FB_BM - 1) / FB_BM;
+  int hi_k0 = 0, hi_key = 0;  // (DOC) hi of the block's first key (its smallest) and of the lane's key
+  if constexpr (DOC) {
+    const int* hip = a.doc_hi + (long)b * a.Sq;
+    auto hi_of = [&](int key) {
+      const int kc = min(key, a.Sk - 1);
+      return min(a.Sq, max(hip[kc], kc + 1));
+    };
+    hi_k0 = hi_of(k0);
+    hi_key = hi_of(kw + li);
+    nqt = min(nqt, (hi_of(k0 + FB_BN - 1) + FB_BM - 1) / FB_BM);  // > qt0: that hi lies past k0
+  }
   const int per_head = nqt - qt0;
   const int total = (k0 < kv_end && per_head > 0) ? rep * per_head : 0;
   // this block's chunk [it0, it1) of the walk; causal key blocks differ in work by up to Sq / 64 x, so one block
@@ -528,7 +605,8 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
         }
       }
       // ---- P = exp2(S c - lse2), dS = P (dP - delta)
-      const bool need_mask = q0 + FB_BM > a.Sq || k0 + FB_BN > kv_end || (a.causal && k0 + FB_BN - 1 > q0 + off);
+      bool need_mask = q0 + FB_BM > a.Sq || k0 + FB_BN > kv_end || (a.causal && k0 + FB_BN - 1 > q0 + off);
+      if constexpr (DOC) need_mask = need_mask || q0 + FB_BM > hi_k0;
 #pragma unroll
       for (int qs = 0; qs < NQ; ++qs) {
         f32x4_t l4 = *reinterpret_cast<const f32x4_t*>(tl + qs * 16 + g * 4);
@@ -539,7 +617,8 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int qi = q0 + qs * 16 + g * 4 + r;
-            const bool ok = qi < a.Sq && key < kv_end && !(a.causal && key > qi + off);
+            bool ok = qi < a.Sq && key < kv_end && !(a.causal && key > qi + off);
+            if constexpr (DOC) ok = ok && qi < hi_key;
             sv[qs][r] = ok ? sv[qs][r] : -INFINITY;
             l4[r] = ok ? l4[r] : 0.f;
             d4[r] = ok ? d4[r] : 0.f;
@@ -653,7 +732,9 @@ __global__ void __launch_bounds__(256) flash_dkv_reduce_kernel(AttnBwdArgs a) {
 // dQ^T += K^T dS^T with dS^T consumed in place (permuted k) and K^T read transposed from the K tile.
 // No atomics: each block owns its queries.
 // DROP: the same dS as the dK/dV kernel; a lane's QS row keys come from the row-key table next to lse / delta.
-template <int D, int TILE, int QS, bool DROP = false>
+// DOC: the forward's document mask: the key-tile loop starts at the tile of the block's first query's lo, a wave skips
+// a tile that ends at or below the lo of its first query, and the lane's clamped lo joins the per-score select.
+template <int D, int TILE, int QS, bool DROP = false, bool DOC = false>
 __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 : 2) flash_bwd_dq_kernel(AttnBwdArgs a) {
   constexpr int ND = D / 16, NK = D / 32;
   constexpr int FB_BN = TILE;  // keys per iteration
@@ -679,6 +760,20 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
   int kv_stop = kv_end;
   if (a.causal) kv_stop = min(kv_stop, q0 + BMQ + off);
   const int ntiles = kv_stop > 0 ? (kv_stop + FB_BN - 1) / FB_BN : 0;
+  int t0 = 0, lo_w0 = 0, lo_w1 = 0, lo_q[QS];  // (DOC) as the forward's
+  if constexpr (DOC) {
+    const int* lop = a.doc_lo + (long)b * a.Sq;
+    const int qe = a.Sq - 1;
+    auto lo_of = [&](int qi) {
+      const int qc = min(qi, qe);
+      return max(0, min(lop[qc], qc));
+    };
+    t0 = lo_of(q0) / FB_BN;  // q0 < kv_stop, so t0 < ntiles
+    lo_w0 = lo_of(q0w);
+    lo_w1 = lo_of(q0w + QW - 1);
+#pragma unroll
+    for (int qs = 0; qs < QS; ++qs) lo_q[qs] = lo_of(q0w + 16 * qs + li);
+  }
 
   const uint16_t* qp = a.q + (long)b * a.sqb + (long)h * a.sqh;
   const uint16_t* dop = a.dO + (long)b * a.sdb + (long)h * a.sdh;
@@ -747,17 +842,18 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
     }
   };
   if (ntiles > 0) {
-    stage(0, 0);
+    if constexpr (DOC) stage(t0 & 1, t0 * FB_BN);
+    else stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
   const int q_ = li >> 2, pp = li & 3;
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = DOC ? t0 : 0; t < ntiles; ++t) {
     const int cur = t & 1, key0 = t * FB_BN;
     if (t + 1 < ntiles) stage(cur ^ 1, key0 + FB_BN);
     const char* tk = smem + cur * 2 * KT;
     const char* tv = tk + KT;
-    if (!(a.causal && key0 > q0w + QW - 1 + off)) {
+    if (!((a.causal && key0 > q0w + QW - 1 + off) || (DOC && key0 + FB_BN <= lo_w0))) {
       f32x4_t s[NI][QS], dp[NI][QS];
 #pragma unroll
       for (int i = 0; i < NI; ++i)
@@ -778,7 +874,7 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
       }
       // masked scores -> -inf before the exponent (exp2(-inf) = 0): a select per score in masked tiles only, no
       // branch around each exponent (the per-element `ok ? exp : 0` form compiled to 72 exec-mask branches)
-      if ((key0 + FB_BN > kv_end) || (a.causal && key0 + FB_BN - 1 > q0w + off)) {
+      if ((key0 + FB_BN > kv_end) || (a.causal && key0 + FB_BN - 1 > q0w + off) || (DOC && key0 < lo_w1)) {
 #pragma unroll
         for (int qs = 0; qs < QS; ++qs) {
           const int qi = q0w + 16 * qs + li;
@@ -786,7 +882,11 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
 #pragma unroll
           for (int i = 0; i < NI; ++i)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) s[i][qs][r] = key0 + i * 16 + g * 4 + r > klim ? -INFINITY : s[i][qs][r];
+            for (int r = 0; r < 4; ++r) {
+              const int key = key0 + i * 16 + g * 4 + r;
+              if constexpr (DOC) s[i][qs][r] = key > klim || key < lo_q[qs] ? -INFINITY : s[i][qs][r];
+              else s[i][qs][r] = key > klim ? -INFINITY : s[i][qs][r];
+            }
         }
       }
 #pragma unroll
@@ -1128,6 +1228,12 @@ bool flash_dropout_fused(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split) 
 // D = 64 with long sequences: 128-wide key / query steps (same MFMA work per barrier as D = 128)
 static bool big_tile(int D, int S) { return D == 64 && S >= 1024; }
 
+// what the DOC forms are defined for
+static bool flash_doc_ok(const int* lo, const int* hi, int Sq, int Sk, int causal, const int* kv_lens,
+                         const void* drop_state) {
+  return lo && hi && causal && Sq == Sk && !kv_lens && !drop_state;
+}
+
 
 
 // dK/dV chunks per key block: causal key blocks carry from 1 to Sq / 64 query tiles of work, so with one block per
@@ -1155,6 +1261,15 @@ static bool fwd_one_tile() {
 void launch_flash_fwd(const AttnFwdArgs& a, int D, hipStream_t st) {
   const int nqb = (a.Sq + FA_BM - 1) / FA_BM;
   const dim3 grid(nqb * a.Hq * a.B), blk(FA_THREADS);
+  if (a.doc_lo || a.doc_hi) {  // the DOC forms: multi-tile only (a short sequence takes the 64-key tiles)
+    if (!flash_doc_ok(a.doc_lo, a.doc_hi, a.Sq, a.Sk, a.causal, a.kv_lens, a.drop.state))
+      throw std::runtime_error("flash_fwd: a document mask needs both tables, causal self-attention, no kv_lens and "
+                               "no dropout");
+    if (D == 128) hipLaunchKernelGGL((flash_fwd_kernel<128, 64, 2, 2, false, true>), grid, blk, 0, st, a);
+    else if (big_tile(D, a.Sk)) hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 2, 2, false, true>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((flash_fwd_kernel<64, 64, 2, 2, false, true>), grid, blk, 0, st, a);
+    return;
+  }
   if (a.drop.state) {  // the DROP form of what the plain dispatch below picks at D = 64
     if (!flash_dropout_fused(D, a.Sq, a.Sk, a.Hq, a.Hkv, 1))
       throw std::runtime_error("flash_fwd: dropout needs a shape of flash_dropout_fused");
@@ -1199,6 +1314,38 @@ static void launch_flash_bwd_drop(const AttnBwdArgs& a, const uint16_t* o, long 
 
 void launch_flash_bwd(const AttnBwdArgs& a, int D, const uint16_t* o, long sob, long sos, long soh,
                       hipStream_t st) {
+  if (a.doc_lo || a.doc_hi) {
+    // the DOC forms: never the one-block kernel (so no column partials) and never the QS = 2 dQ
+    if (!flash_doc_ok(a.doc_lo, a.doc_hi, a.Sq, a.Sk, a.causal, a.kv_lens, a.drop.state) || a.cpart)
+      throw std::runtime_error("flash_bwd: a document mask needs both tables, causal self-attention, no kv_lens, no "
+                               "dropout and no bias gradient");
+    const long R = (long)a.B * a.Sq * a.Hq;
+    const dim3 dgrid((unsigned)((R * (D / 8) + 255) / 256)), blk(FA_THREADS);
+    const dim3 gkv(((a.Sk + FB_BN - 1) / FB_BN) * a.Hkv * a.B * a.dkv_split), gq(((a.Sq + 63) / 64) * a.Hq * a.B);
+    if (D == 128) {
+      hipLaunchKernelGGL(flash_delta_kernel<128>, dgrid, dim3(256), 0, st, o, sob, sos, soh, a.dO, a.sdb, a.sds, a.sdh,
+                         a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
+      hipLaunchKernelGGL((flash_bwd_dkv_kernel<128, 64, false, true>), gkv, blk, 0, st, a);
+      hipLaunchKernelGGL((flash_bwd_dq_kernel<128, 64, 1, false, true>), gq, blk, 0, st, a);
+    } else {
+      hipLaunchKernelGGL(flash_delta_kernel<64>, dgrid, dim3(256), 0, st, o, sob, sos, soh, a.dO, a.sdb, a.sds, a.sdh,
+                         a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
+      if (big_tile(D, a.Sq)) {
+        hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 128, false, true>), gkv, blk, 0, st, a);
+        hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 128, 1, false, true>), gq, blk, 0, st, a);
+      } else {
+        hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 64, false, true>), gkv, blk, 0, st, a);
+        hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 1, false, true>), gq, blk, 0, st, a);
+      }
+    }
+    if (a.dkv_split > 1) {
+      const long n = (long)a.B * a.Hkv * a.Sk * (D / 8);
+      const dim3 rg((unsigned)((n + 255) / 256));
+      if (D == 128) hipLaunchKernelGGL(flash_dkv_reduce_kernel<128>, rg, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(flash_dkv_reduce_kernel<64>, rg, dim3(256), 0, st, a);
+    }
+    return;
+  }
   if (flash_bwd_one_block(D, a.Sq, a.Sk, a.Hq, a.Hkv, a.dkv_split)) {
     if ((long)a.B * a.Hq > 0) {
       if (a.drop.state)

@@ -337,6 +337,11 @@ struct AttnFwdArgs {
   float scale_log2;
   // dropout on the probabilities (the shapes of flash_dropout_fused): row = (b * Hq + h) * Sq + q, col = key
   DropArgs drop;
+  // document-boundary mask (the DOC forms; causal self-attention only): int32 [B, Sq], query i sees the keys
+  // doc_lo[i] <= j <= i, and hi[j] is one past the last query that sees key j. Both or neither; device data the
+  // kernels clamp before use.
+  const int* doc_lo = nullptr;
+  const int* doc_hi = nullptr;
 };
 struct AttnBwdArgs {
   const uint16_t *q, *k, *v, *dO;
@@ -362,6 +367,8 @@ struct AttnBwdArgs {
   // dropout on the three-kernel form: the queries' row keys, [B, Hq, lse_ld] scratch next to delta (written by the
   // delta kernel from the device [seed, step] pair, read by the dK/dV and dQ kernels)
   uint32_t* rowkey = nullptr;
+  const int* doc_lo = nullptr;  // as the forward's (the dQ kernel reads lo, the dK/dV kernel hi)
+  const int* doc_hi = nullptr;
 };
 int flash_dkv_splits(int B, int Sq, int Sk, int Hkv, int causal);
 // the whole backward of one (batch, head) in one block (flash_bwd_short_kernel) applies to this shape
@@ -449,6 +456,12 @@ void launch_mlm_batch(const void* src, bool u16, long Tn, const long* table, int
                       long* positions, hipStream_t st);
 void launch_causal_batch(const void* src, bool u16, long Tn, const long* starts, int N, int S, long* ids, long* labels,
                          hipStream_t st);
+// causal_batch with document boundaries: doc_tok int64 [Dn + 1] ascending token offsets of the documents (device),
+// abs_starts the windows' positions in the split; also writes int32 [N, S] lo, hi (the document of each token, as
+// row indices) and pos (the token's position inside its document)
+void launch_causal_doc_batch(const void* src, bool u16, long Tn, const long* starts, const long* abs_starts,
+                             const long* doc_tok, long Dn, int N, int S, long* ids, long* labels, int* lo, int* hi,
+                             int* pos, hipStream_t st);
 
 // ---- NHWC max pooling (pool.hip): idx = winning window position per output element (uint8)
 void launch_subsample_nhwc(const uint16_t* x, uint16_t* y, int N, int H, int W, int C, int s, hipStream_t st);

@@ -1,6 +1,7 @@
-// Token batch assembly: a whole BERT pretraining batch (mlm_batch_kernel) or a causal-LM batch (causal_batch_kernel)
+// Token batch assembly: a whole BERT pretraining batch (mlm_batch_kernel) or a causal-LM batch (causal_batch_kernel;
+// causal_doc_batch_kernel with the document bounds, positions and boundary-aware labels of document-masked attention)
 // from the token array and a small host table, in one launch. Integer arithmetic only: ops/reference.py mlm_batch /
-// causal_batch are the same definitions in torch and match bit for bit.
+// causal_batch / causal_doc_batch are the same definitions in torch and match bit for bit.
 //
 // src    uint16 or int32 [T]   the split's tokens (or one staged batch of them)
 // table  int64 [N][6]          per sample (a0, la, b0, lb, n, ord), drawn on the host (data/token_sampler.py)
@@ -152,6 +153,40 @@ __global__ void __launch_bounds__(256) causal_batch_kernel(const T* __restrict__
   labels[e] = tok_load(src, at + 1, Tn);
 }
 
+// causal_batch with document boundaries: element (n, j) sits at p = abs_starts[n] + j of the split; d is the largest
+// index with doc_tok[d] <= p, clamped into [0, Dn - 1] (a binary search over the ascending offsets, at most 40 steps,
+// every probe inside the table), and
+//   lo = max(doc_tok[d] - abs, 0), hi = min(doc_tok[d + 1] - abs, S), pos = j - lo,
+//   label = src[start + j + 1] if p + 1 < doc_tok[d + 1] else -100.
+// The three int32 results are clamped into [0, S] / [-S, S] on their way out, which changes nothing for a window
+// inside the split.
+template <typename T>
+__global__ void __launch_bounds__(256) causal_doc_batch_kernel(const T* __restrict__ src, long Tn,
+                                                               const long* __restrict__ starts,
+                                                               const long* __restrict__ abs_starts,
+                                                               const long* __restrict__ doc_tok, int Dn, int S,
+                                                               int total, long* __restrict__ ids,
+                                                               long* __restrict__ labels, int* __restrict__ lo,
+                                                               int* __restrict__ hi, int* __restrict__ pos) {
+  const int e = blockIdx.x * 256 + threadIdx.x;  // output element (n, j)
+  if (e >= total) return;
+  const int n = e / S, j = e - n * S;
+  const long at = starts[n] + j, ab = abs_starts[n], p = ab + j;
+  int d = 0, top = Dn - 1;  // doc_tok[d] <= p < doc_tok[top + 1], or an end of the range
+  for (int it = 0; it < 40 && d < top; ++it) {
+    const int mid = (d + top + 1) >> 1;
+    if (doc_tok[mid] <= p) d = mid;
+    else top = mid - 1;
+  }
+  const long first = doc_tok[d], end = doc_tok[d + 1];
+  const long l = tok_clamp(first - ab, S), h = tok_clamp(end - ab, S);
+  ids[e] = tok_load(src, at, Tn);
+  labels[e] = p + 1 < end ? tok_load(src, at + 1, Tn) : -100;
+  lo[e] = (int)l;
+  hi[e] = (int)h;
+  pos[e] = (int)(j - l);
+}
+
 void launch_mlm_batch(const void* src, bool u16, long Tn, const long* table, int N, int S, int P, uint32_t vocab,
                       const TokSpecial& sp, uint64_t seed, int stream, long* ids, long* types, long* labels,
                       long* positions, hipStream_t st) {
@@ -177,6 +212,21 @@ void launch_causal_batch(const void* src, bool u16, long Tn, const long* starts,
   else
     hipLaunchKernelGGL(causal_batch_kernel<int>, grid, block, 0, st, (const int*)src, Tn, starts, S, (int)total, ids,
                        labels);
+}
+
+void launch_causal_doc_batch(const void* src, bool u16, long Tn, const long* starts, const long* abs_starts,
+                             const long* doc_tok, long Dn, int N, int S, long* ids, long* labels, int* lo, int* hi,
+                             int* pos, hipStream_t st) {
+  const long total = (long)N * S;
+  if (N < 1 || Tn < 1 || S < 1 || Dn < 1 || Dn >= (1L << 31) - 1 || total >= (1L << 31))
+    throw std::runtime_error("causal_doc_batch: bad shape");
+  const dim3 grid(cdiv(total, 256)), block(256);
+  if (u16)
+    hipLaunchKernelGGL(causal_doc_batch_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)src, Tn, starts,
+                       abs_starts, doc_tok, (int)Dn, S, (int)total, ids, labels, lo, hi, pos);
+  else
+    hipLaunchKernelGGL(causal_doc_batch_kernel<int>, grid, block, 0, st, (const int*)src, Tn, starts, abs_starts,
+                       doc_tok, (int)Dn, S, (int)total, ids, labels, lo, hi, pos);
 }
 
 }  // namespace k8s_amd

@@ -11,7 +11,9 @@ As ``loader.Loader``, three paths end in the same call and produce the same bits
 
 ``batch(t)`` returns, for BERT, ``(ids, token_types, labels [N, P], nsp, positions [N, P], kv_lens)`` --
 ``BertForPreTraining.forward``'s positional order, so the real sequence lengths reach attention -- and for Llama
-``(ids, labels)``.
+``(ids, labels)``, or with ``doc_mask=True`` ``(ids, labels, lo, hi, pos)`` from one ``ops.data.causal_doc_batch`` call:
+the bounds of every token's document inside its row, positions that restart at each document, and -100 labels on every
+document's last token -- ``LlamaForCausalLM.forward``'s positional order.
 """
 from __future__ import annotations
 
@@ -39,13 +41,21 @@ class TokenLoader:
 
     def __init__(self, ds: TokenDataset, split: str, device, batch: int, seq: int, kind: str = "bert",
                  max_predictions: int = 20, seed: int = 0, rank: int = 0, world: int = 1, resident_gb: float = 4.0,
-                 train: bool = True):
+                 train: bool = True, doc_mask: bool = False):
         assert kind in KINDS
         self.ds, self.split, self.device, self.kind = ds, ds.split(split), torch.device(device), kind
         self.tokens = self.split.tokens
         self.batch_size, self.S, self.P, self.train = int(batch), int(seq), int(max_predictions), train
         self.seed, self.rank, self.world = int(seed), int(rank), int(world)
         self.stream = 0 if train else 1
+        self.doc_mask, self.doc_tok_host, self.doc_tok = bool(doc_mask), None, None
+        if self.doc_mask:
+            if kind != "llama":
+                raise DataError("document-boundary masks are implemented for the Llama models only")
+            if self.split.segments is None or self.split.docs is None:
+                raise DataError("dataset %s: a document mask needs %s_segments.npy and %s_docs.npy"
+                                % (ds.path, split, split))
+            self.doc_tok_host = np.ascontiguousarray(self.split.segments[self.split.docs], dtype=np.int64)
         if kind == "bert":
             ts.check_seq(self.S, self.P)
             if ds.special is None or self.split.segments is None or self.split.docs is None or self.split.D < 2:
@@ -66,6 +76,8 @@ class TokenLoader:
         gpu = self.device.type == "cuda"
         self.resident = is_resident(self.split.nbytes, resident_gb, self.device)
         self.src, self.streamer, self._plans = None, None, {}
+        if self.doc_mask:  # checked on the host and uploaded once
+            self.doc_tok = kdata.doc_offsets(self.doc_tok_host, self.device)
         if self.resident:
             self.src = _as_torch(np.array(self.tokens)).to(self.device)  # one read of the map, one upload
         elif gpu:
@@ -136,7 +148,11 @@ class TokenLoader:
             self.compact(plan, buf)
             src, rows = _as_torch(buf), plan["local"]
         rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64))
-        if self.kind == "llama":
+        doc = ()
+        if self.kind == "llama" and self.doc_mask:
+            at = torch.from_numpy(np.ascontiguousarray(plan["starts"], dtype=np.int64))
+            ids, labels, *doc = kdata.causal_doc_batch(src, rows, at, self.doc_tok, self.S, self.split.T)
+        elif self.kind == "llama":
             ids, labels = kdata.causal_batch(src, rows, self.S)
         else:
             ids, types, labels, positions = kdata.mlm_batch(src, rows, self.S, self.P, self.ds.vocab, self.ds.special,
@@ -146,7 +162,7 @@ class TokenLoader:
         if plan["real"] is not None:  # evaluation rows past the end of the split: no label counts
             labels = labels.masked_fill(~self._upload(plan["real"]).unsqueeze(1), -100)
         if self.kind == "llama":
-            return ids, labels
+            return (ids, labels) + tuple(doc)
         return (ids, types, labels, self._upload(plan["nsp"]), positions,
                 self._upload(plan["kv_lens"].astype(np.int32)))
 
@@ -162,8 +178,17 @@ class TokenLoader:
             return 0.0
         return float(1.0 - self.plan(t)["kv_lens"].mean() / self.S)
 
+    def docs_per_row(self, t: int = 0) -> float:
+        """The mean number of documents a row of batch ``t`` holds (from the host tables)."""
+        at = self.plan(t)["starts"]
+        first = np.searchsorted(self.doc_tok_host, at, side="right")
+        last = np.searchsorted(self.doc_tok_host, at + self.S - 1, side="right")
+        return float((last - first + 1).mean())
+
     def info(self) -> dict:
         out = {"resident": self.resident}
+        if self.doc_mask:
+            out.update(doc_mask=True, docs_per_row=round(self.docs_per_row(0), 4))
         if self.streamer is not None and self.streamer.gather_s > 0:
             out["gather_gb_per_s"] = round(self.streamer.gather_bytes / self.streamer.gather_s / 1e9, 3)
             out["restarts"] = self.streamer.restarts

@@ -70,9 +70,10 @@ class LlamaLayer(nn.Module):
         self.swiglu_blk = 64 if c.intermediate % 64 == 0 else 0
         self.down = store.new(name + ".mlp.down_proj.weight", (h, c.intermediate), out_std)
 
-    def forward(self, x, res, B, S, pos, table):
+    def forward(self, x, res, B, S, pos, table, doc=None):
         """x: this layer's input stream delta, res: running residual (None for the first layer).
-        Returns (delta, residual) so every residual add is fused into the next RMSNorm."""
+        Returns (delta, residual) so every residual add is fused into the next RMSNorm. ``doc`` = (lo, hi): the
+        document-boundary mask of ``ops.attention`` (``pos`` then restarts at every document)."""
         c = self.c
         d = c.head_dim
         if res is None:
@@ -83,9 +84,10 @@ class LlamaLayer(nn.Module):
         # the q / k rotary embedding in the QKV GEMM's epilogue where the kernel takes the shape (else in place below)
         qkv, rotated = K.linear_rope(hn, self.qkv, pos, table, (c.heads + c.kv_heads) * d)
         # causal GQA flash attention and the packed QKV gradient in one op (no split/cat/copies)
+        kw = {} if doc is None else {"doc": doc}
         o = attention_qkv(qkv, B, S, c.heads, c.kv_heads, d, causal=True, rope=(pos, table),
                           rope_in_place=True,  # qkv: this linear's output, read by nothing else
-                          rope_applied=rotated)
+                          rope_applied=rotated, **kw)
         a = K.linear(o.reshape(B * S, c.heads * d), self.o)
         hn, res = K.rms_norm(a, self.mlp_norm, c.eps, residual=res)
         sl = K.SwiGLULink(self.swiglu_blk)  # the SwiGLU backward inside the down projection's data gradient
@@ -110,14 +112,24 @@ class LlamaForCausalLM(nn.Module):
         self.table = K.rope_table(self.c.max_position, self.c.head_dim, self.c.rope_theta, device)
         return self.to(device)
 
-    def forward(self, input_ids, labels, dtype=torch.bfloat16):
+    def forward(self, input_ids, labels, doc_lo=None, doc_hi=None, pos=None, dtype=torch.bfloat16):
+        """``doc_lo``, ``doc_hi``, ``pos`` (int32 [B, S], all three or none; ``ops.data.causal_doc_batch``): rows that
+        pack several documents -- attention stays inside each token's document and ``pos``, restarting at every
+        document, replaces 0 .. S - 1."""
         B, S = input_ids.shape
         c = self.c
-        pos = torch.arange(S, device=input_ids.device, dtype=torch.int32).repeat(B)
+        doc = None
+        if doc_lo is None and doc_hi is None and pos is None:
+            pos = torch.arange(S, device=input_ids.device, dtype=torch.int32).repeat(B)
+        elif doc_lo is None or doc_hi is None or pos is None:
+            raise ValueError("doc_lo, doc_hi and pos go together")
+        else:
+            doc = (doc_lo, doc_hi)
+            pos = pos.to(torch.int32).reshape(-1).contiguous()
         x = K.embedding_sum([(input_ids, self.embed)], S, dtype).reshape(B * S, c.hidden)
         res = None
         for layer in self.layers:
-            x, res = layer(x, res, B, S, pos, self.table)
+            x, res = layer(x, res, B, S, pos, self.table, doc)
         hn, _ = K.rms_norm(x, self.norm, c.eps, residual=res)
         logits = K.linear(hn, self.lm_head)
         return K.cross_entropy(logits, labels.reshape(-1))

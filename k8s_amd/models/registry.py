@@ -154,6 +154,16 @@ def token_dataset_plan(name: str, device, batch: int, seq: Optional[int], data: 
               seed=data.get("seed", 0), rank=data.get("rank", 0), world=data.get("world", 1),
               resident_gb=data.get("resident_gb", 4.0))
     tr = ds.split("train")
+    doc_mask = bool(data.get("doc_mask"))
+    if doc_mask:
+        if bert:
+            raise DataError("document-boundary masks are implemented for the Llama models only, not %s" % name)
+        for sp_name in ("train", "val") if need_val else ("train",):
+            sp = ds.split(sp_name)
+            if sp.segments is None or sp.docs is None:
+                raise DataError("dataset %s: --doc-mask needs %s_segments.npy and %s_docs.npy"
+                                % (ds.path, sp_name, sp_name))
+        kw["doc_mask"] = True
     if bert:
         ts.check_seq(seq, kw["max_predictions"])
         items, what = tr.G, "segments"
@@ -170,6 +180,14 @@ def token_dataset_plan(name: str, device, batch: int, seq: Optional[int], data: 
             "val": size(ds.splits["val"]) if "val" in ds.splits else None, "seq": seq,
             "resident": is_resident(tr.nbytes, kw["resident_gb"], torch.device(device)), "steps_per_epoch": E,
             "pad_fraction": pad_fraction}
+    if doc_mask:  # the documents per row of the first batch, from the host tables alone
+        import numpy as np
+
+        idx = ts.train_items(kw["seed"], 0, kw["rank"], kw["world"], batch, items)[0]
+        doc_tok = tr.segments[tr.docs]
+        first = np.searchsorted(doc_tok, idx * seq, side="right")
+        last = np.searchsorted(doc_tok, idx * seq + seq - 1, side="right")
+        info.update(doc_mask=True, docs_per_row=round(float((last - first + 1).mean()), 4))
     return ds, kw, info
 
 

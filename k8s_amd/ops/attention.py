@@ -15,6 +15,13 @@ reference (no SDPA dispatch, so no Triton-built kernels run).
 shapes of ``flash_dropout_fused`` -- head_dim 64 and either the one-block backward's shapes (Sq, Sk <= 128, Hq == Hkv)
 or Sq and Sk multiples of 64 (the multi-tile forward and the three-kernel backward); any other GPU shape runs the
 reference composition with the same mask, counted in ``DROPOUT_FALLBACKS`` and warned about once.
+
+``doc=(lo, hi)``: a document-boundary mask inside the causal triangle, for rows that pack several documents. ``lo`` and
+``hi`` are int32 [B, S]: ``lo[b, i]`` is the row index of the first token of token ``i``'s document and ``hi[b, i]`` one
+past its last (``doc_bounds`` derives both from ``lo``). Query ``i`` sees key ``j`` iff ``lo[i] <= j <= i``. The DOC
+forms of the multi-tile forward, the dK/dV and the dQ kernels skip the key (query) tiles no query (key) of a block can
+see. Causal self-attention only: with ``kv_lens``, ``dropout`` or ``causal=False`` it is a ``ValueError``. GPU operands
+outside the flash contract run the reference with the same mask.
 """
 from __future__ import annotations
 
@@ -64,9 +71,63 @@ def _flash_ok(q, k, v) -> bool:
     return ok and hasattr(_load(), "flash_fwd")  # _load() raises if the extension is missing on a GPU box
 
 
+def doc_mask_reference(doc_lo: torch.Tensor) -> torch.Tensor:
+    """bool [B, S, S], True where query i may NOT see key j: the complement of ``lo[i] <= j <= i``."""
+    S = doc_lo.shape[1]
+    i = torch.arange(S, device=doc_lo.device)
+    return (i[None, None, :] < doc_lo.long()[:, :, None]) | (i[None, None, :] > i[None, :, None])
+
+
+def doc_bounds(doc_starts: torch.Tensor):
+    """``doc_starts`` integer [B, S]: for every token the row index of the first token of its document. Returns the
+    ``(lo, hi)`` int32 pair ``attention(..., doc=)`` takes, on the same device: ``lo`` is ``doc_starts`` and ``hi[i]``
+    the next document's start after ``i`` (``S`` in the last document). A CPU tensor is checked first (``lo`` ascending,
+    ``0 <= lo[i] <= i`` and ``lo[lo[i]] == lo[i]``) and a bad one raises ``ValueError``; device tensors are not read by
+    the host, and the kernels clamp whatever they hold."""
+    if doc_starts.dim() != 2 or doc_starts.dtype not in (torch.int32, torch.int64) or doc_starts.shape[1] < 1:
+        raise ValueError("doc_starts must be an int32 or int64 [B, S] tensor")
+    B, S = doc_starts.shape
+    lo = doc_starts.long()
+    idx = torch.arange(S, device=lo.device).expand(B, S)
+    if not doc_starts.is_cuda:
+        ok = bool((lo >= 0).all()) and bool((lo <= idx).all()) and bool((lo[:, 1:] >= lo[:, :-1]).all())
+        if not (ok and bool((torch.gather(lo, 1, lo) == lo).all())):
+            raise ValueError("doc_starts must ascend along each row with 0 <= start[i] <= i and start[start[i]] == "
+                             "start[i]")
+    # hi[i] = the smallest document start above i: a reversed running minimum over (j if a document starts at j else S)
+    nxt = torch.where(lo == idx, idx, torch.full_like(idx, S))
+    nxt = torch.cat([nxt[:, 1:], torch.full((B, 1), S, dtype=nxt.dtype, device=nxt.device)], 1)
+    hi = torch.cummin(nxt.flip(1), 1).values.flip(1)
+    return lo.to(torch.int32).contiguous(), hi.to(torch.int32).contiguous()
+
+
+def _doc_spec(doc, q, k, causal, kv_lens, dropout):
+    """The checked ``(lo, hi)`` of a ``doc=`` argument (None when off): causal self-attention, nothing else masked."""
+    if doc is None:
+        return None
+    if not causal or q.shape[1] != k.shape[1]:
+        raise ValueError("attention: a document mask is defined for causal self-attention (Sq == Sk) only")
+    if kv_lens is not None or dropout is not None:
+        raise ValueError("attention: a document mask cannot be combined with kv_lens or dropout")
+    lo, hi = doc
+    shape = (q.shape[0], q.shape[1])
+    if tuple(lo.shape) != shape or tuple(hi.shape) != shape or lo.dtype != torch.int32 or hi.dtype != torch.int32:
+        raise ValueError("attention: doc = (lo, hi) must be two int32 [B, S] tensors (ops.attention.doc_bounds)")
+    return lo, hi
+
+
+def _doc_kw(doc, device) -> dict:
+    """flash_fwd / flash_bwd keyword arguments of a document mask; none when off."""
+    if doc is None:
+        return {}
+    return {"doc_lo": doc[0].to(device).contiguous(), "doc_hi": doc[1].to(device).contiguous()}
+
+
 def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None,
-                        keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0):
-    """``keep`` (bool [B, Hq, Sq, Sk], ``ref.attention_keep``) with ``keep_scale``: dropout on the probabilities."""
+                        keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0,
+                        doc_lo: Optional[torch.Tensor] = None):
+    """``keep`` (bool [B, Hq, Sq, Sk], ``ref.attention_keep``) with ``keep_scale``: dropout on the probabilities.
+    ``doc_lo`` (int [B, S], with ``causal`` and Sq == Sk): the document mask, query i sees the keys lo[i] <= j <= i."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
     rep = Hq // Hkv
@@ -82,6 +143,8 @@ def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] =
     if kv_lens is not None:
         keymask = torch.arange(Sk, device=q.device)[None, :] >= kv_lens[:, None].to(q.device)
         s = s.masked_fill(keymask[:, None, None, :], float("-inf"))
+    if doc_lo is not None:
+        s = s.masked_fill(doc_mask_reference(doc_lo.to(q.device))[:, None], float("-inf"))
     p = torch.softmax(s, -1)
     if keep is not None:
         p = torch.where(keep, p * keep_scale, torch.zeros((), device=p.device))
@@ -106,11 +169,11 @@ def _ref_keep(drop, q, k):
 
 class _Flash(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None):
+    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None, doc=None):
         C = _load()
         if kv_lens is not None:
             kv_lens = kv_lens.to(device=q.device, dtype=torch.int32).contiguous()
-        ctx.drop = _drop_kw(drop)
+        ctx.drop = dict(_drop_kw(drop), **_doc_kw(doc, q.device))
         o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.drop)
         ctx.save_for_backward(q, k, v, o, lse, kv_lens if kv_lens is not None else torch.empty(0))
         ctx.causal, ctx.scale, ctx.has_lens = causal, scale, kv_lens is not None
@@ -122,17 +185,18 @@ class _Flash(torch.autograd.Function):
         C = _load()
         dq, dk, dv = C.flash_bwd(do.contiguous(), q, k, v, o, lse, ctx.causal, lens if ctx.has_lens else None,
                                  ctx.scale, **ctx.drop)
-        return dq, dk, dv, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None
 
 
 class _Reference(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None):
+    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None, doc=None):
         ctx.save_for_backward(q, k, v)
         ctx.causal, ctx.kv_lens, ctx.scale, ctx.drop = causal, kv_lens, scale, drop
+        ctx.doc_lo = doc[0] if doc is not None else None
         with torch.no_grad():
             keep, ks = _ref_keep(drop, q, k)
-            return attention_reference(q, k, v, causal, kv_lens, scale, keep, ks)
+            return attention_reference(q, k, v, causal, kv_lens, scale, keep, ks, ctx.doc_lo)
 
     @staticmethod
     def backward(ctx, do):
@@ -140,14 +204,17 @@ class _Reference(torch.autograd.Function):
         with torch.enable_grad():
             qq, kk, vv = (t.detach().float().requires_grad_(True) for t in (q, k, v))
             keep, ks = _ref_keep(ctx.drop, q, k)  # the forward's mask again (same seed, step and site)
-            o = attention_reference(qq, kk, vv, ctx.causal, ctx.kv_lens, ctx.scale, keep, ks)
+            o = attention_reference(qq, kk, vv, ctx.causal, ctx.kv_lens, ctx.scale, keep, ks, ctx.doc_lo)
             dq, dk, dv = torch.autograd.grad(o, (qq, kk, vv), do.float())
-        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None, None
+        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None, None, None
 
 
 def attention(q, k, v, causal: bool = False, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None,
-              dropout: Optional[tuple] = None):
+              dropout: Optional[tuple] = None, doc: Optional[tuple] = None):
     scale = scale or 1.0 / math.sqrt(q.shape[-1])
+    doc = _doc_spec(doc, q, k, causal, kv_lens, dropout)
+    if doc is not None:  # the DOC kernels, or the reference with the same mask: never a call that drops it
+        return (_Flash if _flash_ok(q, k, v) else _Reference).apply(q, k, v, causal, None, scale, None, doc)
     drop = _drop_spec(dropout)
     if drop is not None:
         if _drop_fused(q, k, v, causal):
@@ -168,7 +235,7 @@ class _FlashQKV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, B, S, H, Hkv, D, causal, kv_lens, scale, pos, table, bias_link=None, rope_in_place=False,
-                rope_applied=False, drop=None):
+                rope_applied=False, drop=None, doc=None):
         C = _load()
         if kv_lens is not None:
             kv_lens = kv_lens.to(device=qkv.device, dtype=torch.int32).contiguous()
@@ -182,7 +249,7 @@ class _FlashQKV(torch.autograd.Function):
             C.rope_(x[:, : (H + Hkv) * D], pos, table, False)
         g = x.view(B, S, H + 2 * Hkv, D)
         q, k, v = g.narrow(2, 0, H), g.narrow(2, H, Hkv), g.narrow(2, H + Hkv, Hkv)
-        ctx.drop = _drop_kw(drop)
+        ctx.drop = dict(_drop_kw(drop), **_doc_kw(doc, qkv.device))
         o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.drop)
         ctx.save_for_backward(x, o, lse, kv_lens if kv_lens is not None else torch.empty(0),
                               pos if pos is not None else torch.empty(0), table if table is not None else torch.empty(0))
@@ -201,8 +268,8 @@ class _FlashQKV(torch.autograd.Function):
         # the projection's bias gradient (column sums of dqkv) from the one-block kernel (BiasLink); not with rope,
         # which rotates dqkv after the kernel
         bl, dsum, ss, lpb = ctx.bias_link, None, None, None
-        if bl is not None and bl.pb is not None and not has_rope and \
-                C.flash_bwd_one_block(D, S, S, H, Hkv, causal, B):
+        if bl is not None and bl.pb is not None and not has_rope and "doc_lo" not in ctx.drop and \
+                C.flash_bwd_one_block(D, S, S, H, Hkv, causal, B):  # (a document mask has no one-block form)
             lpb = bl.pb
             ss = lpb.store.slot_for_write(lpb)
             dsum = ss.view(lpb.shape) if ss is not None else torch.empty(lpb.shape, device=x.device,
@@ -214,13 +281,13 @@ class _FlashQKV(torch.autograd.Function):
             bl.done = True
         if has_rope:
             C.rope_(dqkv[:, : (H + Hkv) * D], pos, table, True)
-        return (dqkv,) + (None,) * 14
+        return (dqkv,) + (None,) * 15
 
 
 def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int, causal: bool = False,
                   kv_lens: Optional[torch.Tensor] = None, rope: Optional[tuple] = None,
                   scale: Optional[float] = None, bias_link=None, rope_in_place: bool = False,
-                  rope_applied: bool = False, dropout: Optional[tuple] = None):
+                  rope_applied: bool = False, dropout: Optional[tuple] = None, doc: Optional[tuple] = None):
     """Self-attention of a packed QKV projection ``qkv`` [B*S, (heads + 2*kv_heads) * head_dim] (q heads, then k,
     then v); ``rope`` = (pos [B*S] int32, table) applies rotary embeddings to q and k. Returns o [B, S, heads, D].
     GPU bf16: one fused path (``_FlashQKV``); otherwise the split + ``attention`` reference composition.
@@ -234,11 +301,18 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
     returns the gradient of the UN-rotated projection output (dqkv rotated back), which is what that linear's backward
     takes. ``dropout`` = (p, DropoutState, site): dropout on the probabilities, fused on the ``flash_dropout_fused``
     shapes (see the module docstring; the bias gradient stays a one-block feature); other shapes take the split +
-    ``attention`` composition, which counts the fallback."""
+    ``attention`` composition, which counts the fallback. ``doc`` = (lo, hi): the document mask of ``attention``
+    (causal, no ``kv_lens``, no dropout); with ``rope`` the caller passes positions that restart at every document."""
     D = head_dim
     scale = scale or 1.0 / math.sqrt(D)
     W = (heads + 2 * kv_heads) * D
     drop = _drop_spec(dropout)
+    if doc is not None:
+        if not causal or kv_lens is not None or dropout is not None:
+            raise ValueError("attention_qkv: a document mask needs causal=True and takes neither kv_lens nor dropout")
+        if any(tuple(t.shape) != (B, S) or t.dtype != torch.int32 for t in doc):
+            raise ValueError("attention_qkv: doc = (lo, hi) must be two int32 [B, S] tensors "
+                             "(ops.attention.doc_bounds)")
     fused = qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128) and qkv.shape[-1] == W and \
         W % 8 == 0 and qkv.is_contiguous()
     if fused and drop is not None:
@@ -246,7 +320,7 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
     if fused:
         pos, table = rope if rope is not None else (None, None)
         return _FlashQKV.apply(qkv, B, S, heads, kv_heads, D, causal, kv_lens, scale, pos, table, bias_link,
-                               rope_in_place, rope_applied, drop)
+                               rope_in_place, rope_applied, drop, doc)
     if rope_applied:
         raise RuntimeError("attention_qkv: q / k rotated by the projection epilogue need the fused GPU path")
     q, k, v = qkv.split([heads * D, kv_heads * D, kv_heads * D], dim=-1)
@@ -255,4 +329,4 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
 
         q, k = _nn.rope(q, rope[0], rope[1]), _nn.rope(k, rope[0], rope[1])
     return attention(q.reshape(B, S, heads, D), k.reshape(B, S, kv_heads, D), v.reshape(B, S, kv_heads, D),
-                     causal=causal, kv_lens=kv_lens, scale=scale, dropout=dropout)
+                     causal=causal, kv_lens=kv_lens, scale=scale, dropout=dropout, doc=doc)

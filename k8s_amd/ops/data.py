@@ -7,8 +7,10 @@ host runs ``ops.reference.augment``, the same definition in torch (float64), whi
 
 ``mlm_batch`` turns N rows of an int64 table into a BERT pretraining batch in one launch: ``[CLS] A [SEP] B [SEP] pad``,
 token types, exactly ``n`` masked positions drawn without replacement from a counter generator, the 80 / 10 / 10 rule
-and the compacted [N, P] labels and positions. ``causal_batch`` gathers causal-LM windows. Both are integer
-arithmetic: the GPU kernels match ``ops.reference.mlm_batch`` / ``causal_batch`` (the CPU path) bit for bit.
+and the compacted [N, P] labels and positions. ``causal_batch`` gathers causal-LM windows, and ``causal_doc_batch``
+also returns every token's document bounds inside its row, its position inside the document and labels that stop at
+document ends. All are integer arithmetic: the GPU kernels match ``ops.reference.mlm_batch`` / ``causal_batch`` /
+``causal_doc_batch`` (the CPU path) bit for bit.
 """
 from __future__ import annotations
 
@@ -72,3 +74,27 @@ def causal_batch(src: torch.Tensor, starts: torch.Tensor, S: int):
     if src.is_cuda:
         return tuple(_load_ext().causal_batch(src, starts, int(S)))
     return ref.causal_batch(src, starts, int(S))
+
+
+def doc_offsets(doc_tok, device) -> torch.Tensor:
+    """The documents' token offsets (int64 [D + 1], e.g. ``segments[docs]`` of a token split) checked once on the host
+    -- strictly ascending from 0, else ``ValueError`` -- and uploaded to ``device`` for ``causal_doc_batch``."""
+    t = torch.as_tensor(doc_tok).contiguous()
+    ref.check_doc_tok(t)
+    return t.to(device)
+
+
+def causal_doc_batch(src: torch.Tensor, starts: torch.Tensor, abs_starts: torch.Tensor, doc_tok: torch.Tensor, S: int,
+                     split_tokens: int = None):
+    """``causal_batch`` for rows that hold several documents, in one launch: ``(ids, labels, lo, hi, pos)``, ids and
+    labels int64 [N, S], the rest int32 [N, S]. ``starts`` (int64 [N], host) index ``src``; ``abs_starts`` are the same
+    windows' positions in the split (equal to ``starts`` when ``src`` is the whole split); ``doc_tok`` is
+    ``doc_offsets``' tensor on ``src``'s device. ``lo`` / ``hi`` bound each token's document inside its row
+    (``ops.attention``'s ``doc=``), ``pos`` restarts at every document (what ``rope_`` / ``linear_rope`` take), and the
+    last token of a document carries the label -100. ``split_tokens``: ``doc_tok[-1]``, known to the caller from the
+    host copy (read back from the device when not given). Windows that leave ``src`` or the split are rejected before
+    the launch."""
+    if src.is_cuda:
+        total = int(doc_tok[-1]) if split_tokens is None else int(split_tokens)
+        return tuple(_load_ext().causal_doc_batch(src, starts, abs_starts, doc_tok, int(S), total))
+    return ref.causal_doc_batch(src, starts, abs_starts, doc_tok, int(S))

@@ -557,3 +557,38 @@ def causal_batch(src, starts, S: int):
         raise ValueError("a window [start, start + %d + 1) leaves the %d tokens of src" % (S, T))
     at = starts.to(src.device).unsqueeze(1) + torch.arange(S, dtype=torch.int64, device=src.device)
     return _token_values(src, at), _token_values(src, at + 1)
+
+
+def check_doc_tok(doc_tok) -> None:
+    """The documents' token offsets: int64 [D + 1], strictly ascending from 0."""
+    doc_tok = torch.as_tensor(doc_tok)
+    if doc_tok.dtype != torch.int64 or doc_tok.dim() != 1 or doc_tok.shape[0] < 2 or int(doc_tok[0]) != 0 or \
+            not bool((doc_tok[1:] > doc_tok[:-1]).all()):
+        raise ValueError("doc_tok must be int64 [D + 1] and ascend strictly from 0")
+
+
+def causal_doc_batch(src, starts, abs_starts, doc_tok, S: int):
+    """The definition of ``ops.data.causal_doc_batch``: ``causal_batch`` with document boundaries. ``starts`` index
+    ``src``, ``abs_starts`` are the same windows' positions in the split and ``doc_tok`` int64 [D + 1] the documents'
+    token offsets. For element (n, j) at p = abs_starts[n] + j with d the last document starting at or before p:
+    lo = max(doc_tok[d] - abs_starts[n], 0), hi = min(doc_tok[d + 1] - abs_starts[n], S), pos = j - lo (int32 [N, S]),
+    ids = src[start + j] and labels = src[start + j + 1], or -100 where p is its document's last token."""
+    src = torch.as_tensor(src)
+    starts, abs_starts, doc_tok = torch.as_tensor(starts), torch.as_tensor(abs_starts), torch.as_tensor(doc_tok)
+    ids, labels = causal_batch(src, starts, S)
+    S = int(S)
+    check_doc_tok(doc_tok.cpu())
+    if abs_starts.dtype != torch.int64 or abs_starts.shape != starts.shape:
+        raise ValueError("abs_starts must be int64 [N] like starts")
+    if bool(((abs_starts < 0) | (abs_starts > int(doc_tok[-1]) - S - 1)).any()):
+        raise ValueError("a window [start, start + %d + 1) leaves the %d tokens of the split" % (S, int(doc_tok[-1])))
+    dev = src.device
+    doc_tok, ab = doc_tok.to(dev), abs_starts.to(dev).unsqueeze(1)
+    j = torch.arange(S, dtype=torch.int64, device=dev)
+    p = ab + j
+    d = (torch.searchsorted(doc_tok, p.contiguous(), right=True) - 1).clamp(0, doc_tok.shape[0] - 2)
+    end = doc_tok[d + 1]
+    lo = (doc_tok[d] - ab).clamp(min=0)
+    hi = (end - ab).clamp(max=S)
+    labels = torch.where(p + 1 < end, labels, torch.full_like(labels, -100))
+    return ids, labels, lo.to(torch.int32), hi.to(torch.int32), (j - lo).to(torch.int32)

@@ -4,7 +4,7 @@
                                                    [--size 40]
     python -m k8s_amd.tools.make_dataset --out DIR --cifar10-batches DIR_WITH_PICKLES
     python -m k8s_amd.tools.make_dataset --out DIR --toy-tokens [--seed 0] [--train-docs 512] [--val-docs 64]
-                                                   [--vocab 512]
+                                                   [--vocab 512] [--segments-per-doc 2 6]
 
 ``--toy``: a learnable set that is a pure function of its seed. Class k is a fixed random 5x5x3 uint8 prototype
 (numpy Philox key 7, the same for every seed) upscaled to ``--size`` (x8 to 40x40 by default, nearest cell at other
@@ -12,7 +12,7 @@ sizes); Gaussian noise of sigma 48 is added and the result clipped to uint8; lab
 
 ``--toy-tokens``: a learnable token set (``k8s_amd.data.tokens``) that is a pure function of its seed, for the BERT
 and Llama models. Specials pad 0, cls 1, sep 2, mask 3; 8 topics, topic k owning the ids 8 + 63 k .. 8 + 63 k + 62. A
-document draws one topic, 2 to 6 segments and 4 to 12 tokens per segment; a segment's first token is uniform in the
+document draws one topic, 2 to 6 segments (``--segments-per-doc LO HI``) and 4 to 12 tokens per segment; a segment's first token is uniform in the
 topic's slice and each later one is ``base + (5 * prev_off + 1) mod 63`` with probability 0.9, else uniform in the
 slice.
 
@@ -66,13 +66,15 @@ TOY_TOPICS, TOY_SLICE, TOY_FIRST_ID = 8, 63, 8
 TOY_SPECIAL = {"pad": 0, "cls": 1, "sep": 2, "mask": 3}
 
 
-def toy_token_split(seed: int, which: int, documents: int):
-    """(tokens int64 [T], segments int64 [G + 1], docs int64 [D + 1]) of split number ``which`` for ``seed``."""
+def toy_token_split(seed: int, which: int, documents: int, segments_per_doc=(2, 6)):
+    """(tokens int64 [T], segments int64 [G + 1], docs int64 [D + 1]) of split number ``which`` for ``seed``; a
+    document holds ``segments_per_doc`` = (lo, hi) segments, both ends included."""
+    seg_lo, seg_hi = int(segments_per_doc[0]), int(segments_per_doc[1])
     g = np.random.Generator(np.random.Philox(np.random.SeedSequence([0x70F7, int(seed), int(which)])))
     tokens, segments, docs = [], [0], [0]
     for _ in range(documents):
         base = TOY_FIRST_ID + TOY_SLICE * int(g.integers(0, TOY_TOPICS))
-        for _ in range(int(g.integers(2, 7))):
+        for _ in range(int(g.integers(seg_lo, seg_hi + 1))):
             n = int(g.integers(4, 13))
             follow, fresh = g.random(n) < 0.9, g.integers(0, TOY_SLICE, size=n)
             off = int(fresh[0])
@@ -85,14 +87,17 @@ def toy_token_split(seed: int, which: int, documents: int):
     return np.asarray(tokens, dtype=np.int64), np.asarray(segments, dtype=np.int64), np.asarray(docs, dtype=np.int64)
 
 
-def make_toy_tokens(out: str, seed: int = 0, train_docs: int = 512, val_docs: int = 64, vocab: int = 512) -> None:
+def make_toy_tokens(out: str, seed: int = 0, train_docs: int = 512, val_docs: int = 64, vocab: int = 512,
+                    segments_per_doc=(2, 6)) -> None:
     if vocab < TOY_FIRST_ID + TOY_TOPICS * TOY_SLICE:
         raise ValueError("--vocab must be at least %d (8 specials and reserved ids, 8 topics of 63 ids)"
                          % (TOY_FIRST_ID + TOY_TOPICS * TOY_SLICE))
     if train_docs < 2 or val_docs < 2:
         raise ValueError("--train-docs and --val-docs must be at least 2 (sentence pairs need another document)")
-    write_token_dataset(out, vocab, {"train": toy_token_split(seed, 0, train_docs),
-                                     "val": toy_token_split(seed, 1, val_docs)}, TOY_SPECIAL)
+    if not 1 <= int(segments_per_doc[0]) <= int(segments_per_doc[1]):
+        raise ValueError("--segments-per-doc LO HI must satisfy 1 <= LO <= HI")
+    write_token_dataset(out, vocab, {"train": toy_token_split(seed, 0, train_docs, segments_per_doc),
+                                     "val": toy_token_split(seed, 1, val_docs, segments_per_doc)}, TOY_SPECIAL)
 
 
 def read_cifar_batch(path: str):
@@ -132,10 +137,13 @@ def main(argv=None) -> int:
     ap.add_argument("--train-docs", type=int, default=512)
     ap.add_argument("--val-docs", type=int, default=64)
     ap.add_argument("--vocab", type=int, default=512)
+    ap.add_argument("--segments-per-doc", type=int, nargs=2, default=[2, 6], metavar=("LO", "HI"),
+                    help="--toy-tokens: segments per document, both ends included (documents of HI * 8 tokens on "
+                         "average at LO = HI)")
     a = ap.parse_args(argv)
     try:
         if a.toy_tokens:
-            make_toy_tokens(a.out, a.seed, a.train_docs, a.val_docs, a.vocab)
+            make_toy_tokens(a.out, a.seed, a.train_docs, a.val_docs, a.vocab, tuple(a.segments_per_doc))
         elif a.toy:
             make_toy(a.out, a.seed, a.train, a.val, a.classes, a.size)
         else:

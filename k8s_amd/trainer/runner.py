@@ -20,6 +20,8 @@ process exit code (`/root/reference/pkg/trainer/training.go:45-73`):
   replica and it resumes from the latest checkpoint;
 * evaluation (``--eval-every N`` / ``--eval-only``): forward-only passes over held-out synthetic batches or the
   fixed training batch, an ``eval`` event (loss, top-1 / top-5 or perplexity) and ``eval/*`` TensorBoard scalars;
+* ``--doc-mask`` (Llama on ``--data-dir``): document-boundary attention masks, positions that restart per document
+  and no label across a boundary (``ops.data.causal_doc_batch``, the DOC forms of the flash kernels);
 * data: synthetic batches of the model's shape, or ``--data-dir``: a dataset directory (``k8s_amd.data``; images for
   the ResNet models, tokens for BERT and Llama) whose ``train`` split feeds the fused augmentation / token batch
   kernel and whose ``val`` split is the held-out evaluation data;
@@ -120,6 +122,10 @@ def parse(argv=None):
     ap.add_argument("--data-resident-gb", type=float, default=4.0,
                     help="--data-dir: a split up to this many GiB is uploaded once; a larger one is streamed batch "
                          "by batch by a background thread (0: always streamed)")
+    ap.add_argument("--doc-mask", action="store_true",
+                    help="Llama on --data-dir: attention stays inside each token's document, RoPE positions restart "
+                         "at every document and a document's last token predicts nothing (the dataset needs its "
+                         "segments and docs arrays)")
     ap.add_argument("--accum-steps", type=int, default=1,
                     help="gradient accumulation: micro-batches of --batch per optimizer step (global batch = batch x "
                          "world x N). A step stays an optimizer step everywhere (--steps, warmup, logging, "
@@ -362,6 +368,10 @@ def train(a) -> int:
         config_error = "--data-dir cannot be combined with --graph (a data step is not captured)"
     elif a.data_dir and a.eval_data == "train":
         config_error = "--data-dir evaluates its val split: not with --eval-data train"
+    elif a.doc_mask and not a.data_dir:
+        config_error = "--doc-mask masks the document boundaries of a token dataset: it needs --data-dir"
+    elif a.doc_mask and not a.model.startswith("llama"):
+        config_error = "--doc-mask is implemented for the Llama models only, not %s" % a.model
     if config_error:
         print("error: %s" % config_error, file=sys.stderr, flush=True)
         return EXIT_PERMANENT
@@ -395,6 +405,8 @@ def train(a) -> int:
         from k8s_amd.models.registry import dataset_plan, token_dataset_plan
 
         data = {"dir": a.data_dir, "resident_gb": a.data_resident_gb, "seed": a.seed, "rank": rank, "world": world}
+        if a.doc_mask:
+            data["doc_mask"] = True
         try:
             if a.model.startswith("resnet"):
                 data.update(augment=a.augment or "crop", crop_pad=4 if a.crop_pad is None else a.crop_pad)
