@@ -112,6 +112,48 @@ Tensor conv3x3_dgrad_bnstats(Tensor gy, Tensor wt, Tensor x, Tensor gamma, Tenso
   return dx;
 }
 
+// A 3x3 / pad-1 convolution (stride 1 or 2) on the 4-wave GEMM with gathered A rows (gemm256.hip ConvGather), always:
+// a shape outside conv3x3_w4_ok raises (ops/conv.py asks conv3x3_w4_use, the policy, first). y = conv(x, w), w
+// [K, 3, 3, C]; with `stats` (zeroed fp32 [conv_stat_replicas, 2, K]) also the BatchNorm statistics of the stored y.
+Tensor conv3x3_w4(const Tensor& x, const Tensor& w, int64_t stride, float* stats, const uint16_t* bn_x,
+                  const float* bn_tab, float* bn_sums) {
+  check_bf16_dense(x, 4, "x"); check_bf16_dense(w, 4, "w");
+  const auto [N, H, W, C, K, R, S] = conv_geom(x, w);
+  TORCH_CHECK(R == 3 && S == 3 && k8s_amd::conv3x3_w4_ok(N, H, W, C, K, (int)stride),
+              "conv3x3_w4: 3x3, stride 1 or 2, C % 64 == 0, K % 256 == 0, N Ho Wo % 256 == 0, x below 2^31 elements");
+  const int Ho = conv_out(H, 3, stride, 1, 1), Wo = conv_out(W, 3, stride, 1, 1);
+  Tensor y = torch::empty({N, Ho, Wo, K}, x.options());
+  const SkScratch sk(k8s_amd::conv3x3_w4_plan(N, H, W, C, K, (int)stride), x);
+  launch_conv3x3_w4(cbf(x), cbf(w), bf(y), N, H, W, C, K, (int)stride, stats, bn_x, bn_tab, bn_sums, sk.slab_ptr(),
+                    sk.sync_ptr(), cur_stream());
+  return y;
+}
+Tensor conv3x3_w4_fwd(Tensor x, Tensor w, int64_t stride, OptTensor stats) {
+  if (stats) {
+    check_stat_sums(*stats, w.size(0), "stats", true);
+    TORCH_CHECK(stats->device() == x.device(), "stats: on x's device");
+  }
+  return conv3x3_w4(x, w, stride, stats ? f32(*stats) : nullptr, nullptr, nullptr, nullptr);
+}
+// The stride-1 data gradient dx = conv(gy, wt) the same way (wt = conv_dgrad_wtrans(w), [C, 3, 3, K]); with x, gamma,
+// beta, mean, invstd and sums (together) also the BatchNorm-backward sums of dx for the relu(BN(x)) that produced the
+// convolution's input, as conv3x3_dgrad_bnstats takes them. sums: zeroed fp32 [conv_stat_replicas, 2, C].
+Tensor conv3x3_w4_dgrad(Tensor gy, Tensor wt, OptTensor x, OptTensor gamma, OptTensor beta, OptTensor mean,
+                        OptTensor invstd, OptTensor sums) {
+  if (!sums) {
+    TORCH_CHECK(!x && !gamma && !beta && !mean && !invstd, "conv3x3_w4_dgrad: x, gamma, beta, mean, invstd come with sums");
+    return conv3x3_w4(gy, wt, 1, nullptr, nullptr, nullptr, nullptr);
+  }
+  TORCH_CHECK(x && gamma && beta && mean && invstd, "conv3x3_w4_dgrad: sums need x, gamma, beta, mean and invstd");
+  TORCH_CHECK(gy.dim() == 4 && wt.dim() == 4 && x->dim() == 4 && x->size(0) == gy.size(0) && x->size(1) == gy.size(1) &&
+                  x->size(2) == gy.size(2) && x->size(3) == wt.size(0),
+              "x: the shape of dx");
+  bn_bwd_sums(*x, *mean, *sums, {}, gamma, beta, invstd, {}, {}, {});  // (the checks of the relu kind)
+  TORCH_CHECK(x->device() == gy.device() && sums->device() == gy.device(), "x and sums: on gy's device");
+  Tensor tab = torch::cat({*gamma, *beta, *mean, *invstd});
+  return conv3x3_w4(gy, wt, 1, nullptr, cbf(*x), f32(tab), f32(*sums));
+}
+
 // The fused backward of a 1x1 / stride-1 convolution whose input is relu(BN(x)) normalised on load (bwd1x1_fused.hip):
 // returns dz [M, C] = gy [M, K] . w [K, C]; writes (accumulate: adds) dw [K, C] fp32 = gy^T . relu(bf16(x scale +
 // shift)) with xform = fp32 [2, C] (scale | shift), and adds the BatchNorm-backward sums of dz (g = relu_on(x) ? dz : 0:
@@ -191,6 +233,24 @@ Tensor bwd1x1_fused(Tensor gy, Tensor x, Tensor w, OptTensor xform, OptTensor ga
   return dz;
 }
 
+// The 3x3 / pad-1 weight gradient dw [K, 3, 3, C] fp32 (+)= dy^T . im2col(x) on the 4-wave GEMM with gathered B rows
+// (gemm256.hip), always: a shape outside conv3x3_w4_wgrad_ok raises (conv_wgrad asks conv3x3_w4_wgrad_use first).
+void conv3x3_w4_wgrad(Tensor x, Tensor dy, Tensor dw, int64_t stride, bool accumulate) {
+  check_bf16_dense(x, 4, "x"); check_bf16_dense(dy, 4, "dy");
+  check_cuda(dw, "dw"); check_dtype(dw, at::kFloat, "dw"); check_aligned(dw, "dw");
+  const auto [N, H, W, C, K, R, S] = conv_geom(x, dw);
+  TORCH_CHECK(R == 3 && S == 3 && k8s_amd::conv3x3_w4_wgrad_ok(N, H, W, C, K, (int)stride),
+              "conv3x3_w4_wgrad: 3x3, stride 1 or 2, C % 256 == 0, K % 256 == 0, N Ho Wo % 64 == 0");
+  TORCH_CHECK(dy.size(0) == N && dy.size(1) == conv_out(H, 3, stride, 1, 1) && dy.size(2) == conv_out(W, 3, stride, 1, 1) &&
+                  dy.size(3) == K && dy.device() == x.device() && dw.device() == x.device(),
+              "dy shape / device mismatch");
+  Tensor ws;
+  const long nws = k8s_amd::conv3x3_w4_wgrad_workspace(N, H, W, C, K, (int)stride);
+  if (nws) ws = torch::empty({nws}, dw.options());
+  launch_conv3x3_w4_wgrad(cbf(x), cbf(dy), f32(dw), N, H, W, C, K, (int)stride, accumulate, nws ? f32(ws) : nullptr,
+                          cur_stream());
+}
+
 // dw[K,R,S,C] fp32 (+)= dy^T . im2col(x)
 void conv_wgrad(Tensor x, Tensor dy, Tensor dw, int64_t stride, int64_t pad, int64_t dil, int64_t splits,
                 bool accumulate, OptTensor xform) {
@@ -202,6 +262,12 @@ void conv_wgrad(Tensor x, Tensor dy, Tensor dw, int64_t stride, int64_t pad, int
   TORCH_CHECK(dy.dim() == 4 && dy.size(0) == N && dy.size(1) == Ho && dy.size(2) == Wo && dy.size(3) == K,
               "dy shape mismatch");
   const float* xf = xform_ptr(xform, C);
+  // the 256 / 512-channel 3x3 layers on a chip-filling grid: the 4-wave GEMM with gathered B rows (gemm256.hip)
+  if (!xf && splits <= 0 && R == 3 && S == 3 && pad == 1 && dil == 1 &&
+      k8s_amd::conv3x3_w4_wgrad_use(N, H, W, C, K, (int)stride)) {
+    conv3x3_w4_wgrad(x, dy, dw, stride, accumulate);
+    return;
+  }
   if (dil == 1 && Ho == H && Wo == W && H == W && k8s_amd::wgrad3x3_tiled_ok(C, K, R, S, (int)stride, (int)pad, W)) {
     auto wsp = torch::empty({k8s_amd::wgrad3x3_tiled_workspace(N, H, W, C)}, dw.options());
     launch_wgrad3x3_tiled(cbf(x), cbf(dy), f32(wsp), f32(dw), N, H, W, C, accumulate, cur_stream(), xf);
@@ -271,6 +337,23 @@ void bind_conv(pybind11::module_& m) {
   });
   m.def("conv3x3_dgrad_bnstats", &conv3x3_dgrad_bnstats,
         "3x3 stride-1 data gradient with the BatchNorm-backward sums of a relu(BN(x)) input (conv3x3.hip)");
+  m.def("conv3x3_w4_fwd", &conv3x3_w4_fwd, "x"_a, "w"_a, "stride"_a, "stats"_a = py::none(),
+        "3x3 pad-1 convolution (stride 1 / 2) on the 4-wave GEMM with gathered A rows (gemm256.hip ConvGather)");
+  m.def("conv3x3_w4_dgrad", &conv3x3_w4_dgrad, "gy"_a, "wt"_a, "x"_a = py::none(), "gamma"_a = py::none(),
+        "beta"_a = py::none(), "mean"_a = py::none(), "invstd"_a = py::none(), "sums"_a = py::none(),
+        "3x3 stride-1 data gradient on the same kernel, optionally with the BatchNorm-backward sums of dx");
+  m.def("conv3x3_w4_ok", &k8s_amd::conv3x3_w4_ok, "N"_a, "H"_a, "W"_a, "C"_a, "K"_a, "stride"_a,
+        "the contract of conv3x3_w4_fwd / _dgrad (a data gradient: C and K exchanged)");
+  m.def("conv3x3_w4_use", &k8s_amd::conv3x3_w4_use, "N"_a, "H"_a, "W"_a, "C"_a, "K"_a, "stride"_a, "dgrad"_a,
+        "the policy: K8S_AMD_CONV3X3_W4, a chip-filling grid and the shapes where the route measured faster");
+  m.def("conv3x3_w4_wgrad", &conv3x3_w4_wgrad, "x"_a, "dy"_a, "dw"_a, "stride"_a, "accumulate"_a,
+        "3x3 pad-1 weight gradient (stride 1 / 2) on the 4-wave GEMM with gathered B rows");
+  m.def("conv3x3_w4_wgrad_ok", &k8s_amd::conv3x3_w4_wgrad_ok, "N"_a, "H"_a, "W"_a, "C"_a, "K"_a, "stride"_a);
+  m.def("conv3x3_w4_wgrad_use", &k8s_amd::conv3x3_w4_wgrad_use, "N"_a, "H"_a, "W"_a, "C"_a, "K"_a, "stride"_a,
+        "whether conv_wgrad routes this layer there: K8S_AMD_CONV3X3_W4 and a chip-filling grid");
+  m.def("conv3x3_w4_tail_splits", [](int N, int H, int W, int C, int K, int stride) {
+    return k8s_amd::conv3x3_w4_plan(N, H, W, C, K, stride).sk;
+  }, "K splits of the launch's stream-K tail (1: no tail)");
   m.def("conv_fwd_subgrid", &conv_fwd_subgrid, "x"_a, "w"_a, "pad"_a, "Hs"_a, "Ws"_a, "out"_a, "stride"_a, "a"_a, "b"_a,
         "accumulate"_a = false, "bn_x"_a = py::none(), "bn_mask"_a = py::none(), "bn_mean"_a = py::none(),
         "bn_sums"_a = py::none(), "bn_gamma"_a = py::none(), "bn_beta"_a = py::none(), "bn_invstd"_a = py::none());

@@ -917,11 +917,37 @@ __device__ __forceinline__ void copy_out_bnbwd(uint16_t* __restrict__ C, const u
   add_column_sums(sm, sq, sums, smem, stg, rep, N, n0);
 }
 
-template <bool AMN, bool BMN, bool X>
+// Gathered A (GS == 1): A is not a matrix but an NHWC tensor [.][H][W][C], and row m of the GEMM is output pixel
+// (n, ho, wo) of its 3x3 / pad 1 / stride `stride` convolution: the implicit GEMM's im2col rows, K = 9 C. With
+// C % 64 == 0 a 64-deep stage lies inside one tap (r, s) = t / (C / 64), so an A stage is the same 256 rows x 128 B as
+// a K-major stage -- the LDS image, the swizzle on the source chunk and everything after the DMA are unchanged; only
+// each row's address differs: x + ((n H + ho stride - 1 + r) W + wo stride - 1 + s) C + c0. A lane's row of each of its
+// 8 pieces is fixed for the whole K loop: its byte offset at tap (0, 0) (goff, mod 2^32: the first row's is below x)
+// and a 9-bit mask of the taps inside the image (gmask) are decoded once per tile; the stage's tap offset and tap bit
+// are wave-uniform (gather_stage). A tap outside the image -- which, shifted, may well be a valid address in the
+// neighbouring row or image -- reads 16 B of zeros from g_w4_zero (the idiom of ConvA::at / g_c3_zero). The pieces go
+// by global_load_lds with a per-lane address; B keeps its buffer loads.
+//
+// Gathered B (GS == 2, the weight gradient dW [K][9 C] = dy^T . im2col(x), both operands MN-major): B's k-row is pixel
+// m and its columns the C channels of one tap. With C % 256 == 0 a 256-column tile lies inside one tap -- a constant
+// of the workgroup -- and a lane touches two k-rows per stage, one per k-half (4 pieces each, 64 columns apart): it
+// decodes their (n, ho, wo) per stage (gather_stage: two FastDivs each) for the address and the validity. A (dy) keeps
+// its buffer loads.
+struct ConvGather {
+  int H, W, C, Ho, Wo, stride;
+  FastDiv dhw, dwo;  // / (Ho Wo), / Wo (GS == 2)
+};
+// source of the taps outside the image (GS == 2: a lane's 4 pieces read it at +0, 128, 256 and 384 B)
+__device__ __attribute__((aligned(64))) uint16_t g_w4_zero[256];
+
+template <bool AMN, bool BMN, bool X, int GS = 0>
 __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __restrict__ A, long lda,
                                                              const uint16_t* __restrict__ B, long ldb, g256::Epi E,
                                                              Fused F, int M, int N, int K, int kps,
-                                                             g256r::SkArgs SK) {
+                                                             g256r::SkArgs SK, ConvGather G) {
+  constexpr bool GA = GS == 1, GB = GS == 2;
+  static_assert(!GA || !AMN, "gathered A: K-major rows");
+  static_assert(!GB || (AMN && BMN && !X), "gathered B: the weight gradient's MN-major operands, fp32 output");
   __shared__ __attribute__((aligned(1024))) char smem[LDS_BYTES];
   void* Cv = E.c;
   const long ldc = E.ldc;
@@ -971,16 +997,81 @@ __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __r
   const int vb = BMN ? ((drow * (int)ldb) + (((lane & 7) ^ g256::mn128_swz(drow)) * 8)) * 2
                      : (drow * (int)ldb + lch * 8) * 2;
   const int sa = 64 * (int)lda, sb = 64 * (int)ldb;  // K-major: bytes between instruction i and i + 1 (32 rows)
+  // GA (ConvGather): piece p of this lane is row m0 + 32 p + drow, chunk lch
+  unsigned goff[GA ? 8 : 1], gmask[GA ? 8 : 1];
+  unsigned gs_off = 0, gs_bit = 0;  // the stage being issued: its tap's byte offset (+ channel slice) and tap bit
+  int g_tap = 0, g_cs = 0;          // ... and the tap / channel slice of the next one
+  const int g_cpt = GA ? G.C >> 6 : 1;
+  if constexpr (GA) {
+    const int hw = G.Ho * G.Wo;
+#pragma unroll
+    for (int p = 0; p < 8; ++p) {
+      const int row = m0 + p * 32 + drow;
+      const int n = row / hw, rem = row - n * hw, ho = rem / G.Wo, wo = rem - ho * G.Wo;
+      const int hi0 = ho * G.stride - 1, wi0 = wo * G.stride - 1;
+      goff[p] = (unsigned)(((n * G.H + hi0) * G.W + wi0) * G.C + lch * 8) * 2u;
+      unsigned mk = 0;
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+          if ((unsigned)(hi0 + r) < (unsigned)G.H && (unsigned)(wi0 + s) < (unsigned)G.W) mk |= 1u << (r * 3 + s);
+      gmask[p] = mk;
+    }
+    const int t0 = (int)(koff >> 6);  // a stream-K split starts inside the reduction
+    g_tap = t0 / g_cpt;
+    g_cs = t0 - g_tap * g_cpt;
+  }
+  // GB: this lane's two k-rows (pixels) of the stage being issued, as source pointers for column block 0
+  const char* gb[2] = {nullptr, nullptr};
+  int g_m = 0;  // ... and the first pixel of the next stage
+  int gb_dh = 0, gb_dw = 0, gb_c = 0;
+  if constexpr (GB) {
+    const int tap = n0 / G.C, r = (tap * 11) >> 5;
+    gb_dh = r - 1;
+    gb_dw = tap - 3 * r - 1;
+    gb_c = n0 - tap * G.C + ((lane & 7) ^ g256::mn128_swz(drow)) * 8;
+    g_m = (int)koff + drow;
+  }
+  auto gather_stage = [&]() {  // before a stage's gathered pieces: its tap, wave-uniform; then on to the next stage
+    if constexpr (GB) {
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int m = g_m + 32 * h, n = G.dhw.div(m), rem = m - n * (G.Ho * G.Wo), ho = G.dwo.div(rem);
+        const int hi = ho * G.stride + gb_dh, wi = (rem - ho * G.Wo) * G.stride + gb_dw;
+        const bool ok = (unsigned)hi < (unsigned)G.H && (unsigned)wi < (unsigned)G.W;
+        gb[h] = ok ? reinterpret_cast<const char*>(B + ((long)((n * G.H + hi) * G.W + wi) * G.C + gb_c))
+                   : reinterpret_cast<const char*>(g_w4_zero);
+      }
+      g_m += KS;
+    }
+    if constexpr (GA) {
+      const int r = (g_tap * 11) >> 5, s = g_tap - 3 * r;  // tap / 3, tap % 3 for tap < 9
+      gs_off = (unsigned)((r * G.W + s) * G.C + g_cs * 64) * 2u;
+      gs_bit = 1u << g_tap;
+      if (++g_cs == g_cpt) {
+        g_cs = 0;
+        ++g_tap;
+      }
+    }
+  };
   // piece p (0-7: A instruction p, 8-15: B instruction p - 8) of stage t into buffer dbuf
   auto dma = [&](int p, int t, int dbuf) {
     char* d = smem + dbuf * STAGE + wid * 1024 + (p & 7) * 4096 + (p >> 3) * STAGE_A;
     auto* l = (__attribute__((address_space(3))) void*)d;
     if (p < 8) {
-      if constexpr (AMN)
+      if constexpr (GA) {
+        const char* src = (gmask[p & 7] & gs_bit) ? reinterpret_cast<const char*>(A) + (goff[p & 7] + gs_off)
+                                                  : reinterpret_cast<const char*>(g_w4_zero);
+        glds16(src, d);
+      } else if constexpr (AMN)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, l, 16, va, ((p >> 2) * 32 * (int)lda + (p & 3) * 64) * 2 +
                                                                      t * (KS * 2) * (int)lda, 0, 0);
       else
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, l, 16, va, p * sa + t * (KS * 2), 0, 0);
+    } else if constexpr (GB) {
+      const int q = p - 8;
+      glds16(gb[q >> 2] + (q & 3) * 128, d);
     } else if constexpr (BMN) {
       const int q = p - 8;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, l, 16, vb, ((q >> 2) * 32 * (int)ldb + (q & 3) * 64) * 2 +
@@ -1092,9 +1183,11 @@ __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __r
       bj[j] = E.bias ? *reinterpret_cast<const f32x4_t*>(E.bias + n0 + wc * 128 + j * 16 + 4 * (lane >> 4))
                      : f32x4_t{0.f, 0.f, 0.f, 0.f};
   }
+  gather_stage();
 #pragma unroll
   for (int p = 0; p < 16; ++p) dma(p, 0, 0);
   if (nst > 1) {
+    gather_stage();
 #pragma unroll
     for (int p = 0; p < 16; ++p) dma(p, 1, 1);
     g256::vmwait<16>();  // stage 0 landed, stage 1 in flight
@@ -1142,6 +1235,7 @@ __global__ void __launch_bounds__(THREADS, 1) gemm_w4_kernel(const uint16_t* __r
   int s = 0;
   for (; s + 2 < nst; ++s) {
     first(s);
+    gather_stage();
     mm(0, 64, a1, b1, a0, b0, T_{}, (s & 1) ^ 1, 0, T_{}, s + 2, s & 1);  // + stage s + 1's reads, stage s + 2's DMA
     second_done();
   }
@@ -1347,7 +1441,7 @@ namespace g4 {
 // launched.
 static int launch(const uint16_t* A, long lda, bool a_kmajor, const uint16_t* B, long ldb, bool b_kmajor, bool x,
                   const g256::Epi& e, const Fused& f, int M, int N, int K, int splits, float* sk_slabs, int* sk_sync,
-                  hipStream_t st) {
+                  hipStream_t st, const ConvGather* gather = nullptr, int gs = 0) {
   const int tiles = (M / 256) * (N / 256);
   g256r::SkArgs sk{tiles, 1, nullptr, nullptr};
   int blocks = tiles, kps = K, ysplits = 1;
@@ -1362,9 +1456,22 @@ static int launch(const uint16_t* A, long lda, bool a_kmajor, const uint16_t* B,
       blocks = plan.full + (tiles - plan.full) * plan.sk;
     }
   }
+  if (gather && gs == 2) {  // the gathered-B form: the weight gradient's MN-major operands, plain fp32 output
+    if (a_kmajor || b_kmajor || x) throw std::runtime_error("gemm_w4: gathered B is MN-major, fp32 output");
+    hipLaunchKernelGGL((gemm_w4_kernel<true, true, false, 2>), dim3(blocks, ysplits), dim3(THREADS), 0, st, A, lda, B,
+                       ldb, e, f, M, N, K, kps, sk, *gather);
+    return ysplits;
+  }
+  if (gather) {  // the gathered-A form: both operands K-major, the X copy-outs
+    if (!a_kmajor || !b_kmajor || !x || splits > 1) throw std::runtime_error("gemm_w4: gathered A is K-major, X, unsplit");
+    hipLaunchKernelGGL((gemm_w4_kernel<false, false, true, 1>), dim3(blocks, ysplits), dim3(THREADS), 0, st, A, lda,
+                       B, ldb, e, f, M, N, K, kps, sk, *gather);
+    return ysplits;
+  }
   auto go = [&](auto amn, auto bmn, auto xx) {
     hipLaunchKernelGGL((gemm_w4_kernel<decltype(amn)::value, decltype(bmn)::value, decltype(xx)::value>),
-                       dim3(blocks, ysplits), dim3(THREADS), 0, st, A, lda, B, ldb, e, f, M, N, K, kps, sk);
+                       dim3(blocks, ysplits), dim3(THREADS), 0, st, A, lda, B, ldb, e, f, M, N, K, kps, sk,
+                       ConvGather{});
   };
   auto pick_x = [&](auto amn, auto bmn) {
     if (x) go(amn, bmn, std::true_type{});
@@ -1482,6 +1589,84 @@ void launch_gemm_w4_dgrad_bnstats(const uint16_t* A, const uint16_t* B, uint16_t
   f.bn_tab = tab;
   f.bn_sums = sums;
   g4::launch(A, K, true, B, N, false, true, g4::bf16_out(y, N), f, M, N, K, 1, sk_slabs, sk_sync, st);
+}
+
+// The gathered-A form (ConvGather): ResNet's 256- and 512-channel 3x3 convolutions -- forward with the BnStats
+// epilogue, stride-1 data gradient with BnBwdSums -- as the implicit GEMM M = N Ho Wo, N = K, K = 9 C.
+static int conv3x3_out(int in, int stride) { return (in - 1) / stride + 1; }  // 3x3, pad 1
+bool conv3x3_w4_ok(int N, int H, int W, int C, int K, int stride) {
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || (stride != 1 && stride != 2)) return false;
+  const long M = (long)N * conv3x3_out(H, stride) * conv3x3_out(W, stride);
+  // (the lanes' byte offsets into x are 32-bit: x below 2^31 elements; the output's rows are ints)
+  return C % 64 == 0 && K % 256 == 0 && M % 256 == 0 && (long)N * H * W * C < (1L << 31) && M < (1L << 31);
+}
+bool conv3x3_w4_use(int N, int H, int W, int C, int K, int stride, bool dgrad) {
+  const char* e = getenv("K8S_AMD_CONV3X3_W4");
+  if ((e && e[0] == '0') || !conv3x3_w4_ok(N, H, W, C, K, stride) || (dgrad && stride != 1)) return false;
+  // Measured per layer at batch 3072 (profiles/conv3x3_w4_ab.jsonl): against the generic implicit GEMM the route wins
+  // everywhere -- 28 -> 14 / 256 ch forward 0.83 -> 0.68 ms, 14 -> 7 / 512 ch 0.76 -> 0.58, 7x7 / 512 ch forward 0.68 ->
+  // 0.52 and data gradient 0.66 -> 0.57 -- but not against the staged-window kernel (14x14 / 256 ch: forward 0.64 ->
+  // 0.63, inside that kernel's run-to-run spread; data gradient with the sums 0.67 -> 0.69): its layers stay there.
+  if (stride == 1 && conv3x3_eligible(H, W, C, K, 3, 3, 1, 1, 1)) return false;
+  const long M = (long)N * conv3x3_out(H, stride) * conv3x3_out(W, stride);
+  return (M / 256) * (K / 256) >= planner_cus();  // at least one wave of tiles
+}
+Gemm256Plan conv3x3_w4_plan(int N, int H, int W, int C, int K, int stride) {
+  return gemm256_plan(N * conv3x3_out(H, stride) * conv3x3_out(W, stride), K, 9 * C);
+}
+void launch_conv3x3_w4(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int C, int K,
+                       int stride, float* stats, const uint16_t* bn_x, const float* bn_tab, float* bn_sums,
+                       float* sk_slabs, int* sk_sync, hipStream_t st) {
+  if (!conv3x3_w4_ok(N, H, W, C, K, stride)) throw std::runtime_error("conv3x3_w4: shape outside the contract");
+  if (stats && bn_sums) throw std::runtime_error("conv3x3_w4: statistics or BatchNorm-backward sums, not both");
+  if (bn_sums && (!bn_x || !bn_tab)) throw std::runtime_error("conv3x3_w4: BatchNorm-backward sums need bn_x, bn_tab");
+  const g4::ConvGather g{H, W, C, conv3x3_out(H, stride), conv3x3_out(W, stride), stride, FastDiv{}, FastDiv{}};
+  const int M = N * g.Ho * g.Wo;
+  g4::Fused f{stats ? g4::EpiKind::BnStats : bn_sums ? g4::EpiKind::BnBwdSums : g4::EpiKind::Linear};
+  f.stats = stats;
+  f.bn_x = bn_x;
+  f.bn_tab = bn_tab;
+  f.bn_sums = bn_sums;
+  g4::launch(x, C, true, w, 9L * C, true, true, g4::bf16_out(y, K), f, M, K, 9 * C, 1, sk_slabs, sk_sync, st, &g, 1);
+}
+
+// The weight gradient the same way (gathered B): dw [K][3][3][C] fp32 (+)= dy^T . im2col(x), the GEMM M = K, N = 9 C
+// over the N Ho Wo pixels, tall-K split over gridDim.y into the slabs of `ws` as launch_gemm256's weight gradients.
+bool conv3x3_w4_wgrad_ok(int N, int H, int W, int C, int K, int stride) {
+  if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || (stride != 1 && stride != 2)) return false;
+  const long M = (long)N * conv3x3_out(H, stride) * conv3x3_out(W, stride);
+  return C % 256 == 0 && K % 256 == 0 && M % 64 == 0 && (long)N * H * W * C < (1L << 31) && M * K < (1L << 31);
+}
+// (the weight gradient won on all four layer shapes, the tiled kernel's 14x14 included: 0.65 -> 0.57 ms, the generic
+// split-K GEMM's 1.05-1.15 -> 0.56-0.62 -- so its policy is the switch and a chip-filling grid)
+bool conv3x3_w4_wgrad_use(int N, int H, int W, int C, int K, int stride) {
+  const char* e = getenv("K8S_AMD_CONV3X3_W4");
+  if ((e && e[0] == '0') || !conv3x3_w4_wgrad_ok(N, H, W, C, K, stride)) return false;
+  const int M = N * conv3x3_out(H, stride) * conv3x3_out(W, stride);
+  const long blocks = (long)(K / 256) * (9 * C / 256) * conv3x3_w4_wgrad_splits(N, H, W, C, K, stride);
+  return blocks >= 3L * planner_cus() / 4 && M >= 512;
+}
+int conv3x3_w4_wgrad_splits(int N, int H, int W, int C, int K, int stride) {
+  return gemm256_choose_splits(K, 9 * C, N * conv3x3_out(H, stride) * conv3x3_out(W, stride));
+}
+long conv3x3_w4_wgrad_workspace(int N, int H, int W, int C, int K, int stride) {
+  const int sp = conv3x3_w4_wgrad_splits(N, H, W, C, K, stride);
+  return sp > 1 ? (long)sp * K * 9 * C : 0;
+}
+void launch_conv3x3_w4_wgrad(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, int C, int K,
+                             int stride, bool accumulate, float* ws, hipStream_t st) {
+  if (!conv3x3_w4_wgrad_ok(N, H, W, C, K, stride)) throw std::runtime_error("conv3x3_w4_wgrad: outside the contract");
+  const g4::ConvGather g{H, W, C, conv3x3_out(H, stride), conv3x3_out(W, stride), stride,
+                         make_fastdiv(conv3x3_out(H, stride) * conv3x3_out(W, stride)),
+                         make_fastdiv(conv3x3_out(W, stride))};
+  const int M = N * g.Ho * g.Wo, splits = conv3x3_w4_wgrad_splits(N, H, W, C, K, stride);
+  if (splits > 1 && !ws) throw std::runtime_error("conv3x3_w4_wgrad: the tall-K split needs its workspace");
+  const long KN = (long)K * 9 * C;
+  const g256::Epi e{splits > 1 ? (void*)ws : (void*)dw, 9L * C, nullptr, nullptr, 1, 0,
+                    (splits == 1 && accumulate) ? 1 : 0, 1.f, splits > 1 ? KN : 0};
+  const int ysplits = g4::launch(dy, K, false, x, C, false, false, e, g4::Fused{g4::EpiKind::Linear}, K, 9 * C, M,
+                                 splits, nullptr, nullptr, st, &g, 2);
+  if (splits > 1) splitk_reduce(ws, ysplits, KN, dw, accumulate, st);
 }
 
 // Stream-K tail plan for a grid of 256 x 256 tiles on P = planner_cus() CUs (one block per CU; 256 on MI355X): with

@@ -222,6 +222,29 @@ void launch_gemm_w4_dgrad_bnstats(const uint16_t* A, const uint16_t* B, uint16_t
                                   hipStream_t st);
 void launch_gemm_w4_stats(const uint16_t* A, long lda, const uint16_t* B, long ldb, uint16_t* y, int M, int N, int K,
                           float* stats, float* sk_slabs, int* sk_sync, hipStream_t st);
+// gemm256.hip: a 3x3 / pad-1 / dilation-1 convolution (stride 1 or 2) as an implicit GEMM on the 4-wave kernel, its A
+// rows gathered from the NHWC x [N][H][W][C] (ConvGather): y [N][Ho][Wo][K] = conv(x, w [K][3][3][C]). A stride-1 data
+// gradient is the same call on dy with conv_dgrad_wtrans(w). One epilogue at most: `stats` (BnStats of the stored y,
+// zeroed [kConvStatReplicas][2][K]) or bn_x / bn_tab / bn_sums (BnBwdSums, the operands of
+// launch_gemm_w4_dgrad_bnstats); neither: the plain store. conv3x3_w4_ok is the contract (C % 64, K % 256, whole
+// 256-row tiles, x below 2^31 elements); conv3x3_w4_use the policy -- $K8S_AMD_CONV3X3_W4 (0: off, read per call), a
+// chip-filling grid and the shapes where the route measured faster than the kernels it replaces.
+struct Gemm256Plan;
+bool conv3x3_w4_ok(int N, int H, int W, int C, int K, int stride);
+bool conv3x3_w4_use(int N, int H, int W, int C, int K, int stride, bool dgrad);
+Gemm256Plan conv3x3_w4_plan(int N, int H, int W, int C, int K, int stride);  // its stream-K tail, for the workspace
+void launch_conv3x3_w4(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int C, int K,
+                       int stride, float* stats, const uint16_t* bn_x, const float* bn_tab, float* bn_sums,
+                       float* sk_slabs, int* sk_sync, hipStream_t st);
+// ... and its weight gradient dw [K][3][3][C] fp32 (+)= dy^T . im2col(x) with gathered B rows: C % 256 == 0 (a 256-column
+// tile lies inside one tap), K % 256 == 0, N Ho Wo % 64 == 0; the tall-K split (conv3x3_w4_wgrad_splits > 1) goes
+// through `ws` (conv3x3_w4_wgrad_workspace floats) and splitk_reduce. _use: the switch, and a chip-filling grid.
+bool conv3x3_w4_wgrad_ok(int N, int H, int W, int C, int K, int stride);
+bool conv3x3_w4_wgrad_use(int N, int H, int W, int C, int K, int stride);
+int conv3x3_w4_wgrad_splits(int N, int H, int W, int C, int K, int stride);
+long conv3x3_w4_wgrad_workspace(int N, int H, int W, int C, int K, int stride);
+void launch_conv3x3_w4_wgrad(const uint16_t* x, const uint16_t* dy, float* dw, int N, int H, int W, int C, int K,
+                             int stride, bool accumulate, float* ws, hipStream_t st);
 bool gemm_w4_rope_ok(int M, int N, int K, long lda, long ldb, int rot_cols);
 void launch_gemm_w4_rope(const uint16_t* A, long lda, const uint16_t* B, long ldb, uint16_t* y, int M, int N, int K,
                          const int* pos, const float* table, int rot_cols, float* sk_slabs, int* sk_sync,

@@ -46,7 +46,9 @@ STATS = {"hip_fwd": 0, "aten_fwd": 0, "hip_wgrad": 0, "aten_wgrad": 0, "hip_dgra
          # a downsample block's two BatchNorms (nn.bn_act_dual) holding two nn.Bn3Links: backwards that deferred both
          # apply halves, apply passes run for a deferred half after all, and launches of the fused 1x1 backward's
          # final form (the downsample convolution's; with or without the downsample BatchNorm's backward on load)
-         "dual_onload": 0, "dual_apply": 0, "fused_final": 0}
+         "dual_onload": 0, "dual_apply": 0, "fused_final": 0,
+         # 3x3 forwards on the 4-wave GEMM with gathered A rows (_w4_3x3; counted in hip_fwd as well)
+         "w4_3x3_fwd": 0}
 # data-gradient route name -> times executed. The names name the data gradient's contract (what it accumulates onto,
 # which sums it takes), not the kernel: the fused 1x1 backward's final form is counted under the name _plan_dgrad gives
 # its data gradient ("tile_final_sums"), the kernel that ran in STATS["fused_final"].
@@ -106,12 +108,28 @@ def _vendor(op, x, w, stride, padding):
             warnings.warn("k8s_amd conv: %s is outside the MFMA kernels' shape contract; using ATen" % key)
 
 
+def _w4_3x3(C_, x, w, stride, padding, dgrad=False):
+    """Whether the 3x3 / pad-1 convolution of ``x`` [N, H, W, C] with ``w`` [K, 3, 3, C] goes to the 4-wave GEMM with
+    gathered A rows (gemm256.hip ConvGather; ``dgrad``: the stride-1 data gradient, ``x`` is dy [N, H, W, K], which
+    is correlated with conv_dgrad_wtrans(w) [C, 3, 3, K]). The extension's ``conv3x3_w4_use`` is the policy: K8S_AMD_CONV3X3_W4=0 (read per call)
+    switches the route off, and it takes only chip-filling grids of the shapes where it measured faster."""
+    use = getattr(C_, "conv3x3_w4_use", None)  # (the planners' test stubs carry no such predicate)
+    K, R, S, C = (w.shape[3], 3, 3, w.shape[0]) if dgrad else w.shape
+    N, H, W = x.shape[:3]
+    return (use is not None and w.shape[1] == 3 and w.shape[2] == 3 and padding == 1 and x.is_contiguous()
+            and w.is_contiguous() and use(N, H, W, C, K, stride, dgrad))
+
+
 def conv_fwd(x, w, stride, padding, stats=None):
     """y = conv(x, w); with ``stats`` (zeroed fp32 [R, 2, K]) the epilogue also accumulates the per-channel
     sum / sum-of-squares of y for the following BatchNorm (HIP path only)."""
     if fwd_uses_hip(x, w, stride, padding):
         STATS["hip_fwd"] += 1
-        return _load().conv_fwd(x, w, stride, padding, 1, False, None, 0, stats)
+        C_ = _load()
+        if _w4_3x3(C_, x, w, stride, padding):
+            STATS["w4_3x3_fwd"] += 1
+            return C_.conv3x3_w4_fwd(x, w, stride, stats)
+        return C_.conv_fwd(x, w, stride, padding, 1, False, None, 0, stats)
     _vendor("fwd", x, w, stride, padding)
     return _nhwc(F.conv2d(_nchw(x), _nchw(w), None, stride, padding))
 
@@ -208,6 +226,10 @@ def _plan_dgrad(C_, gy, w, padding, addend, bn_link):
     N, Ho, Wo = gy.shape[:3]
     masked = addend is not None and not torch.is_tensor(addend)  # nn.MaskedGrad: (dy, packed ReLU mask)
     kind = _link_kind(bn_link, (N, Ho + R - 1 - 2 * padding, Wo + S - 1 - 2 * padding, C))
+    # the 256 / 512-channel 3x3 layers on a chip-filling grid: the 4-wave GEMM with gathered A rows, with the sums of a
+    # BatchNorm + ReLU where the staged-window route would take them (and at 7x7, where no other route does)
+    if _w4_3x3(C_, gy, w, 1, padding, True):
+        return "w4_3x3_relu_sums" if BSTATS_3X3 and kind == "relu" and addend is None else "w4_3x3_flipped"
     if (BSTATS_3X3 and kind == "relu" and addend is None and R == 3 and S == 3 and padding == 1 and Ho == Wo
             and C_.conv3x3_staged_ok(Ho, Wo, C, K, 3, 3, 1, 1)):
         return "conv3x3_relu_sums"
@@ -253,6 +275,16 @@ def _dgrad_hip(C_, gy, w, padding, addend=None, bn_link=None):
             addend = addend.materialize()
         dx = C_.conv_fwd(gy, C_.conv_dgrad_wtrans(w), 1, R - 1 - padding, 1, False, None, 0, None)
         return dx if addend is None else dx.add_(addend)
+    if route == "w4_3x3_flipped":
+        if addend is not None and not torch.is_tensor(addend):
+            addend = addend.materialize()
+        dx = C_.conv3x3_w4_dgrad(gy, C_.conv_dgrad_wtrans(w))
+        return dx if addend is None else dx.add_(addend)
+    if route == "w4_3x3_relu_sums":
+        sums = _bn_sums(C_, ln, C, gy.device)
+        dx = C_.conv3x3_w4_dgrad(gy, C_.conv_dgrad_wtrans(w), ln.x, ln.gamma, ln.beta, ln.mean, ln.invstd, sums)
+        ln.deposit(sums, None, dx)
+        return dx
     if route == "conv3x3_relu_sums":
         sums = _bn_sums(C_, ln, C, gy.device)
         dx = C_.conv3x3_dgrad_bnstats(gy, C_.conv_dgrad_wtrans(w), ln.x, ln.gamma, ln.beta, ln.mean, ln.invstd, sums)

@@ -118,7 +118,7 @@ class BnStatLink:
 
     Kinds, and the data-gradient routes of ``ops.conv`` that can serve each:
       relu  a non-residual BatchNorm + ReLU (ResNet's bn1 / bn2), the ReLU decision recomputed from the affine:
-            conv3x3_relu_sums, tile_relu_sums, parity_relu_sums, fused_1x1
+            conv3x3_relu_sums, w4_3x3_relu_sums, tile_relu_sums, parity_relu_sums, fused_1x1
       mask  a residual BatchNorm, ``y = relu(BN(x) + r)``, with the packed ReLU mask: short_mask_sums, tile_mask_sums
             (a masked residual addend: an identity block's conv1); short_entry_pending then parity_complete_sums (a
             stage-entry block's conv1, then its downsample)
