@@ -34,6 +34,37 @@ void fill_doc(Args& a, const OptTensor& doc_lo, const OptTensor& doc_hi, bool wi
   a.doc_hi = doc_hi->data_ptr<int>();
 }
 
+// span_lo / span_hi (optional, both or neither): the span mask of non-causal self-attention at head dim 64, int32
+// [B, Sq]; span_tile 0 (the dispatch's default), 64 or 128. The kernels clamp what the tables hold; here what the host
+// can see is checked, the index limits of the SPAN forms (flash_span_ok) included.
+template <class Args>
+void fill_span(Args& a, long D, long max_token_stride, const OptTensor& span_lo, const OptTensor& span_hi,
+               int64_t span_tile, bool with_lens, bool with_drop) {
+  if (!span_lo && !span_hi) {
+    TORCH_CHECK(span_tile == 0, "span_tile needs span_lo and span_hi");
+    return;
+  }
+  TORCH_CHECK(span_lo && span_hi, "span_lo and span_hi must be given together");
+  TORCH_CHECK(!a.causal, "a span mask is bidirectional and cannot be combined with causal");
+  TORCH_CHECK(a.Sq == a.Sk, "a span mask is defined for self-attention (Sq == Sk) only");
+  TORCH_CHECK(!with_lens, "a span mask cannot be combined with kv_lens");
+  TORCH_CHECK(!with_drop, "a span mask cannot be combined with dropout");
+  TORCH_CHECK(!a.doc_lo, "a span mask cannot be combined with a document mask");
+  TORCH_CHECK(D == 64, "the span kernels take head dim 64 only, got ", D);
+  for (const Tensor* t : {&*span_lo, &*span_hi}) {
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt, "span_lo / span_hi must be int32 GPU tensors");
+    TORCH_CHECK(t->is_contiguous() && t->dim() == 2 && t->size(0) == a.B && t->size(1) == a.Sq,
+                "span_lo / span_hi must be contiguous [B, Sq]");
+  }
+  TORCH_CHECK(span_tile == 0 || span_tile == 64 || span_tile == 128, "span_tile must be 0, 64 or 128, got ", span_tile);
+  TORCH_CHECK(k8s_amd::flash_span_ok((int)D, a.B, a.Sq, a.Sk, a.Hq, max_token_stride),
+              "the span kernels index Sq < 2^24, B * Hq * Sq < 2^31 and token strides below 2^24 elements; got B = ", a.B,
+              ", Sq = ", a.Sq, ", Hq = ", a.Hq, ", largest token stride ", max_token_stride);
+  a.span_lo = span_lo->data_ptr<int>();
+  a.span_hi = span_hi->data_ptr<int>();
+  a.span_tile = (int)span_tile;
+}
+
 // what AttnFwdArgs and AttnBwdArgs share: q / k / v [B, S, H, D] with their strides, the shape, the softmax scale and
 // kv_lens. Returns the head dim D.
 template <class Args>
@@ -59,11 +90,15 @@ long fill_qkv(Args& a, const Tensor& q, const Tensor& k, const Tensor& v, bool c
 // form, or Sq and Sk multiples of 64)
 std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, bool causal, OptTensor kv_lens, double scale,
                               OptTensor drop_state, int64_t drop_thr, double drop_scale, int64_t drop_site,
-                              OptTensor doc_lo, OptTensor doc_hi) {
+                              OptTensor doc_lo, OptTensor doc_hi, OptTensor span_lo, OptTensor span_hi,
+                              int64_t span_tile) {
   AttnFwdArgs a;
   const long D = fill_qkv(a, q, k, v, causal, kv_lens, scale);
   const long B = a.B, Sq = a.Sq, Hq = a.Hq, Sk = a.Sk, Hkv = a.Hkv;
   fill_doc(a, doc_lo, doc_hi, kv_lens.has_value(), drop_state.has_value());
+  // (o is allocated contiguous below: its token stride is Hq * D)
+  fill_span(a, D, std::max({a.sqs, a.sks, a.svs, Hq * D}), span_lo, span_hi, span_tile, kv_lens.has_value(),
+            drop_state.has_value());
   if (drop_state) {
     TORCH_CHECK(k8s_amd::flash_dropout_fused((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, 1),
                 "attention dropout needs a flash_dropout_fused shape (D = 64: one-block, or Sq, Sk multiples of 64)");
@@ -84,12 +119,15 @@ std::vector<Tensor> flash_fwd(Tensor q, Tensor k, Tensor v, bool causal, OptTens
 std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, bool causal,
                               OptTensor kv_lens, double scale, OptTensor dqkv, OptTensor dbias, OptTensor drop_state,
                               int64_t drop_thr, double drop_scale, int64_t drop_site, OptTensor doc_lo,
-                              OptTensor doc_hi) {
+                              OptTensor doc_hi, OptTensor span_lo, OptTensor span_hi, int64_t span_tile) {
   AttnBwdArgs a;
   const long D = fill_qkv(a, q, k, v, causal, kv_lens, scale);
   const long B = a.B, Sq = a.Sq, Hq = a.Hq, Sk = a.Sk, Hkv = a.Hkv;
   fill_doc(a, doc_lo, doc_hi, kv_lens.has_value(), drop_state.has_value());
   check_attn_operand(o, "o", D); check_attn_operand(dO, "dO", D);
+  // (the gradients are contiguous tensors or views of the packed buffer: token stride at most (Hq + 2 Hkv) * D)
+  fill_span(a, D, std::max({a.sqs, a.sks, a.svs, (long)o.stride(1), (long)dO.stride(1), (Hq + 2 * Hkv) * D}), span_lo,
+            span_hi, span_tile, kv_lens.has_value(), drop_state.has_value());
   TORCH_CHECK(dO.sizes() == q.sizes() && o.sizes() == q.sizes(), "dO / o must match q");
   check_cuda(lse, "lse"); check_dtype(lse, at::kFloat, "lse");
   const long ld = (Sq + 127) / 128 * 128;
@@ -97,8 +135,8 @@ std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o,
               "lse must be the [B, Hq, round_up(Sq, 128)] tensor flash_fwd returned");
   const long Wp = (Hq + 2 * Hkv) * D;  // the packed QKV projection's width
   a.dkv_split = k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal);
-  // (a document mask always takes the three-kernel form)
-  const bool one_block = !a.doc_lo &&
+  // (a document or span mask always takes the three-kernel form)
+  const bool one_block = !a.doc_lo && !a.span_lo &&
                          k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv, a.dkv_split);
   if (dqkv) {
     TORCH_CHECK(Sq == Sk, "packed QKV gradient needs self-attention (Sq == Sk)");
@@ -107,6 +145,7 @@ std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o,
   }
   if (dbias) {  // the packed projection's bias gradient from the one-block kernel's column partials
     TORCH_CHECK(!a.doc_lo, "dbias is not available with a document mask (no one-block form)");
+    TORCH_CHECK(!a.span_lo, "dbias is not available with a span mask (no one-block form)");
     TORCH_CHECK(dqkv && one_block, "dbias needs the packed gradient and a one-block shape (flash_bwd_one_block)");
     check_channel_f32(*dbias, Wp, "dbias");
   }
@@ -159,10 +198,18 @@ std::vector<Tensor> flash_bwd(Tensor dO, Tensor q, Tensor k, Tensor v, Tensor o,
 
 void bind_attention(pybind11::module_& m) {
   m.def("flash_fwd", &flash_fwd, "q"_a, "k"_a, "v"_a, "causal"_a, "kv_lens"_a, "scale"_a, "drop_state"_a = py::none(),
-        "drop_thr"_a = 0, "drop_scale"_a = 1.0, "drop_site"_a = 0, "doc_lo"_a = py::none(), "doc_hi"_a = py::none());
+        "drop_thr"_a = 0, "drop_scale"_a = 1.0, "drop_site"_a = 0, "doc_lo"_a = py::none(), "doc_hi"_a = py::none(),
+        "span_lo"_a = py::none(), "span_hi"_a = py::none(), "span_tile"_a = 0);
   m.def("flash_bwd", &flash_bwd, "dO"_a, "q"_a, "k"_a, "v"_a, "o"_a, "lse"_a, "causal"_a, "kv_lens"_a, "scale"_a,
         "dqkv"_a = py::none(), "dbias"_a = py::none(), "drop_state"_a = py::none(), "drop_thr"_a = 0,
-        "drop_scale"_a = 1.0, "drop_site"_a = 0, "doc_lo"_a = py::none(), "doc_hi"_a = py::none());
+        "drop_scale"_a = 1.0, "drop_site"_a = 0, "doc_lo"_a = py::none(), "doc_hi"_a = py::none(),
+        "span_lo"_a = py::none(), "span_hi"_a = py::none(), "span_tile"_a = 0);
+  m.def("flash_span_ok", [](int64_t D, int64_t B, int64_t Sq, int64_t Sk, int64_t Hq, int64_t max_token_stride) {
+          return k8s_amd::flash_span_ok((int)D, B, Sq, Sk, Hq, max_token_stride);
+        }, "whether the span forms of flash_fwd / flash_bwd index this shape (D = 64, Sq == Sk < 2^24, B * Hq * Sq < 2^31, "
+           "token strides < 2^24)");
+  m.def("flash_span_tile", [](int64_t S) { return k8s_amd::flash_span_tile((int)S); },
+        "keys per tile the span forms take by default");
   m.def("flash_bwd_one_block", [](int64_t D, int64_t Sq, int64_t Sk, int64_t Hq, int64_t Hkv, bool causal, int64_t B) {
           return k8s_amd::flash_bwd_one_block((int)D, (int)Sq, (int)Sk, (int)Hq, (int)Hkv,
                                               k8s_amd::flash_dkv_splits((int)B, (int)Sq, (int)Sk, (int)Hkv, causal));

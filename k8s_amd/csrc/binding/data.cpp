@@ -81,8 +81,8 @@ void check_host_i64(const Tensor& t, int64_t cols, const char* name) {
 // src: the tokens on the GPU; table int64 [N, 6] on the host, rows (a0, la, b0, lb, n, ord); special (pad, cls, sep,
 // mask). Every row is validated here before anything is allocated or launched; then the table is uploaded through
 // pinned memory and the kernel (which clamps once more) runs on the current stream.
-std::vector<Tensor> mlm_batch(Tensor src, Tensor table, int64_t S, int64_t P, int64_t vocab,
-                              std::vector<int64_t> special, int64_t seed, int64_t stream) {
+bool check_mlm_args(const Tensor& src, const Tensor& table, int64_t S, int64_t P, int64_t vocab,
+                    const std::vector<int64_t>& special, int64_t stream) {
   const bool u16 = check_token_src(src);
   TORCH_CHECK(vocab >= 2 && vocab <= 0x7fffffffLL, "vocab must be in [2, 2^31 - 1], got ", vocab);
   TORCH_CHECK(!u16 || vocab <= 65536, "uint16 tokens need vocab <= 65536, got ", vocab);
@@ -104,6 +104,13 @@ std::vector<Tensor> mlm_batch(Tensor src, Tensor table, int64_t S, int64_t P, in
     TORCH_CHECK(n >= 1 && n <= P && n <= la + lb, "table row ", r, ": n = ", n, " must be in [1, min(P, la + lb)]");
     TORCH_CHECK(ord >= 0, "table row ", r, ": negative ordinal");
   }
+  return u16;
+}
+
+std::vector<Tensor> mlm_batch(Tensor src, Tensor table, int64_t S, int64_t P, int64_t vocab,
+                              std::vector<int64_t> special, int64_t seed, int64_t stream) {
+  const bool u16 = check_mlm_args(src, table, S, P, vocab, special, stream);
+  const int64_t T = src.size(0), N = table.size(0);
   const k8s_amd::TokSpecial sp{(int)special[0], (int)special[1], (int)special[2], (int)special[3]};
   auto dtable = table.pin_memory().to(src.device(), /*non_blocking=*/true);
   auto opt = src.options().dtype(at::kLong);
@@ -114,6 +121,45 @@ std::vector<Tensor> mlm_batch(Tensor src, Tensor table, int64_t S, int64_t P, in
                    (uint64_t)seed, (int)stream, ids.data_ptr<int64_t>(), types.data_ptr<int64_t>(),
                    labels.data_ptr<int64_t>(), positions.data_ptr<int64_t>(), cur_stream());
   return {ids, types, labels, positions};
+}
+
+// mlm_batch without padding: the N samples back to back in one stream of T rows. cu int64 [N + 1] on the host, the
+// samples' first rows: cu[0] = 0 and cu[n + 1] - cu[n] = la + lb + 3 of table row n; T is cu[N] rounded up to a
+// multiple of 128. Everything mlm_batch validates is validated, then cu and T, all before anything is allocated or
+// launched. Returns ids, token_types, pos (int64 [T]), labels, rows (int64 [N, P]), cls_rows (int64 [N]) and the span
+// bounds lo, hi (int32 [1, T]).
+std::vector<Tensor> mlm_batch_unpadded(Tensor src, Tensor table, Tensor cu, int64_t T, int64_t S, int64_t P,
+                                       int64_t vocab, std::vector<int64_t> special, int64_t seed, int64_t stream) {
+  const bool u16 = check_mlm_args(src, table, S, P, vocab, special, stream);
+  const int64_t Tn = src.size(0), N = table.size(0);
+  TORCH_CHECK(cu.device().is_cpu(), "cu must be a CPU tensor (it is validated on the host, then uploaded)");
+  check_dtype(cu, at::kLong, "cu");
+  TORCH_CHECK(cu.dim() == 1 && cu.is_contiguous() && cu.size(0) == N + 1, "cu must be a contiguous int64 [N + 1] with "
+              "N = ", N, " table rows");
+  const int64_t* c = cu.data_ptr<int64_t>();
+  const int64_t* t = table.data_ptr<int64_t>();
+  TORCH_CHECK(c[0] == 0, "cu[0] must be 0, got ", c[0]);
+  for (int64_t r = 0; r < N; ++r)
+    TORCH_CHECK(c[r + 1] - c[r] == t[6 * r + 1] + t[6 * r + 3] + 3, "cu row ", r, ": ", c[r + 1], " - ", c[r],
+                " is not la + lb + 3 = ", t[6 * r + 1] + t[6 * r + 3] + 3);
+  TORCH_CHECK(T >= c[N], "T = ", T, " is below cu[N] = ", c[N]);
+  TORCH_CHECK(T % 128 == 0, "T = ", T, " must be a multiple of 128");
+  TORCH_CHECK(T - c[N] < 128, "T = ", T, " must be cu[N] = ", c[N], " rounded up to a multiple of 128");
+  TORCH_CHECK(T < (1L << 31), "mlm_batch_unpadded: too many stream rows in one call");
+  const k8s_amd::TokSpecial sp{(int)special[0], (int)special[1], (int)special[2], (int)special[3]};
+  auto both = torch::cat({table.reshape({-1}), cu});  // one upload: [6 N | N + 1]
+  auto dboth = both.pin_memory().to(src.device(), /*non_blocking=*/true);
+  auto opt = src.options().dtype(at::kLong), opt32 = src.options().dtype(at::kInt);
+  auto ids = torch::empty({T}, opt), types = torch::empty({T}, opt), pos = torch::empty({T}, opt);
+  auto labels = torch::empty({N, P}, opt), rows = torch::empty({N, P}, opt), cls_rows = torch::empty({N}, opt);
+  auto lo = torch::empty({1, T}, opt32), hi = torch::empty({1, T}, opt32);
+  ++g_token_launches;
+  launch_mlm_batch_unpadded(src.data_ptr(), u16, Tn, dboth.data_ptr<int64_t>(), dboth.data_ptr<int64_t>() + 6 * N, T,
+                            (int)N, (int)S, (int)P, (uint32_t)vocab, sp, (uint64_t)seed, (int)stream,
+                            ids.data_ptr<int64_t>(), types.data_ptr<int64_t>(), pos.data_ptr<int64_t>(),
+                            labels.data_ptr<int64_t>(), rows.data_ptr<int64_t>(), cls_rows.data_ptr<int64_t>(),
+                            lo.data_ptr<int>(), hi.data_ptr<int>(), cur_stream());
+  return {ids, types, pos, labels, rows, cls_rows, lo, hi};
 }
 
 // starts int64 [N] on the host: ids = src[start : start + S], labels = src[start + 1 : start + S + 1].
@@ -179,6 +225,9 @@ void bind_data(pybind11::module_& m) {
         "split_tokens"_a, "gather causal-LM windows with their document bounds, positions and boundary-aware labels");
   m.def("mlm_batch", &mlm_batch, "src"_a, "table"_a, "S"_a, "P"_a, "vocab"_a, "special"_a, "seed"_a, "stream"_a = 0,
         "assemble a BERT pretraining batch (ids, token types, MLM labels and positions) from a token array");
+  m.def("mlm_batch_unpadded", &mlm_batch_unpadded, "src"_a, "table"_a, "cu"_a, "T"_a, "S"_a, "P"_a, "vocab"_a,
+        "special"_a, "seed"_a, "stream"_a = 0,
+        "assemble a BERT pretraining batch as one unpadded token stream with its span bounds and gather rows");
   m.def("causal_batch", &causal_batch, "src"_a, "starts"_a, "S"_a, "gather causal-LM windows (ids, shifted labels)");
   m.def("token_launches", [] { return g_token_launches; }, "token batch kernels launched by this process");
   m.def("augment", &augment, "src"_a, "table"_a, "a"_a, "b"_a, "S"_a, "layout"_a,

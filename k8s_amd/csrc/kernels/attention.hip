@@ -122,14 +122,24 @@ __device__ __forceinline__ const uint16_t* kh_src(const uint16_t* base, long rst
 // last valid one: the key tiles start at the first one's tile, the tiles below the second are masked, and a wave
 // skips a tile that ends at or below the lo of its first query. Every lo is clamped into [0, query] before use, so no
 // table content moves a trip count outside [0, ntiles] or an address outside the tensors.
-template <int D, int TILE, int NB = 2, int QS = 2, bool DROP = false, bool DOC = false>
+// SPAN: bidirectional span mask (query i sees the keys span_lo[i] <= j < span_hi[i]; non-causal self-attention, D = 64,
+// NB = 2 forms). Both tables ascend along the row, so the block's key tiles are [lo(first query) / TILE,
+// ceil(hi(last query) / TILE)); the tiles from lo(last query) up to hi(first query) lie inside every query's span and
+// run the mask-free body, the others are masked per score, and a wave skips a tile outside [lo(its first query),
+// hi(its last query)). They run in the DOC forms' order: mask-free, leading, trailing. lo is clamped into [0, query]
+// and hi into [query + 1, Sq] before use, so the tile range stays inside [0, ntiles) and is never empty.
+template <int D, int TILE, int NB = 2, int QS = 2, bool DROP = false, bool DOC = false, bool SPAN = false>
 // (DROP on the one-tile form: 2 blocks per CU -- the mask's integer temporaries beside the 128-key score tile do not
 // fit the 168 registers of 3. On 64-key tiles they do: bounded to 3 blocks per CU like the plain form, which left
 // alone took 174 registers)
 // (DOC on 64-key tiles at D = 64: bounded to the 3 blocks per CU the plain form reaches; left alone it took 194)
-__global__ void __launch_bounds__(FA_THREADS, NB == 1 && !DROP ? (QS == 1 ? 4 : 3)
-                                                               : ((DROP || (DOC && D == 64)) && TILE == 64 ? 3 : 2))
+// (SPAN on 64-key tiles: the same bound)
+__global__ void __launch_bounds__(FA_THREADS,
+                                  NB == 1 && !DROP ? (QS == 1 ? 4 : 3)
+                                                   : ((DROP || ((DOC || SPAN) && D == 64)) && TILE == 64 ? 3 : 2))
 flash_fwd_kernel(AttnFwdArgs a) {
+  static_assert(!SPAN || (D == 64 && NB == 2 && !DROP && !DOC), "the span forms: D = 64, multi-tile, no dropout");
+  constexpr bool TAB = DOC || SPAN;  // the tiles come from a mask table and run out of key order
   constexpr int BM = 64 * QS;  // queries per block
   constexpr int FA_BN = TILE;  // keys per iteration
   constexpr int NI = FA_BN / 16;       // 16-key subtiles
@@ -170,6 +180,35 @@ flash_fwd_kernel(AttnFwdArgs a) {
     lo_w1 = lo_of(q0w + 16 * QS - 1);
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) lo_q[qs] = lo_of(q0w + qs * 16 + li);
+  }
+  // (SPAN) one past the block's last key tile, the first tile past the mask-free ones, hi of the wave's first and last
+  // query, hi of the lane's queries
+  int tend = ntiles, thi = 0, hi_w0 = 0, hi_w1 = 0, hi_q[QS];
+  if constexpr (SPAN) {
+    const int* lop = a.span_lo + (long)b * a.Sq;
+    const int* hip = a.span_hi + (long)b * a.Sq;
+    const int qe = a.Sq - 1;
+    auto lo_of = [&](int qi) {
+      const int qc = min(qi, qe);
+      return max(0, min(lop[qc], qc));
+    };
+    auto hi_of = [&](int qi) {
+      const int qc = min(qi, qe);
+      return min(a.Sq, max(hip[qc], qc + 1));
+    };
+    t0 = lo_of(q0) / FA_BN;  // lo <= q0, hi > q0: t0 < tend <= ntiles
+    tend = min(ntiles, (hi_of(q0 + BM - 1) + FA_BN - 1) / FA_BN);
+    tlo = (lo_of(q0 + BM - 1) + FA_BN - 1) / FA_BN;
+    thi = hi_of(q0) / FA_BN;
+    lo_w0 = lo_of(q0w);
+    lo_w1 = lo_of(q0w + 16 * QS - 1);
+    hi_w0 = hi_of(q0w);
+    hi_w1 = hi_of(q0w + 16 * QS - 1);
+#pragma unroll
+    for (int qs = 0; qs < QS; ++qs) {
+      lo_q[qs] = lo_of(q0w + qs * 16 + li);
+      hi_q[qs] = hi_of(q0w + qs * 16 + li);
+    }
   }
 
   const uint16_t* qp = a.q + (long)b * a.sqb + (long)h * a.sqh;
@@ -254,6 +293,10 @@ flash_fwd_kernel(AttnFwdArgs a) {
       doc_tl = min(max(tlo, t0), ntiles);
       doc_tf = max(doc_tl, tfull_);
       stage(0, seq(0) * FA_BN);
+    } else if constexpr (SPAN) {
+      doc_tl = min(max(tlo, t0), tend);
+      doc_tf = min(max(thi, doc_tl), tend);
+      stage(0, seq(0) * FA_BN);
     } else {
       stage(0, 0);
     }
@@ -266,11 +309,11 @@ flash_fwd_kernel(AttnFwdArgs a) {
   // (DOC: the tiles run out of order: tile t is the ti-th of the block's doc_n to run, and the buffers alternate in ti.
   // Passing the buffer and the next tile in as two values instead made the compiler wait for the prefetch, vmcnt(0),
   // in front of every tile's first LDS read: profiles/doc_mask_static.md)
-  const int doc_n = ntiles - t0;
+  const int doc_n = tend - t0;
   auto tile = [&](const int t, auto masked_tag, const int ti = 0) {
     constexpr bool MASKED = decltype(masked_tag)::value;
-    const int cur = DOC ? (ti & 1) : (NB > 1 ? (t & 1) : 0), key0 = t * FA_BN;
-    if constexpr (DOC) {
+    const int cur = TAB ? (ti & 1) : (NB > 1 ? (t & 1) : 0), key0 = t * FA_BN;
+    if constexpr (TAB) {
       if (ti + 1 < doc_n) stage(cur ^ 1, seq(ti + 1) * FA_BN);
     } else {
       if (NB > 1 && t + 1 < ntiles) stage(cur ^ 1, key0 + FA_BN);
@@ -279,6 +322,7 @@ flash_fwd_kernel(AttnFwdArgs a) {
     const char* tv = tk + KT;
     bool skip = MASKED && a.causal && key0 > q0w + 16 * QS - 1 + off;  // whole tile masked for this wave
     if constexpr (DOC && MASKED) skip = skip || key0 + FA_BN <= lo_w0;  // (every query's document starts past it)
+    if constexpr (SPAN && MASKED) skip = key0 + FA_BN <= lo_w0 || key0 >= hi_w1;  // (outside every query's span)
     if (!skip) {
       // ---- S^T = K Q^T
       f32x4_t s[NI][QS];
@@ -298,6 +342,7 @@ flash_fwd_kernel(AttnFwdArgs a) {
       // ---- online softmax (per query column = lane & 15)
       bool need_mask = MASKED && ((key0 + FA_BN > kv_end) || (a.causal && key0 + FA_BN - 1 > q0w + off));
       if constexpr (DOC && MASKED) need_mask = need_mask || key0 < lo_w1;
+      if constexpr (SPAN && MASKED) need_mask = key0 < lo_w1 || key0 + FA_BN > hi_w0;  // (hi <= Sk: the ragged end too)
 #pragma unroll
       for (int qs = 0; qs < QS; ++qs) {
         const int qi = q0w + qs * 16 + li;
@@ -309,7 +354,8 @@ flash_fwd_kernel(AttnFwdArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int key = key0 + i * 16 + g * 4 + r;
-              if constexpr (DOC) s[i][qs][r] = key > klim || key < lo_q[qs] ? -INFINITY : s[i][qs][r];
+              if constexpr (SPAN) s[i][qs][r] = key < lo_q[qs] || key >= hi_q[qs] ? -INFINITY : s[i][qs][r];
+              else if constexpr (DOC) s[i][qs][r] = key > klim || key < lo_q[qs] ? -INFINITY : s[i][qs][r];
               else s[i][qs][r] = key > klim ? -INFINITY : s[i][qs][r];
             }
         }
@@ -375,7 +421,7 @@ flash_fwd_kernel(AttnFwdArgs a) {
   int tfull = kv_end / FA_BN;
   if (a.causal) tfull = min(tfull, max(0, q0 + off + 1) / FA_BN);
   tfull = min(tfull, ntiles);
-  if constexpr (DOC) {
+  if constexpr (TAB) {
     const int nf = doc_tf - doc_tl;
     int i = 0;
     for (; i < nf; ++i) tile(seq(i), std::false_type{}, i);
@@ -461,8 +507,12 @@ __global__ void __launch_bounds__(256) flash_rowkey_kernel(uint32_t* rowkey, Dro
 // DOC: the document mask (key j is seen by the queries j <= i < doc_hi[j]; hi ascends along the row): the query walk
 // of a key block ends at the tile holding the last query of its last valid key's document, and the lane's hi, clamped
 // into [key + 1, Sq], joins the mask test.
-template <int D, int TILE, bool DROP = false, bool DOC = false>
+// SPAN: the span mask (key j is seen by the queries span_lo[j] <= i < span_hi[j], the tables ascending): the query
+// walk of a key block is [lo(first key) / TILE, ceil(hi(last key) / TILE)), never empty since lo <= key < hi after
+// the clamps, and the lane's lo and hi replace the causal test.
+template <int D, int TILE, bool DROP = false, bool DOC = false, bool SPAN = false>
 __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArgs a) {
+  static_assert(!SPAN || (D == 64 && !DROP && !DOC), "the span forms: D = 64, no dropout");
   constexpr int ND = D / 16, NK = D / 32;
   constexpr int FB_BM = TILE;              // queries per iteration
   constexpr int NQ = FB_BM / 16;           // 16-query subtiles
@@ -494,7 +544,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
 #pragma unroll
   for (int i = 0; i < ND; ++i) dka[i] = dva[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
-  const int qt0 = a.causal ? max(0, k0 - off) / FB_BM : 0;
+  int qt0 = a.causal ? max(0, k0 - off) / FB_BM : 0;
   int nqt = (a.Sq + FB_BM - 1) / FB_BM;
   int hi_k0 = 0, hi_key = 0;  // (DOC) hi of the block's first key (its smallest) and of the lane's key
   if constexpr (DOC) {
@@ -506,6 +556,25 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
     hi_k0 = hi_of(k0);
     hi_key = hi_of(kw + li);
     nqt = min(nqt, (hi_of(k0 + FB_BN - 1) + FB_BM - 1) / FB_BM);  // > qt0: that hi lies past k0
+  }
+  int lo_k1 = 0, lo_key = 0;  // (SPAN) lo of the block's last key (its largest) and of the lane's key; hi as DOC's
+  if constexpr (SPAN) {
+    const int* lop = a.span_lo + (long)b * a.Sq;
+    const int* hip = a.span_hi + (long)b * a.Sq;
+    auto lo_of = [&](int key) {
+      const int kc = min(key, a.Sk - 1);
+      return max(0, min(lop[kc], kc));
+    };
+    auto hi_of = [&](int key) {
+      const int kc = min(key, a.Sk - 1);
+      return min(a.Sq, max(hip[kc], kc + 1));
+    };
+    hi_k0 = hi_of(k0);
+    hi_key = hi_of(kw + li);
+    lo_k1 = lo_of(k0 + FB_BN - 1);
+    lo_key = lo_of(kw + li);
+    qt0 = lo_of(k0) / FB_BM;  // lo <= k0 < hi: qt0 < nqt
+    nqt = min(nqt, (hi_of(k0 + FB_BN - 1) + FB_BM - 1) / FB_BM);
   }
   const int per_head = nqt - qt0;
   const int total = (k0 < kv_end && per_head > 0) ? rep * per_head : 0;
@@ -607,6 +676,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
       // ---- P = exp2(S c - lse2), dS = P (dP - delta)
       bool need_mask = q0 + FB_BM > a.Sq || k0 + FB_BN > kv_end || (a.causal && k0 + FB_BN - 1 > q0 + off);
       if constexpr (DOC) need_mask = need_mask || q0 + FB_BM > hi_k0;
+      if constexpr (SPAN) need_mask = need_mask || q0 + FB_BM > hi_k0 || q0 < lo_k1;
 #pragma unroll
       for (int qs = 0; qs < NQ; ++qs) {
         f32x4_t l4 = *reinterpret_cast<const f32x4_t*>(tl + qs * 16 + g * 4);
@@ -619,6 +689,7 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
             const int qi = q0 + qs * 16 + g * 4 + r;
             bool ok = qi < a.Sq && key < kv_end && !(a.causal && key > qi + off);
             if constexpr (DOC) ok = ok && qi < hi_key;
+            if constexpr (SPAN) ok = ok && qi < hi_key && qi >= lo_key;
             sv[qs][r] = ok ? sv[qs][r] : -INFINITY;
             l4[r] = ok ? l4[r] : 0.f;
             d4[r] = ok ? d4[r] : 0.f;
@@ -734,8 +805,12 @@ __global__ void __launch_bounds__(256) flash_dkv_reduce_kernel(AttnBwdArgs a) {
 // DROP: the same dS as the dK/dV kernel; a lane's QS row keys come from the row-key table next to lse / delta.
 // DOC: the forward's document mask: the key-tile loop starts at the tile of the block's first query's lo, a wave skips
 // a tile that ends at or below the lo of its first query, and the lane's clamped lo joins the per-score select.
-template <int D, int TILE, int QS, bool DROP = false, bool DOC = false>
+// SPAN: the forward's span mask: the key tiles [lo(first query) / TILE, ceil(hi(last query) / TILE)) in key order, a
+// wave skips a tile outside [lo(its first query), hi(its last query)), and the lane's clamped lo and hi make the
+// per-score select.
+template <int D, int TILE, int QS, bool DROP = false, bool DOC = false, bool SPAN = false>
 __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 : 2) flash_bwd_dq_kernel(AttnBwdArgs a) {
+  static_assert(!SPAN || (D == 64 && QS == 1 && !DROP && !DOC), "the span forms: D = 64, QS = 1, no dropout");
   constexpr int ND = D / 16, NK = D / 32;
   constexpr int FB_BN = TILE;  // keys per iteration
   constexpr int NI = FB_BN / 16;
@@ -773,6 +848,31 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
     lo_w1 = lo_of(q0w + QW - 1);
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) lo_q[qs] = lo_of(q0w + 16 * qs + li);
+  }
+  int tend = ntiles, hi_w0 = 0, hi_w1 = 0, hi_q[QS];  // (SPAN) as the forward's
+  if constexpr (SPAN) {
+    const int* lop = a.span_lo + (long)b * a.Sq;
+    const int* hip = a.span_hi + (long)b * a.Sq;
+    const int qe = a.Sq - 1;
+    auto lo_of = [&](int qi) {
+      const int qc = min(qi, qe);
+      return max(0, min(lop[qc], qc));
+    };
+    auto hi_of = [&](int qi) {
+      const int qc = min(qi, qe);
+      return min(a.Sq, max(hip[qc], qc + 1));
+    };
+    t0 = lo_of(q0) / FB_BN;  // lo <= q0 < hi: t0 < tend <= ntiles
+    tend = min(ntiles, (hi_of(q0 + BMQ - 1) + FB_BN - 1) / FB_BN);
+    lo_w0 = lo_of(q0w);
+    lo_w1 = lo_of(q0w + QW - 1);
+    hi_w0 = hi_of(q0w);
+    hi_w1 = hi_of(q0w + QW - 1);
+#pragma unroll
+    for (int qs = 0; qs < QS; ++qs) {
+      lo_q[qs] = lo_of(q0w + 16 * qs + li);
+      hi_q[qs] = hi_of(q0w + 16 * qs + li);
+    }
   }
 
   const uint16_t* qp = a.q + (long)b * a.sqb + (long)h * a.sqh;
@@ -842,18 +942,19 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
     }
   };
   if (ntiles > 0) {
-    if constexpr (DOC) stage(t0 & 1, t0 * FB_BN);
+    if constexpr (DOC || SPAN) stage(t0 & 1, t0 * FB_BN);
     else stage(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
   const int q_ = li >> 2, pp = li & 3;
-  for (int t = DOC ? t0 : 0; t < ntiles; ++t) {
+  for (int t = DOC || SPAN ? t0 : 0; t < tend; ++t) {
     const int cur = t & 1, key0 = t * FB_BN;
-    if (t + 1 < ntiles) stage(cur ^ 1, key0 + FB_BN);
+    if (t + 1 < tend) stage(cur ^ 1, key0 + FB_BN);
     const char* tk = smem + cur * 2 * KT;
     const char* tv = tk + KT;
-    if (!((a.causal && key0 > q0w + QW - 1 + off) || (DOC && key0 + FB_BN <= lo_w0))) {
+    if (!((a.causal && key0 > q0w + QW - 1 + off) || (DOC && key0 + FB_BN <= lo_w0) ||
+          (SPAN && (key0 + FB_BN <= lo_w0 || key0 >= hi_w1)))) {
       f32x4_t s[NI][QS], dp[NI][QS];
 #pragma unroll
       for (int i = 0; i < NI; ++i)
@@ -874,7 +975,8 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
       }
       // masked scores -> -inf before the exponent (exp2(-inf) = 0): a select per score in masked tiles only, no
       // branch around each exponent (the per-element `ok ? exp : 0` form compiled to 72 exec-mask branches)
-      if ((key0 + FB_BN > kv_end) || (a.causal && key0 + FB_BN - 1 > q0w + off) || (DOC && key0 < lo_w1)) {
+      if ((key0 + FB_BN > kv_end) || (a.causal && key0 + FB_BN - 1 > q0w + off) || (DOC && key0 < lo_w1) ||
+          (SPAN && (key0 < lo_w1 || key0 + FB_BN > hi_w0))) {
 #pragma unroll
         for (int qs = 0; qs < QS; ++qs) {
           const int qi = q0w + 16 * qs + li;
@@ -884,7 +986,8 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int key = key0 + i * 16 + g * 4 + r;
-              if constexpr (DOC) s[i][qs][r] = key > klim || key < lo_q[qs] ? -INFINITY : s[i][qs][r];
+              if constexpr (SPAN) s[i][qs][r] = key < lo_q[qs] || key >= hi_q[qs] ? -INFINITY : s[i][qs][r];
+              else if constexpr (DOC) s[i][qs][r] = key > klim || key < lo_q[qs] ? -INFINITY : s[i][qs][r];
               else s[i][qs][r] = key > klim ? -INFINITY : s[i][qs][r];
             }
         }
@@ -1234,7 +1337,24 @@ static bool flash_doc_ok(const int* lo, const int* hi, int Sq, int Sk, int causa
   return lo && hi && causal && Sq == Sk && !kv_lens && !drop_state;
 }
 
+// what the SPAN forms are defined for: both tables, non-causal self-attention at D = 64, nothing else masked, a tile
+// they are instantiated with and a shape inside their index limits (flash_span_ok)
+int flash_span_tile(int S) {
+  (void)S;  // the 128-key form is instantiated and selectable (span_tile); every length takes the 64-key tiles by default
+  return 64;
+}
 
+bool flash_span_ok(int D, long B, long Sq, long Sk, long Hq, long max_token_stride) {
+  return D == 64 && B > 0 && Hq > 0 && Sq > 0 && Sq == Sk && Sq < (1L << 24) && B * Hq * Sq < (1L << 31) &&
+         max_token_stride < (1L << 24);
+}
+
+template <class Args>
+static bool flash_span_args_ok(const Args& a, int D, long max_token_stride) {
+  return a.span_lo && a.span_hi && !a.doc_lo && !a.doc_hi && !a.causal && !a.kv_lens && !a.drop.state &&
+         (a.span_tile == 0 || a.span_tile == 64 || a.span_tile == 128) &&
+         flash_span_ok(D, a.B, a.Sq, a.Sk, a.Hq, max_token_stride);
+}
 
 // dK/dV chunks per key block: causal key blocks carry from 1 to Sq / 64 query tiles of work, so with one block per
 // key block the first ones ran long after the rest of the chip had drained. Split each key block's (head, query tile)
@@ -1261,6 +1381,16 @@ static bool fwd_one_tile() {
 void launch_flash_fwd(const AttnFwdArgs& a, int D, hipStream_t st) {
   const int nqb = (a.Sq + FA_BM - 1) / FA_BM;
   const dim3 grid(nqb * a.Hq * a.B), blk(FA_THREADS);
+  if (a.span_lo || a.span_hi) {  // the SPAN forms: multi-tile only, 64-key tiles unless span_tile asks for 128
+    if (!flash_span_args_ok(a, D, std::max({a.sqs, a.sks, a.svs, a.sos})))
+      throw std::runtime_error("flash_fwd: a span mask needs both tables, non-causal self-attention at head dim 64, no "
+                               "kv_lens, no dropout, no document mask and a shape of flash_span_ok");
+    if ((a.span_tile ? a.span_tile : flash_span_tile(a.Sk)) == 128)
+      hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 2, 2, false, false, true>), grid, blk, 0, st, a);
+    else
+      hipLaunchKernelGGL((flash_fwd_kernel<64, 64, 2, 2, false, false, true>), grid, blk, 0, st, a);
+    return;
+  }
   if (a.doc_lo || a.doc_hi) {  // the DOC forms: multi-tile only (a short sequence takes the 64-key tiles)
     if (!flash_doc_ok(a.doc_lo, a.doc_hi, a.Sq, a.Sk, a.causal, a.kv_lens, a.drop.state))
       throw std::runtime_error("flash_fwd: a document mask needs both tables, causal self-attention, no kv_lens and "
@@ -1314,6 +1444,25 @@ static void launch_flash_bwd_drop(const AttnBwdArgs& a, const uint16_t* o, long 
 
 void launch_flash_bwd(const AttnBwdArgs& a, int D, const uint16_t* o, long sob, long sos, long soh,
                       hipStream_t st) {
+  if (a.span_lo || a.span_hi) {
+    // the SPAN forms: never the one-block kernel (so no column partials), never the QS = 2 dQ, one chunk per key block
+    if (!flash_span_args_ok(a, D, std::max({a.sqs, a.sks, a.svs, a.sds, sos, a.sgqs, a.sgks, a.sgvs})) || a.cpart ||
+        a.dkv_split != 1)
+      throw std::runtime_error("flash_bwd: a span mask needs both tables, non-causal self-attention at head dim 64, no "
+                               "kv_lens, no dropout, no document mask, no bias gradient and a shape of flash_span_ok");
+    const long R = (long)a.B * a.Sq * a.Hq;
+    const dim3 gkv(((a.Sk + FB_BN - 1) / FB_BN) * a.Hkv * a.B), gq(((a.Sq + 63) / 64) * a.Hq * a.B), blk(FA_THREADS);
+    hipLaunchKernelGGL(flash_delta_kernel<64>, dim3((unsigned)((R * 8 + 255) / 256)), dim3(256), 0, st, o, sob, sos, soh,
+                       a.dO, a.sdb, a.sds, a.sdh, a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
+    if ((a.span_tile ? a.span_tile : flash_span_tile(a.Sk)) == 128) {
+      hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 128, false, false, true>), gkv, blk, 0, st, a);
+      hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 128, 1, false, false, true>), gq, blk, 0, st, a);
+    } else {
+      hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 64, false, false, true>), gkv, blk, 0, st, a);
+      hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 1, false, false, true>), gq, blk, 0, st, a);
+    }
+    return;
+  }
   if (a.doc_lo || a.doc_hi) {
     // the DOC forms: never the one-block kernel (so no column partials) and never the QS = 2 dQ
     if (!flash_doc_ok(a.doc_lo, a.doc_hi, a.Sq, a.Sk, a.causal, a.kv_lens, a.drop.state) || a.cpart)

@@ -365,6 +365,12 @@ struct AttnFwdArgs {
   // kernels clamp before use.
   const int* doc_lo = nullptr;
   const int* doc_hi = nullptr;
+  // span mask (the SPAN forms; non-causal self-attention at D = 64 only): int32 [B, Sq], query i sees the keys
+  // span_lo[i] <= j < span_hi[i]. Both or neither; clamped by the kernels before use. span_tile: keys per tile of the
+  // span forms, 64 or 128 (0: the dispatch's default, flash_span_tile).
+  const int* span_lo = nullptr;
+  const int* span_hi = nullptr;
+  int span_tile = 0;
 };
 struct AttnBwdArgs {
   const uint16_t *q, *k, *v, *dO;
@@ -392,7 +398,16 @@ struct AttnBwdArgs {
   uint32_t* rowkey = nullptr;
   const int* doc_lo = nullptr;  // as the forward's (the dQ kernel reads lo, the dK/dV kernel hi)
   const int* doc_hi = nullptr;
+  const int* span_lo = nullptr;  // as the forward's (every kernel reads both)
+  const int* span_hi = nullptr;
+  int span_tile = 0;
 };
+// keys (queries in the dK/dV kernel) per tile of the span forms when span_tile is 0
+int flash_span_tile(int S);
+// the span forms index this shape correctly: D = 64, Sq == Sk < 2^24, B * Hq * Sq < 2^31 (grid sizes and the delta
+// kernel's row split are 32-bit) and every token stride below 2^24 elements (a tile row times the stride is a 32-bit
+// product; batch and head strides are multiplied in 64 bits). One row of 131,072 tokens is far inside.
+bool flash_span_ok(int D, long B, long Sq, long Sk, long Hq, long max_token_stride);
 int flash_dkv_splits(int B, int Sq, int Sk, int Hkv, int causal);
 // the whole backward of one (batch, head) in one block (flash_bwd_short_kernel) applies to this shape
 bool flash_bwd_one_block(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split);
@@ -477,6 +492,12 @@ struct TokSpecial {
 void launch_mlm_batch(const void* src, bool u16, long Tn, const long* table, int N, int S, int P, uint32_t vocab,
                       const TokSpecial& sp, uint64_t seed, int stream, long* ids, long* types, long* labels,
                       long* positions, hipStream_t st);
+// the same samples back to back in one stream of Tt rows (Tt % 128 == 0, Tt < 2^31): cu int64 [N + 1] (device) the
+// samples' first rows; ids / types / pos int64 [Tt], labels / rows int64 [N, P], cls_rows int64 [N], lo / hi int32 [Tt]
+void launch_mlm_batch_unpadded(const void* src, bool u16, long Tn, const long* table, const long* cu, long Tt, int N,
+                               int S, int P, uint32_t vocab, const TokSpecial& sp, uint64_t seed, int stream, long* ids,
+                               long* types, long* pos, long* labels, long* rows, long* cls_rows, int* lo, int* hi,
+                               hipStream_t st);
 void launch_causal_batch(const void* src, bool u16, long Tn, const long* starts, int N, int S, long* ids, long* labels,
                          hipStream_t st);
 // causal_batch with document boundaries: doc_tok int64 [Dn + 1] ascending token offsets of the documents (device),

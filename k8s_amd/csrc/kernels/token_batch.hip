@@ -24,8 +24,16 @@
 // come from one __ballot per 64-position chunk and __popcll of the lower lanes and the earlier chunks. Stores: the
 // unused slots get their defaults, the selected lanes scatter theirs; plain vector stores, no atomics.
 //
+// UNPAD (mlm_batch_unpadded): the same samples written back to back into one stream of Tt rows. cu int64 [N + 1] holds
+// the samples' first stream rows (cu[n + 1] - cu[n] = L_n). Sample n writes ids, types and pos = j at row cu[n] + j for
+// j < L_n, with the span bounds lo = cu[n], hi = cu[n + 1] of ops.attention's span mask; labels are unchanged, the
+// [N, P] positions become stream rows cu[n] + j (unused slots: cu[n]), and cls_rows[n] = cu[n]. Block 0 also writes the
+// tail [cu[N], Tt), fewer than 128 rows: pad, type 0, pos 0, lo = cu[N], hi = Tt -- one pad span no real query sees.
+// Selection, replacement and slots are the code below, shared: sample n gets the same masks padded and unpadded.
+//
 // Every source index is clamped into [0, T) and every length into the row here as well as validated on the host: no
-// table content reads outside src or writes outside the outputs.
+// table content reads outside src or writes outside the outputs (UNPAD: every cu entry is clamped into [0, Tt] and
+// every stream row is tested against Tt).
 #include <stdexcept>
 
 #include "common.h"
@@ -46,17 +54,41 @@ __device__ __forceinline__ int tok_load(const T* __restrict__ src, long i, long 
   return (int)src[tok_clamp(i, Tn - 1)];  // uint16_t widens unsigned
 }
 
-template <typename T>
+// the stream outputs of the UNPAD form (unused, all null, by the padded one)
+struct TokUnpad {
+  const long* cu;  // [N + 1] on the device
+  long Tt;         // stream rows
+  long *pos, *cls_rows;
+  int *lo, *hi;
+};
+
+template <typename T, bool UNPAD>
 __global__ void __launch_bounds__(256) mlm_batch_kernel(const T* __restrict__ src, long Tn,
                                                         const long* __restrict__ table, int N, int S, int P,
                                                         uint32_t vocab, TokSpecial sp, uint64_t seed, int stream,
                                                         long* __restrict__ ids, long* __restrict__ types,
-                                                        long* __restrict__ labels, long* __restrict__ positions) {
+                                                        long* __restrict__ labels, long* __restrict__ positions,
+                                                        TokUnpad up) {
   __shared__ uint32_t score_lds[4][kTokMaxS];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int sample = blockIdx.x * 4 + wave;
   const bool live = sample < N;  // wave-uniform; a dead wave still meets the barrier
   const long* row = table + (long)(live ? sample : 0) * 6;
+  long base = 0, end = 0;  // (UNPAD) the sample's stream rows [base, end)
+  if constexpr (UNPAD) {
+    base = tok_clamp(up.cu[live ? sample : 0], up.Tt);
+    end = tok_clamp(up.cu[(live ? sample : 0) + 1], up.Tt);
+    if (blockIdx.x == 0 && threadIdx.x < 128) {  // the tail
+      const long t0 = tok_clamp(up.cu[N], up.Tt), e = t0 + threadIdx.x;
+      if (e < up.Tt) {
+        ids[e] = sp.pad;
+        types[e] = 0;
+        up.pos[e] = 0;
+        up.lo[e] = (int)t0;
+        up.hi[e] = (int)up.Tt;
+      }
+    }
+  }
   const long a0 = row[0], b0 = row[2];
   const int la = (int)tok_clamp(row[1], S), lb = (int)tok_clamp(row[3], S - la);
   const int n = (int)tok_clamp(row[4], P);
@@ -106,7 +138,7 @@ __global__ void __launch_bounds__(256) mlm_batch_kernel(const T* __restrict__ sr
     }
   }
 
-  int base = 0;
+  int nsel = 0;
   const unsigned long long below = (1ull << lane) - 1ull;
   long* lab = labels + (long)sample * P;
   long* pos = positions + (long)sample * P;
@@ -115,8 +147,8 @@ __global__ void __launch_bounds__(256) mlm_batch_kernel(const T* __restrict__ sr
     const int j = c * 64 + lane;
     const bool sel = cand[c] && rank[c] < n;
     const unsigned long long bal = __ballot(sel);
-    const int slot = base + __popcll(bal & below);
-    base += __popcll(bal);
+    const int slot = nsel + __popcll(bal & below);
+    nsel += __popcll(bal);
     int id = tok[c];
     if (sel) {
       const uint32_t jg = (uint32_t)j * kTokG;
@@ -127,19 +159,31 @@ __global__ void __launch_bounds__(256) mlm_batch_kernel(const T* __restrict__ sr
         id = (int)__umulhi(drop_mix32(krep ^ jg), vocab);
       if (live && slot < P) {
         lab[slot] = tok[c];
-        pos[slot] = j;
+        pos[slot] = UNPAD ? base + j : j;
       }
     }
-    if (live && j < S) {
+    const int type = (j >= la + 2 && j <= L - 1) ? 1 : 0;
+    if constexpr (UNPAD) {
+      const long e = base + j;
+      if (live && j < S && j < L && e < up.Tt) {
+        ids[e] = id;
+        types[e] = type;
+        up.pos[e] = j;
+        up.lo[e] = (int)base;
+        up.hi[e] = (int)end;
+      }
+    } else if (live && j < S) {
       ids[(long)sample * S + j] = id;
-      types[(long)sample * S + j] = (j >= la + 2 && j <= L - 1) ? 1 : 0;
+      types[(long)sample * S + j] = type;
     }
   }
-  if (live)
-    for (int p = base + lane; p < P; p += 64) {  // the slots no selected position took
+  if (live) {
+    for (int p = nsel + lane; p < P; p += 64) {  // the slots no selected position took
       lab[p] = -100;
-      pos[p] = 0;
+      pos[p] = UNPAD ? base : 0;
     }
+    if (UNPAD && lane == 0) up.cls_rows[sample] = base;
+  }
 }
 
 template <typename T>
@@ -193,12 +237,30 @@ void launch_mlm_batch(const void* src, bool u16, long Tn, const long* table, int
   if (N < 1 || Tn < 1 || S < 1 || S > kTokMaxS || P < 1 || P > S || vocab < 2 || stream < 0)
     throw std::runtime_error("mlm_batch: bad shape");
   const dim3 grid(cdiv(N, 4)), block(256);
+  const TokUnpad none{nullptr, 0, nullptr, nullptr, nullptr, nullptr};
   if (u16)
-    hipLaunchKernelGGL(mlm_batch_kernel<uint16_t>, grid, block, 0, st, (const uint16_t*)src, Tn, table, N, S, P, vocab,
-                       sp, seed, stream, ids, types, labels, positions);
+    hipLaunchKernelGGL((mlm_batch_kernel<uint16_t, false>), grid, block, 0, st, (const uint16_t*)src, Tn, table, N, S, P,
+                       vocab, sp, seed, stream, ids, types, labels, positions, none);
   else
-    hipLaunchKernelGGL(mlm_batch_kernel<int>, grid, block, 0, st, (const int*)src, Tn, table, N, S, P, vocab, sp, seed,
-                       stream, ids, types, labels, positions);
+    hipLaunchKernelGGL((mlm_batch_kernel<int, false>), grid, block, 0, st, (const int*)src, Tn, table, N, S, P, vocab,
+                       sp, seed, stream, ids, types, labels, positions, none);
+}
+
+void launch_mlm_batch_unpadded(const void* src, bool u16, long Tn, const long* table, const long* cu, long Tt, int N,
+                               int S, int P, uint32_t vocab, const TokSpecial& sp, uint64_t seed, int stream, long* ids,
+                               long* types, long* pos, long* labels, long* rows, long* cls_rows, int* lo, int* hi,
+                               hipStream_t st) {
+  if (N < 1 || Tn < 1 || S < 1 || S > kTokMaxS || P < 1 || P > S || vocab < 2 || stream < 0 || Tt < 1 ||
+      Tt >= (1L << 31) || Tt % 128)
+    throw std::runtime_error("mlm_batch_unpadded: bad shape");
+  const dim3 grid(cdiv(N, 4)), block(256);
+  const TokUnpad up{cu, Tt, pos, cls_rows, lo, hi};
+  if (u16)
+    hipLaunchKernelGGL((mlm_batch_kernel<uint16_t, true>), grid, block, 0, st, (const uint16_t*)src, Tn, table, N, S, P,
+                       vocab, sp, seed, stream, ids, types, labels, rows, up);
+  else
+    hipLaunchKernelGGL((mlm_batch_kernel<int, true>), grid, block, 0, st, (const int*)src, Tn, table, N, S, P, vocab, sp,
+                       seed, stream, ids, types, labels, rows, up);
 }
 
 void launch_causal_batch(const void* src, bool u16, long Tn, const long* starts, int N, int S, long* ids, long* labels,

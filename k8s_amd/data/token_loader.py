@@ -14,6 +14,11 @@ As ``loader.Loader``, three paths end in the same call and produce the same bits
 ``(ids, labels)``, or with ``doc_mask=True`` ``(ids, labels, lo, hi, pos)`` from one ``ops.data.causal_doc_batch`` call:
 the bounds of every token's document inside its row, positions that restart at each document, and -100 labels on every
 document's last token -- ``LlamaForCausalLM.forward``'s positional order.
+
+``unpad=True`` (BERT): one ``ops.data.mlm_batch_unpadded`` call writes the batch as one token stream, the sequences back
+to back, and ``batch(t)`` returns ``(ids, token_types, pos, labels [N, P], nsp, rows [N, P], cls_rows, lo, hi)`` --
+``BertForPreTraining.forward_unpadded``'s positional order. The stream offsets ``cu`` come from the plan's ``kv_lens``
+on the host, so nothing reads the device.
 """
 from __future__ import annotations
 
@@ -41,8 +46,12 @@ class TokenLoader:
 
     def __init__(self, ds: TokenDataset, split: str, device, batch: int, seq: int, kind: str = "bert",
                  max_predictions: int = 20, seed: int = 0, rank: int = 0, world: int = 1, resident_gb: float = 4.0,
-                 train: bool = True, doc_mask: bool = False):
+                 train: bool = True, doc_mask: bool = False, unpad: bool = False):
         assert kind in KINDS
+        self.unpad = bool(unpad)
+        if self.unpad and (kind != "bert" or doc_mask):
+            raise DataError("unpadded batches are implemented for the BERT models only (not Llama, not with a "
+                            "document mask)")
         self.ds, self.split, self.device, self.kind = ds, ds.split(split), torch.device(device), kind
         self.tokens = self.split.tokens
         self.batch_size, self.S, self.P, self.train = int(batch), int(seq), int(max_predictions), train
@@ -76,6 +85,7 @@ class TokenLoader:
         gpu = self.device.type == "cuda"
         self.resident = is_resident(self.split.nbytes, resident_gb, self.device)
         self.src, self.streamer, self._plans = None, None, {}
+        self.last_real_tokens = 0  # non-pad positions of the batch ``batch`` returned last (from its host plan)
         if self.doc_mask:  # checked on the host and uploaded once
             self.doc_tok = kdata.doc_offsets(self.doc_tok_host, self.device)
         if self.resident:
@@ -103,6 +113,24 @@ class TokenLoader:
         if real is not None:
             nsp = np.where(real, nsp, -100)
         return {"table": tab, "nsp": nsp, "kv_lens": lens, "real": real}
+
+    @staticmethod
+    def stream_offsets(plan: dict):
+        """(cu int64 [N + 1], T) of an unpadded batch from its host plan: the sequences' first stream rows and the
+        stream's row count, their total rounded up to a multiple of 128."""
+        cu = np.zeros(len(plan["kv_lens"]) + 1, dtype=np.int64)
+        np.cumsum(plan["kv_lens"], out=cu[1:])
+        return cu, (int(cu[-1]) + 127) // 128 * 128
+
+    def stream_rows(self, t: int = 0) -> int:
+        """Rows of batch ``t``'s unpadded stream (from the host table)."""
+        return self.stream_offsets(self.plan(t))[1]
+
+    def real_tokens(self, t: int) -> int:
+        """Non-pad positions of batch ``t`` (from the host table; every position of a causal window)."""
+        if self.kind == "llama":
+            return self.batch_size * self.S
+        return int(self.plan(t)["kv_lens"].sum())
 
     def compact(self, plan: dict, out: np.ndarray) -> None:
         """Gather the batch's tokens back to back into ``out`` ([capacity], the tokens' dtype or its int16 view) and
@@ -148,12 +176,18 @@ class TokenLoader:
             self.compact(plan, buf)
             src, rows = _as_torch(buf), plan["local"]
         rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64))
+        self.last_real_tokens = self.batch_size * self.S if self.kind == "llama" else int(plan["kv_lens"].sum())
         doc = ()
         if self.kind == "llama" and self.doc_mask:
             at = torch.from_numpy(np.ascontiguousarray(plan["starts"], dtype=np.int64))
             ids, labels, *doc = kdata.causal_doc_batch(src, rows, at, self.doc_tok, self.S, self.split.T)
         elif self.kind == "llama":
             ids, labels = kdata.causal_batch(src, rows, self.S)
+        elif self.unpad:
+            cu, T = self.stream_offsets(plan)
+            ids, types, pos, labels, positions, cls_rows, lo, hi = kdata.mlm_batch_unpadded(
+                src, rows, torch.from_numpy(cu), T, self.S, self.P, self.ds.vocab, self.ds.special, self.seed,
+                self.stream)
         else:
             ids, types, labels, positions = kdata.mlm_batch(src, rows, self.S, self.P, self.ds.vocab, self.ds.special,
                                                             self.seed, self.stream)
@@ -163,6 +197,8 @@ class TokenLoader:
             labels = labels.masked_fill(~self._upload(plan["real"]).unsqueeze(1), -100)
         if self.kind == "llama":
             return (ids, labels) + tuple(doc)
+        if self.unpad:
+            return (ids, types, pos, labels, self._upload(plan["nsp"]), positions, cls_rows, lo, hi)
         return (ids, types, labels, self._upload(plan["nsp"]), positions,
                 self._upload(plan["kv_lens"].astype(np.int32)))
 
@@ -187,6 +223,8 @@ class TokenLoader:
 
     def info(self) -> dict:
         out = {"resident": self.resident}
+        if self.unpad:
+            out.update(unpad=True, stream_rows=self.stream_rows(0))
         if self.doc_mask:
             out.update(doc_mask=True, docs_per_row=round(self.docs_per_row(0), 4))
         if self.streamer is not None and self.streamer.gather_s > 0:

@@ -88,8 +88,9 @@ class BertLayer(nn.Module):
         self.ln2_g = store.new(name + ".output.LayerNorm.weight", (h,), init_const(1), decay=False, lowp=False)
         self.ln2_b = store.new(name + ".output.LayerNorm.bias", (h,), init_const(0), decay=False, lowp=False)
 
-    def forward(self, x, B, S, kv_lens, drop=None):
-        """``drop``: the model's DropoutState when this forward applies dropout (training mode), else None."""
+    def forward(self, x, B, S, kv_lens, drop=None, span=None):
+        """``drop``: the model's DropoutState when this forward applies dropout (training mode), else None. ``span`` =
+        (lo, hi): the span mask of an unpadded token stream (B = 1, S = its rows), in place of ``kv_lens``."""
         c = self.c
         pa = (c.attention_dropout, drop, self.site0) if drop is not None and c.attention_dropout else None
         p1 = (c.hidden_dropout, drop, self.site0 + 1) if drop is not None and c.hidden_dropout else None
@@ -104,7 +105,7 @@ class BertLayer(nn.Module):
         b0, b1, b2 = K.BiasLink(), K.BiasLink(), K.BiasLink()
         qkv = K.linear(x, self.qkv_w, self.qkv_b, grad_link=l1, bias_link=b0)  # [T, 3h]
         o = attention_qkv(qkv, B, S, nh, nh, d, causal=False, kv_lens=kv_lens,
-                          bias_link=b0, dropout=pa)  # packed QKV gradient in place
+                          bias_link=b0, dropout=pa, span=span)  # packed QKV gradient in place
         a = K.linear(o.reshape(B * S, h), self.o_w, self.o_b, bias_link=b1)
         x, _ = K.layer_norm(a, self.ln1_g, self.ln1_b, c.eps, residual=x, res_link=l1, bias_link=b1, dropout=p1)
         # FFN1's GELU backward and bias gradient inside FFN2's data-gradient epilogue (ActLink)
@@ -171,16 +172,44 @@ class BertForPreTraining(nn.Module):
             xm = x.index_select(0, rows)  # [B * P, h]; backward scatters into the encoder output gradient
         else:
             xm = x  # MLM head on every token (labels -100 are ignored by the loss kernel)
+        return self._losses(xm, lambda: x.reshape(B, S, h)[:, 0].contiguous(), mlm_labels, nsp_labels, dtype)
+
+    def _losses(self, xm, cls_rows, mlm_labels, nsp_labels, dtype):
+        """(total, MLM, NSP) losses from the MLM head's rows ``xm`` and the [CLS] rows ``cls_rows()`` returns."""
+        c = self.c
         t = K.linear(xm, self.mlm_w, self.mlm_b, act="gelu")
         t = K.layer_norm(t, self.mlm_ln_g, self.mlm_ln_b, c.eps)
         logits = K.linear(t, self.word, self.dec_b)  # tied decoder, [T, padded_vocab]
         mlm = K.cross_entropy(logits, mlm_labels.reshape(-1), valid=c.vocab_size)
         # NSP head on [CLS]
-        cls = x.reshape(B, S, h)[:, 0].contiguous()
+        cls = cls_rows()
         pooled = torch.tanh(K.linear(cls, self.pool_w, self.pool_b).float()).to(dtype)
         nsp_logits = K.linear(pooled, self.nsp_w, self.nsp_b)
         nsp = K.cross_entropy(nsp_logits, nsp_labels, valid=2)
         return mlm + nsp, mlm, nsp
+
+    def forward_unpadded(self, ids, types, pos, mlm_labels, nsp_labels, mlm_rows, cls_rows, span_lo, span_hi,
+                         dtype=torch.bfloat16):
+        """``forward`` on one unpadded token stream (``ops.data.mlm_batch_unpadded``): ``ids``, ``types`` and ``pos``
+        int64 [T], the N sequences back to back, attention confined to each by the span mask ``span_lo`` / ``span_hi``
+        (int32 [1, T]). The encoder is ``BertLayer`` with B = 1, S = T; the MLM head runs on the stream rows
+        ``mlm_rows`` [N, P] (labels ``mlm_labels`` [N, P], -100 on unused slots) and the NSP head on ``cls_rows`` [N].
+        The losses are ``forward``'s; in exact arithmetic they and every parameter gradient equal the padded
+        forward's, since pad rows are never attended to and carry no label. Dropout is not implemented on this path
+        (the span kernels have no dropout form): a training forward with a nonzero probability raises."""
+        c = self.c
+        if self.training and (c.hidden_dropout or c.attention_dropout):
+            raise ValueError("forward_unpadded: dropout is not implemented on the unpadded path (set both "
+                             "probabilities to 0)")
+        T = ids.numel()
+        e = K.embedding_sum([(ids.reshape(1, T), self.word), (pos.reshape(1, T), self.pos),
+                             (types.reshape(1, T), self.typ)], T, dtype)
+        x = K.layer_norm(e.reshape(T, c.hidden), self.emb_ln_g, self.emb_ln_b, c.eps)
+        span = (span_lo.reshape(1, T), span_hi.reshape(1, T))
+        for layer in self.layers:
+            x = layer(x, 1, T, None, None, span)
+        xm = x.index_select(0, mlm_rows.reshape(-1))  # [N * P, h]
+        return self._losses(xm, lambda: x.index_select(0, cls_rows), mlm_labels, nsp_labels, dtype)
 
 
 def synthetic_batch(c: BertConfig, batch: int, seq: int, device, generator=None, mask_prob=0.15):

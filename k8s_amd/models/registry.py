@@ -164,6 +164,12 @@ def token_dataset_plan(name: str, device, batch: int, seq: Optional[int], data: 
                 raise DataError("dataset %s: --doc-mask needs %s_segments.npy and %s_docs.npy"
                                 % (ds.path, sp_name, sp_name))
         kw["doc_mask"] = True
+    unpad = bool(data.get("unpad"))
+    if unpad:
+        if not bert or doc_mask:
+            raise DataError("unpadded batches are implemented for the BERT models only, not %s%s"
+                            % (name, " with a document mask" if doc_mask else ""))
+        kw["unpad"] = True
     if bert:
         ts.check_seq(seq, kw["max_predictions"])
         items, what = tr.G, "segments"
@@ -175,11 +181,14 @@ def token_dataset_plan(name: str, device, batch: int, seq: Optional[int], data: 
         idx, ords = ts.train_items(kw["seed"], 0, kw["rank"], kw["world"], batch, items)
         lens = ts.pair_rows(tr.segments, tr.docs, idx, ords, kw["seed"], seq, kw["max_predictions"])[2]
         pad_fraction = round(float(1.0 - lens.mean() / seq), 4)
+        stream_rows = (int(lens.sum()) + 127) // 128 * 128  # (unpad) the rows of that batch's token stream
     size = lambda sp: {"tokens": sp.T, "segments": sp.G, "documents": sp.D}  # noqa: E731
     info = {"dir": data["dir"], "kind": "tokens", "vocab": ds.vocab, "train": size(tr),
             "val": size(ds.splits["val"]) if "val" in ds.splits else None, "seq": seq,
             "resident": is_resident(tr.nbytes, kw["resident_gb"], torch.device(device)), "steps_per_epoch": E,
             "pad_fraction": pad_fraction}
+    if unpad:
+        info.update(unpad=True, stream_rows=stream_rows)
     if doc_mask:  # the documents per row of the first batch, from the host tables alone
         import numpy as np
 
@@ -249,6 +258,8 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
     evaluation runs without it. ``data``: train on a dataset directory instead of synthetic batches --
     ``{"dir", "augment", "crop_pad", "resident_gb", "seed", "rank", "world"}`` (``k8s_amd.data.loader.Loader``'s
     arguments, or without the two augmentation keys ``TokenLoader``'s; only ``dir`` is required). The directory's
+    With ``"unpad": True`` (BERT, no dropout) batches are unpadded token streams and the loss is
+    ``forward_unpadded``'s. The directory's
     kind must fit the model: images for ResNet (``classes`` then comes from its meta.json), tokens for BERT and Llama.
     ``batch(t)`` is batch ``t`` of the ``train`` split and ``eval_batch(i)`` batch ``i`` of the ``val`` split."""
     if data is not None:
@@ -257,6 +268,8 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
         check_data_kind(name, dataset_kind(data["dir"]))
     if dropout and name not in ("bert_base", "bert_tiny"):
         raise ValueError("dropout is implemented for the BERT models only, not %r" % name)
+    if data is not None and data.get("unpad") and dropout:
+        raise ValueError("unpadded batches cannot be combined with dropout (the span kernels have no dropout form)")
     device = torch.device(device)
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
     store = ParamStore()
@@ -345,6 +358,12 @@ def build(name: str, device, batch: int, seq: Optional[int] = None, image: Optio
             train, eval_batch, close, info = _token_loaders(name, device, batch, seq, seed, data, mlm_every_token)
         model = M.BertForPreTraining(store, cfg).finalize(device, grad_dtype=grad_dtype, seed=seed, pad_to=pad_to)
         model.drop_state = K.DropoutState(seed if dropout_seed is None else dropout_seed, device)
+        if data is not None and data.get("unpad"):  # batches in forward_unpadded's positional order
+            return Workload(name, model, store, train.batch, lambda b: model.forward_unpadded(*b, dtype=dtype)[0],
+                            batch * seq, "tokens", "adam", 1e-4, {"seq": seq, "data": info, "loader": train},
+                            evaluate=token_eval(lambda b: model.forward_unpadded(*b, dtype=dtype)[0], lambda b: b[3],
+                                                model),
+                            eval_batch=eval_batch, close=close)
         if data is not None:  # batches are (ids, types, labels, nsp, positions, kv_lens): forward's positional order
             return Workload(name, model, store, train.batch, lambda b: model(*b, dtype=dtype)[0], batch * seq,
                             "tokens", "adam", 1e-4, {"seq": seq, "data": info, "loader": train},

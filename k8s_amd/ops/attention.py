@@ -22,6 +22,14 @@ past its last (``doc_bounds`` derives both from ``lo``). Query ``i`` sees key ``
 forms of the multi-tile forward, the dK/dV and the dQ kernels skip the key (query) tiles no query (key) of a block can
 see. Causal self-attention only: with ``kv_lens``, ``dropout`` or ``causal=False`` it is a ``ValueError``. GPU operands
 outside the flash contract run the reference with the same mask.
+
+``span=(lo, hi)``: a bidirectional span mask for rows that hold several sequences back to back (unpadded BERT). ``lo``
+and ``hi`` are int32 [B, S] (``span_bounds`` derives both from the span starts): query ``i`` sees key ``j`` iff
+``lo[i] <= j < hi[i]``; with consistent tables (constant inside a span, spans tiling the row) that equals
+``lo[j] <= i < hi[j]``, and every query sees itself. The SPAN forms of the multi-tile forward, the dK/dV and the dQ
+kernels (head_dim 64) visit only the tiles a block's spans reach. Non-causal self-attention only: with ``causal=True``,
+``kv_lens``, ``dropout`` or ``doc=`` it is a ``ValueError``. head_dim 128 and GPU operands outside the flash contract
+run the reference with the same mask.
 """
 from __future__ import annotations
 
@@ -101,6 +109,71 @@ def doc_bounds(doc_starts: torch.Tensor):
     return lo.to(torch.int32).contiguous(), hi.to(torch.int32).contiguous()
 
 
+def span_mask_reference(span_lo: torch.Tensor, span_hi: torch.Tensor) -> torch.Tensor:
+    """bool [B, S, S], True where query i may NOT see key j: the complement of ``lo[i] <= j < hi[i]``."""
+    S = span_lo.shape[1]
+    j = torch.arange(S, device=span_lo.device)[None, None, :]
+    return (j < span_lo.long()[:, :, None]) | (j >= span_hi.long()[:, :, None])
+
+
+def span_bounds(starts: torch.Tensor):
+    """``starts`` integer [B, S]: for every token the row index of the first token of its span. Returns the ``(lo, hi)``
+    int32 pair ``attention(..., span=)`` takes, on the same device: ``lo`` is ``starts`` and ``hi[i]`` the next span's
+    start after ``i`` (``S`` in the last span). The tables ``doc_bounds`` builds, read without the causal triangle; a
+    CPU tensor is checked the same way and a bad one raises ``ValueError``."""
+    try:
+        return doc_bounds(starts)
+    except ValueError as e:
+        raise ValueError(str(e).replace("doc_starts", "starts")) from None
+
+
+def _span_spec(span, B, Sq, Sk, causal, kv_lens, dropout, doc, who="attention"):
+    """The checked ``(lo, hi)`` of a ``span=`` argument (None when off): non-causal self-attention, nothing else
+    masked."""
+    if span is None:
+        return None
+    if causal:
+        raise ValueError("%s: a span mask is bidirectional and cannot be combined with causal=True" % who)
+    if Sq != Sk:
+        raise ValueError("%s: a span mask is defined for self-attention (Sq == Sk) only" % who)
+    if kv_lens is not None:
+        raise ValueError("%s: a span mask cannot be combined with kv_lens" % who)
+    if dropout is not None:
+        raise ValueError("%s: a span mask cannot be combined with dropout" % who)
+    if doc is not None:
+        raise ValueError("%s: a span mask cannot be combined with a document mask" % who)
+    if not isinstance(span, (tuple, list)) or len(span) != 2 or span[0] is None or span[1] is None:
+        raise ValueError("%s: span = (lo, hi) needs both tables" % who)
+    lo, hi = span
+    if lo.dtype != torch.int32 or hi.dtype != torch.int32:
+        raise ValueError("%s: span = (lo, hi) must be int32 tensors (ops.attention.span_bounds)" % who)
+    if tuple(lo.shape) != (B, Sq) or tuple(hi.shape) != (B, Sq):
+        raise ValueError("%s: span = (lo, hi) must have the shape [B, S] of the queries" % who)
+    return lo, hi
+
+
+# keys per tile of the SPAN kernels: None takes the dispatch's default (flash_span_tile), 64 / 128 select a form
+SPAN_TILE = None
+
+
+def _span_kw(span, device) -> dict:
+    """flash_fwd / flash_bwd keyword arguments of a span mask; none when off."""
+    if span is None:
+        return {}
+    kw = {"span_lo": span[0].to(device).contiguous(), "span_hi": span[1].to(device).contiguous()}
+    if SPAN_TILE is not None:
+        kw["span_tile"] = int(SPAN_TILE)
+    return kw
+
+
+def _span_flash_ok(q, k, v) -> bool:
+    """The SPAN kernels take this call: the flash contract at head_dim 64 inside their index limits."""
+    if q.shape[-1] != 64 or not _flash_ok(q, k, v):
+        return False
+    B, S, Hq, _ = q.shape
+    return bool(_load().flash_span_ok(64, B, S, k.shape[1], Hq, max(t.stride(1) for t in (q, k, v))))
+
+
 def _doc_spec(doc, q, k, causal, kv_lens, dropout):
     """The checked ``(lo, hi)`` of a ``doc=`` argument (None when off): causal self-attention, nothing else masked."""
     if doc is None:
@@ -125,8 +198,11 @@ def _doc_kw(doc, device) -> dict:
 
 def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None,
                         keep: Optional[torch.Tensor] = None, keep_scale: float = 1.0,
-                        doc_lo: Optional[torch.Tensor] = None):
-    """``keep`` (bool [B, Hq, Sq, Sk], ``ref.attention_keep``) with ``keep_scale``: dropout on the probabilities.
+                        doc_lo: Optional[torch.Tensor] = None, span_lo: Optional[torch.Tensor] = None,
+                        span_hi: Optional[torch.Tensor] = None):
+    """``span_lo`` / ``span_hi`` (int [B, S], non-causal, Sq == Sk): the span mask, query i sees the keys
+    lo[i] <= j < hi[i].
+    ``keep`` (bool [B, Hq, Sq, Sk], ``ref.attention_keep``) with ``keep_scale``: dropout on the probabilities.
     ``doc_lo`` (int [B, S], with ``causal`` and Sq == Sk): the document mask, query i sees the keys lo[i] <= j <= i."""
     B, S, Hq, D = q.shape
     Hkv = k.shape[2]
@@ -145,6 +221,12 @@ def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] =
         s = s.masked_fill(keymask[:, None, None, :], float("-inf"))
     if doc_lo is not None:
         s = s.masked_fill(doc_mask_reference(doc_lo.to(q.device))[:, None], float("-inf"))
+    if (span_lo is None) != (span_hi is None):
+        raise ValueError("attention_reference: span_lo and span_hi must be given together")
+    if span_lo is not None:
+        if causal or kv_lens is not None or doc_lo is not None or S != Sk:
+            raise ValueError("attention_reference: a span mask is defined for non-causal self-attention alone")
+        s = s.masked_fill(span_mask_reference(span_lo.to(q.device), span_hi.to(q.device))[:, None], float("-inf"))
     p = torch.softmax(s, -1)
     if keep is not None:
         p = torch.where(keep, p * keep_scale, torch.zeros((), device=p.device))
@@ -169,11 +251,11 @@ def _ref_keep(drop, q, k):
 
 class _Flash(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None, doc=None):
+    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None, doc=None, span=None):
         C = _load()
         if kv_lens is not None:
             kv_lens = kv_lens.to(device=q.device, dtype=torch.int32).contiguous()
-        ctx.drop = dict(_drop_kw(drop), **_doc_kw(doc, q.device))
+        ctx.drop = dict(_drop_kw(drop), **_doc_kw(doc, q.device), **_span_kw(span, q.device))
         o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.drop)
         ctx.save_for_backward(q, k, v, o, lse, kv_lens if kv_lens is not None else torch.empty(0))
         ctx.causal, ctx.scale, ctx.has_lens = causal, scale, kv_lens is not None
@@ -185,18 +267,19 @@ class _Flash(torch.autograd.Function):
         C = _load()
         dq, dk, dv = C.flash_bwd(do.contiguous(), q, k, v, o, lse, ctx.causal, lens if ctx.has_lens else None,
                                  ctx.scale, **ctx.drop)
-        return dq, dk, dv, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 class _Reference(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None, doc=None):
+    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None, doc=None, span=None):
         ctx.save_for_backward(q, k, v)
         ctx.causal, ctx.kv_lens, ctx.scale, ctx.drop = causal, kv_lens, scale, drop
         ctx.doc_lo = doc[0] if doc is not None else None
+        ctx.span = span if span is not None else (None, None)
         with torch.no_grad():
             keep, ks = _ref_keep(drop, q, k)
-            return attention_reference(q, k, v, causal, kv_lens, scale, keep, ks, ctx.doc_lo)
+            return attention_reference(q, k, v, causal, kv_lens, scale, keep, ks, ctx.doc_lo, *ctx.span)
 
     @staticmethod
     def backward(ctx, do):
@@ -204,14 +287,18 @@ class _Reference(torch.autograd.Function):
         with torch.enable_grad():
             qq, kk, vv = (t.detach().float().requires_grad_(True) for t in (q, k, v))
             keep, ks = _ref_keep(ctx.drop, q, k)  # the forward's mask again (same seed, step and site)
-            o = attention_reference(qq, kk, vv, ctx.causal, ctx.kv_lens, ctx.scale, keep, ks, ctx.doc_lo)
+            o = attention_reference(qq, kk, vv, ctx.causal, ctx.kv_lens, ctx.scale, keep, ks, ctx.doc_lo, *ctx.span)
             dq, dk, dv = torch.autograd.grad(o, (qq, kk, vv), do.float())
-        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None, None, None
+        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None, None, None, None
 
 
 def attention(q, k, v, causal: bool = False, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None,
-              dropout: Optional[tuple] = None, doc: Optional[tuple] = None):
+              dropout: Optional[tuple] = None, doc: Optional[tuple] = None, span: Optional[tuple] = None):
     scale = scale or 1.0 / math.sqrt(q.shape[-1])
+    span = _span_spec(span, q.shape[0], q.shape[1], k.shape[1], causal, kv_lens, dropout, doc)
+    if span is not None:  # the SPAN kernels, or the reference with the same mask: never a call that drops it
+        fn = _Flash if _span_flash_ok(q, k, v) else _Reference
+        return fn.apply(q, k, v, False, None, scale, None, None, span)
     doc = _doc_spec(doc, q, k, causal, kv_lens, dropout)
     if doc is not None:  # the DOC kernels, or the reference with the same mask: never a call that drops it
         return (_Flash if _flash_ok(q, k, v) else _Reference).apply(q, k, v, causal, None, scale, None, doc)
@@ -235,7 +322,7 @@ class _FlashQKV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, B, S, H, Hkv, D, causal, kv_lens, scale, pos, table, bias_link=None, rope_in_place=False,
-                rope_applied=False, drop=None, doc=None):
+                rope_applied=False, drop=None, doc=None, span=None):
         C = _load()
         if kv_lens is not None:
             kv_lens = kv_lens.to(device=qkv.device, dtype=torch.int32).contiguous()
@@ -249,7 +336,7 @@ class _FlashQKV(torch.autograd.Function):
             C.rope_(x[:, : (H + Hkv) * D], pos, table, False)
         g = x.view(B, S, H + 2 * Hkv, D)
         q, k, v = g.narrow(2, 0, H), g.narrow(2, H, Hkv), g.narrow(2, H + Hkv, Hkv)
-        ctx.drop = dict(_drop_kw(drop), **_doc_kw(doc, qkv.device))
+        ctx.drop = dict(_drop_kw(drop), **_doc_kw(doc, qkv.device), **_span_kw(span, qkv.device))
         o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.drop)
         ctx.save_for_backward(x, o, lse, kv_lens if kv_lens is not None else torch.empty(0),
                               pos if pos is not None else torch.empty(0), table if table is not None else torch.empty(0))
@@ -269,7 +356,8 @@ class _FlashQKV(torch.autograd.Function):
         # which rotates dqkv after the kernel
         bl, dsum, ss, lpb = ctx.bias_link, None, None, None
         if bl is not None and bl.pb is not None and not has_rope and "doc_lo" not in ctx.drop and \
-                C.flash_bwd_one_block(D, S, S, H, Hkv, causal, B):  # (a document mask has no one-block form)
+                "span_lo" not in ctx.drop and \
+                C.flash_bwd_one_block(D, S, S, H, Hkv, causal, B):  # (a document or span mask has no one-block form)
             lpb = bl.pb
             ss = lpb.store.slot_for_write(lpb)
             dsum = ss.view(lpb.shape) if ss is not None else torch.empty(lpb.shape, device=x.device,
@@ -281,13 +369,14 @@ class _FlashQKV(torch.autograd.Function):
             bl.done = True
         if has_rope:
             C.rope_(dqkv[:, : (H + Hkv) * D], pos, table, True)
-        return (dqkv,) + (None,) * 15
+        return (dqkv,) + (None,) * 16
 
 
 def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int, causal: bool = False,
                   kv_lens: Optional[torch.Tensor] = None, rope: Optional[tuple] = None,
                   scale: Optional[float] = None, bias_link=None, rope_in_place: bool = False,
-                  rope_applied: bool = False, dropout: Optional[tuple] = None, doc: Optional[tuple] = None):
+                  rope_applied: bool = False, dropout: Optional[tuple] = None, doc: Optional[tuple] = None,
+                  span: Optional[tuple] = None):
     """Self-attention of a packed QKV projection ``qkv`` [B*S, (heads + 2*kv_heads) * head_dim] (q heads, then k,
     then v); ``rope`` = (pos [B*S] int32, table) applies rotary embeddings to q and k. Returns o [B, S, heads, D].
     GPU bf16: one fused path (``_FlashQKV``); otherwise the split + ``attention`` reference composition.
@@ -302,7 +391,9 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
     takes. ``dropout`` = (p, DropoutState, site): dropout on the probabilities, fused on the ``flash_dropout_fused``
     shapes (see the module docstring; the bias gradient stays a one-block feature); other shapes take the split +
     ``attention`` composition, which counts the fallback. ``doc`` = (lo, hi): the document mask of ``attention``
-    (causal, no ``kv_lens``, no dropout); with ``rope`` the caller passes positions that restart at every document."""
+    (causal, no ``kv_lens``, no dropout); with ``rope`` the caller passes positions that restart at every document.
+    ``span`` = (lo, hi): the span mask of ``attention`` (non-causal, no ``kv_lens``, no dropout, no ``doc``); the SPAN
+    kernels at head_dim 64, otherwise the split + ``attention`` composition, which keeps the mask."""
     D = head_dim
     scale = scale or 1.0 / math.sqrt(D)
     W = (heads + 2 * kv_heads) * D
@@ -315,12 +406,15 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
                              "(ops.attention.doc_bounds)")
     fused = qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128) and qkv.shape[-1] == W and \
         W % 8 == 0 and qkv.is_contiguous()
+    if span is not None:
+        span = _span_spec(span, B, S, S, causal, kv_lens, dropout, doc, "attention_qkv")
+        fused = fused and D == 64 and bool(_load().flash_span_ok(64, B, S, S, heads, W))
     if fused and drop is not None:
         fused = bool(_load().flash_dropout_fused(D, S, S, heads, kv_heads, causal, B))
     if fused:
         pos, table = rope if rope is not None else (None, None)
         return _FlashQKV.apply(qkv, B, S, heads, kv_heads, D, causal, kv_lens, scale, pos, table, bias_link,
-                               rope_in_place, rope_applied, drop, doc)
+                               rope_in_place, rope_applied, drop, doc, span)
     if rope_applied:
         raise RuntimeError("attention_qkv: q / k rotated by the projection epilogue need the fused GPU path")
     q, k, v = qkv.split([heads * D, kv_heads * D, kv_heads * D], dim=-1)
@@ -329,4 +423,4 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
 
         q, k = _nn.rope(q, rope[0], rope[1]), _nn.rope(k, rope[0], rope[1])
     return attention(q.reshape(B, S, heads, D), k.reshape(B, S, kv_heads, D), v.reshape(B, S, kv_heads, D),
-                     causal=causal, kv_lens=kv_lens, scale=scale, dropout=dropout, doc=doc)
+                     causal=causal, kv_lens=kv_lens, scale=scale, dropout=dropout, doc=doc, span=span)

@@ -9,8 +9,10 @@ host runs ``ops.reference.augment``, the same definition in torch (float64), whi
 token types, exactly ``n`` masked positions drawn without replacement from a counter generator, the 80 / 10 / 10 rule
 and the compacted [N, P] labels and positions. ``causal_batch`` gathers causal-LM windows, and ``causal_doc_batch``
 also returns every token's document bounds inside its row, its position inside the document and labels that stop at
-document ends. All are integer arithmetic: the GPU kernels match ``ops.reference.mlm_batch`` / ``causal_batch`` /
-``causal_doc_batch`` (the CPU path) bit for bit.
+document ends. ``mlm_batch_unpadded`` writes the same BERT samples back to back into one token stream, with the span
+bounds of ``ops.attention``'s ``span=`` and the stream rows the heads gather. All are integer arithmetic: the GPU
+kernels match ``ops.reference.mlm_batch`` / ``mlm_batch_unpadded`` / ``causal_batch`` / ``causal_doc_batch`` (the CPU
+path) bit for bit.
 """
 from __future__ import annotations
 
@@ -66,6 +68,23 @@ def mlm_batch(src: torch.Tensor, table: torch.Tensor, S: int, P: int, vocab: int
         return tuple(_load_ext().mlm_batch(src, table, int(S), int(P), int(vocab), [int(v) for v in special],
                                            _seed64(seed), int(stream)))
     return ref.mlm_batch(src, table, int(S), int(P), int(vocab), special, _seed64(seed), int(stream))
+
+
+def mlm_batch_unpadded(src: torch.Tensor, table: torch.Tensor, cu: torch.Tensor, T: int, S: int, P: int, vocab: int,
+                       special, seed: int, stream: int = 0):
+    """``mlm_batch`` without padding, in one launch: the N samples back to back in one stream of ``T`` rows. ``cu``
+    int64 [N + 1] on the host holds the samples' first rows (cu[0] = 0, cu[n + 1] - cu[n] = la + lb + 3) and ``T`` is
+    cu[N] rounded up to a multiple of 128 (``ops.reference.unpad_stream_rows``). Returns ``(ids, token_types, pos)``
+    int64 [T], ``(labels, rows)`` int64 [N, P] -- ``mlm_batch``'s labels, and the stream rows of its positions, unused
+    slots pointing at the sample's first row --, ``cls_rows`` int64 [N] and the span bounds ``(lo, hi)`` int32 [1, T]
+    that ``ops.attention``'s ``span=`` takes. The tail [cu[N], T) is one pad span. Sample n gets the masks
+    ``mlm_batch`` gives it. The GPU binding validates the table, ``cu`` and ``T`` on the host before anything is
+    launched and raises on the first failed check."""
+    if src.is_cuda:
+        return tuple(_load_ext().mlm_batch_unpadded(src, table, cu, int(T), int(S), int(P), int(vocab),
+                                                    [int(v) for v in special], _seed64(seed), int(stream)))
+    return ref.mlm_batch_unpadded(src, table, cu, int(T), int(S), int(P), int(vocab), special, _seed64(seed),
+                                  int(stream))
 
 
 def causal_batch(src: torch.Tensor, starts: torch.Tensor, S: int):

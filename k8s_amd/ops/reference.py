@@ -546,6 +546,58 @@ def mlm_batch(src, table, S: int, P: int, vocab: int, special, seed: int, stream
     return torch.where(sel, masked, tok), types, labels, positions
 
 
+def check_unpad_stream(table, cu, T: int) -> None:
+    """``cu`` and ``T`` of ``mlm_batch_unpadded`` against a checked table, as the GPU binding does; raises ValueError
+    on the first failed check."""
+    N = table.shape[0]
+    if not isinstance(cu, torch.Tensor) or cu.dtype != torch.int64 or cu.dim() != 1 or cu.shape[0] != N + 1:
+        raise ValueError("cu must be int64 [N + 1] with N = %d table rows" % N)
+    if int(cu[0]) != 0:
+        raise ValueError("cu[0] must be 0, got %d" % int(cu[0]))
+    bad = (cu[1:] - cu[:-1]) != table[:, 1] + table[:, 3] + 3
+    if bool(bad.any()):
+        raise ValueError("cu row %d: the difference is not la + lb + 3" % int(bad.nonzero()[0]))
+    T, end = int(T), int(cu[-1])
+    if T < end:
+        raise ValueError("T = %d is below cu[N] = %d" % (T, end))
+    if T % 128:
+        raise ValueError("T = %d must be a multiple of 128" % T)
+    if T - end >= 128:
+        raise ValueError("T = %d must be cu[N] = %d rounded up to a multiple of 128" % (T, end))
+
+
+def unpad_stream_rows(total: int) -> int:
+    """``T`` of ``mlm_batch_unpadded``: ``total = cu[N]`` rounded up to a multiple of 128."""
+    return (int(total) + 127) // 128 * 128
+
+
+def mlm_batch_unpadded(src, table, cu, T: int, S: int, P: int, vocab: int, special, seed: int, stream: int = 0):
+    """The definition of ``ops.data.mlm_batch_unpadded``: ``mlm_batch`` gathered at the real positions, plus the tail.
+    ``cu`` int64 [N + 1] (host): cu[0] = 0, cu[n + 1] - cu[n] = L_n = la + lb + 3; ``T``: cu[N] rounded up to a
+    multiple of 128. Stream row cu[n] + j (j < L_n) holds what ``mlm_batch`` writes at [n, j], with pos = j and the
+    span bounds lo = cu[n], hi = cu[n + 1]; the tail [cu[N], T) is one pad span (pad, type 0, pos 0, lo = cu[N],
+    hi = T). Returns (ids, token_types, pos) int64 [T], (labels, rows) int64 [N, P] with rows = cu[n] + position
+    (unused slots: cu[n]), cls_rows = cu[:N] int64 [N] and (lo, hi) int32 [1, T]."""
+    src = torch.as_tensor(src)
+    table, cu = torch.as_tensor(table), torch.as_tensor(cu)
+    ids2, types2, labels, positions = mlm_batch(src, table, S, P, vocab, special, seed, stream)
+    check_unpad_stream(table.cpu(), cu.cpu() if isinstance(cu, torch.Tensor) else cu, T)
+    dev, T, N = src.device, int(T), table.shape[0]
+    cu = cu.to(dev)
+    total = int(cu[-1])
+    n = torch.repeat_interleave(torch.arange(N, device=dev), cu[1:] - cu[:-1])
+    j = torch.arange(total, dtype=torch.int64, device=dev) - cu[n]
+    ids = torch.full((T,), int(special[0]), dtype=torch.int64, device=dev)
+    types = torch.zeros(T, dtype=torch.int64, device=dev)
+    pos = torch.zeros(T, dtype=torch.int64, device=dev)
+    lo = torch.full((T,), total, dtype=torch.int64, device=dev)
+    hi = torch.full((T,), T, dtype=torch.int64, device=dev)
+    ids[:total], types[:total], pos[:total] = ids2[n, j], types2[n, j], j
+    lo[:total], hi[:total] = cu[n], cu[n + 1]
+    return (ids, types, pos, labels, cu[:N, None] + positions, cu[:N].clone(), lo.to(torch.int32).unsqueeze(0),
+            hi.to(torch.int32).unsqueeze(0))
+
+
 def causal_batch(src, starts, S: int):
     """The definition of ``ops.data.causal_batch``: ids = src[start + j], labels = src[start + j + 1], int64 [N, S]."""
     src = torch.as_tensor(src)

@@ -5,6 +5,7 @@
     python -m k8s_amd.tools.make_dataset --out DIR --cifar10-batches DIR_WITH_PICKLES
     python -m k8s_amd.tools.make_dataset --out DIR --toy-tokens [--seed 0] [--train-docs 512] [--val-docs 64]
                                                    [--vocab 512] [--segments-per-doc 2 6]
+                                                   [--tokens-per-segment 4 12]
 
 ``--toy``: a learnable set that is a pure function of its seed. Class k is a fixed random 5x5x3 uint8 prototype
 (numpy Philox key 7, the same for every seed) upscaled to ``--size`` (x8 to 40x40 by default, nearest cell at other
@@ -12,7 +13,8 @@ sizes); Gaussian noise of sigma 48 is added and the result clipped to uint8; lab
 
 ``--toy-tokens``: a learnable token set (``k8s_amd.data.tokens``) that is a pure function of its seed, for the BERT
 and Llama models. Specials pad 0, cls 1, sep 2, mask 3; 8 topics, topic k owning the ids 8 + 63 k .. 8 + 63 k + 62. A
-document draws one topic, 2 to 6 segments (``--segments-per-doc LO HI``) and 4 to 12 tokens per segment; a segment's first token is uniform in the
+document draws one topic, 2 to 6 segments (``--segments-per-doc LO HI``) and 4 to 12 tokens per segment
+(``--tokens-per-segment LO HI``; the defaults leave the files unchanged); a segment's first token is uniform in the
 topic's slice and each later one is ``base + (5 * prev_off + 1) mod 63`` with probability 0.9, else uniform in the
 slice.
 
@@ -66,16 +68,18 @@ TOY_TOPICS, TOY_SLICE, TOY_FIRST_ID = 8, 63, 8
 TOY_SPECIAL = {"pad": 0, "cls": 1, "sep": 2, "mask": 3}
 
 
-def toy_token_split(seed: int, which: int, documents: int, segments_per_doc=(2, 6)):
+def toy_token_split(seed: int, which: int, documents: int, segments_per_doc=(2, 6), tokens_per_segment=(4, 12)):
     """(tokens int64 [T], segments int64 [G + 1], docs int64 [D + 1]) of split number ``which`` for ``seed``; a
-    document holds ``segments_per_doc`` = (lo, hi) segments, both ends included."""
+    document holds ``segments_per_doc`` = (lo, hi) segments of ``tokens_per_segment`` = (lo, hi) tokens, both ends
+    included."""
     seg_lo, seg_hi = int(segments_per_doc[0]), int(segments_per_doc[1])
+    tok_lo, tok_hi = int(tokens_per_segment[0]), int(tokens_per_segment[1])
     g = np.random.Generator(np.random.Philox(np.random.SeedSequence([0x70F7, int(seed), int(which)])))
     tokens, segments, docs = [], [0], [0]
     for _ in range(documents):
         base = TOY_FIRST_ID + TOY_SLICE * int(g.integers(0, TOY_TOPICS))
         for _ in range(int(g.integers(seg_lo, seg_hi + 1))):
-            n = int(g.integers(4, 13))
+            n = int(g.integers(tok_lo, tok_hi + 1))
             follow, fresh = g.random(n) < 0.9, g.integers(0, TOY_SLICE, size=n)
             off = int(fresh[0])
             tokens.append(base + off)
@@ -88,7 +92,7 @@ def toy_token_split(seed: int, which: int, documents: int, segments_per_doc=(2, 
 
 
 def make_toy_tokens(out: str, seed: int = 0, train_docs: int = 512, val_docs: int = 64, vocab: int = 512,
-                    segments_per_doc=(2, 6)) -> None:
+                    segments_per_doc=(2, 6), tokens_per_segment=(4, 12)) -> None:
     if vocab < TOY_FIRST_ID + TOY_TOPICS * TOY_SLICE:
         raise ValueError("--vocab must be at least %d (8 specials and reserved ids, 8 topics of 63 ids)"
                          % (TOY_FIRST_ID + TOY_TOPICS * TOY_SLICE))
@@ -96,8 +100,11 @@ def make_toy_tokens(out: str, seed: int = 0, train_docs: int = 512, val_docs: in
         raise ValueError("--train-docs and --val-docs must be at least 2 (sentence pairs need another document)")
     if not 1 <= int(segments_per_doc[0]) <= int(segments_per_doc[1]):
         raise ValueError("--segments-per-doc LO HI must satisfy 1 <= LO <= HI")
-    write_token_dataset(out, vocab, {"train": toy_token_split(seed, 0, train_docs, segments_per_doc),
-                                     "val": toy_token_split(seed, 1, val_docs, segments_per_doc)}, TOY_SPECIAL)
+    if not 1 <= int(tokens_per_segment[0]) <= int(tokens_per_segment[1]):
+        raise ValueError("--tokens-per-segment LO HI must satisfy 1 <= LO <= HI")
+    split = lambda which, documents: toy_token_split(seed, which, documents, segments_per_doc,  # noqa: E731
+                                                     tokens_per_segment)
+    write_token_dataset(out, vocab, {"train": split(0, train_docs), "val": split(1, val_docs)}, TOY_SPECIAL)
 
 
 def read_cifar_batch(path: str):
@@ -140,10 +147,14 @@ def main(argv=None) -> int:
     ap.add_argument("--segments-per-doc", type=int, nargs=2, default=[2, 6], metavar=("LO", "HI"),
                     help="--toy-tokens: segments per document, both ends included (documents of HI * 8 tokens on "
                          "average at LO = HI)")
+    ap.add_argument("--tokens-per-segment", type=int, nargs=2, default=[4, 12], metavar=("LO", "HI"),
+                    help="--toy-tokens: tokens per segment, both ends included (8 56: BERT pairs that fill about "
+                         "half of --seq 128)")
     a = ap.parse_args(argv)
     try:
         if a.toy_tokens:
-            make_toy_tokens(a.out, a.seed, a.train_docs, a.val_docs, a.vocab, tuple(a.segments_per_doc))
+            make_toy_tokens(a.out, a.seed, a.train_docs, a.val_docs, a.vocab, tuple(a.segments_per_doc),
+                            tuple(a.tokens_per_segment))
         elif a.toy:
             make_toy(a.out, a.seed, a.train, a.val, a.classes, a.size)
         else:

@@ -22,6 +22,9 @@ process exit code (`/root/reference/pkg/trainer/training.go:45-73`):
   fixed training batch, an ``eval`` event (loss, top-1 / top-5 or perplexity) and ``eval/*`` TensorBoard scalars;
 * ``--doc-mask`` (Llama on ``--data-dir``): document-boundary attention masks, positions that restart per document
   and no label across a boundary (``ops.data.causal_doc_batch``, the DOC forms of the flash kernels);
+* ``--unpad`` (BERT on ``--data-dir``, no dropout): a batch is one unpadded token stream
+  (``ops.data.mlm_batch_unpadded``, ``BertForPreTraining.forward_unpadded``, the SPAN forms of the flash kernels);
+  ``tokens_per_sec`` still counts ``batch x seq`` positions and ``real_tokens_per_sec`` the non-pad ones;
 * data: synthetic batches of the model's shape, or ``--data-dir``: a dataset directory (``k8s_amd.data``; images for
   the ResNet models, tokens for BERT and Llama) whose ``train`` split feeds the fused augmentation / token batch
   kernel and whose ``val`` split is the held-out evaluation data;
@@ -122,6 +125,9 @@ def parse(argv=None):
     ap.add_argument("--data-resident-gb", type=float, default=4.0,
                     help="--data-dir: a split up to this many GiB is uploaded once; a larger one is streamed batch "
                          "by batch by a background thread (0: always streamed)")
+    ap.add_argument("--unpad", action="store_true",
+                    help="BERT on --data-dir: train without padding -- a batch is one token stream, its sequences back "
+                         "to back, attention confined to each by a span mask (not with --dropout)")
     ap.add_argument("--doc-mask", action="store_true",
                     help="Llama on --data-dir: attention stays inside each token's document, RoPE positions restart "
                          "at every document and a document's last token predicts nothing (the dataset needs its "
@@ -372,6 +378,12 @@ def train(a) -> int:
         config_error = "--doc-mask masks the document boundaries of a token dataset: it needs --data-dir"
     elif a.doc_mask and not a.model.startswith("llama"):
         config_error = "--doc-mask is implemented for the Llama models only, not %s" % a.model
+    elif a.unpad and not a.data_dir:
+        config_error = "--unpad removes the padding of a token dataset's batches: it needs --data-dir"
+    elif a.unpad and not a.model.startswith("bert"):
+        config_error = "--unpad is implemented for the BERT models only, not %s" % a.model
+    elif a.unpad and a.dropout > 0:
+        config_error = "--unpad cannot be combined with --dropout (the span kernels have no dropout form)"
     if config_error:
         print("error: %s" % config_error, file=sys.stderr, flush=True)
         return EXIT_PERMANENT
@@ -407,6 +419,8 @@ def train(a) -> int:
         data = {"dir": a.data_dir, "resident_gb": a.data_resident_gb, "seed": a.seed, "rank": rank, "world": world}
         if a.doc_mask:
             data["doc_mask"] = True
+        if a.unpad:
+            data["unpad"] = True
         try:
             if a.model.startswith("resnet"):
                 data.update(augment=a.augment or "crop", crop_pad=4 if a.crop_pad is None else a.crop_pad)
@@ -614,6 +628,9 @@ def _train(a, w, info, dev, use_cuda, batch, opt_name, sharded, comm, metrics, t
         evaluate(start_step - 1)
     t_last, n_last = time.time(), 0
     loss_v = float("nan")
+    # --unpad: the non-pad positions of the window's batches, from the loader's host plans
+    unpad_loader = w.meta.get("loader") if getattr(w.meta.get("loader"), "unpad", False) else None
+    real_last = 0
     try:
         for step in range(start_step, a.steps):
             if step == a.fail_at_step and a.ckpt_dir:
@@ -632,6 +649,8 @@ def _train(a, w, info, dev, use_cuda, batch, opt_name, sharded, comm, metrics, t
                     begin()
                     with tracer.phase("data"):
                         inputs = w.batch(step)
+                    if unpad_loader is not None:
+                        real_last += unpad_loader.last_real_tokens
                     with tracer.phase("forward"):
                         loss = w.loss(inputs)
                     with tracer.phase("backward"):
@@ -648,6 +667,8 @@ def _train(a, w, info, dev, use_cuda, batch, opt_name, sharded, comm, metrics, t
                         begin(sync=last)
                         with tracer.phase("data"):
                             inputs = w.batch(step * micro + k)
+                        if unpad_loader is not None:
+                            real_last += unpad_loader.last_real_tokens
                         with tracer.phase("forward"):
                             loss_k = w.loss(inputs)
                         with tracer.phase("backward"):
@@ -690,11 +711,13 @@ def _train(a, w, info, dev, use_cuda, batch, opt_name, sharded, comm, metrics, t
                     trust = (opt.trust_ratio_stats() if chief and opt_name in ("lars", "lamb") else None) or {}
                     if epoch_steps:  # the epoch of the step's first batch
                         extra["epoch"] = step * micro // epoch_steps
+                    if unpad_loader is not None:  # (this rank's count times world, as the rate above)
+                        extra["real_tokens_per_sec"] = round(real_last * world / max(now - t_last, 1e-9), 2)
                     metrics.event(event="step", step=step, loss=loss_v, lr=cur_lr,
                                   **{"%s_per_sec" % w.unit: round(rate, 2)}, **extra, **trust)
                     metrics.scalars(step, {"loss": loss_v, "%s_per_sec" % w.unit: rate, "learning_rate": cur_lr,
                                            **trust})
-                t_last, n_last = now, 0
+                t_last, n_last, real_last = now, 0, 0
             if a.eval_every and ((step + 1) % a.eval_every == 0 or step + 1 == a.steps):
                 t_last += evaluate(step)  # evaluation time is not part of the training throughput window
             if a.ckpt_dir and a.ckpt_every and (step + 1) % a.ckpt_every == 0 and step + 1 < a.steps:
