@@ -37,12 +37,22 @@
 //   dQ in a second kernel shaped like the forward (per query block: S^T, dP^T recomputed, dQ^T += K^T dS^T),
 //   so no fp32 atomics; delta = rowsum(dO * O) is a tiny kernel ahead of both. lse / delta rows are padded
 //   to a multiple of 64 so a query tile's 256 B of each can be staged by one global_load_lds.
-//   Dropout on the probabilities (DROP forms, D = 64, flash_dropout_fused): with P~ = keep ? P : 0 and the forward's
+//   Dropout on the probabilities (DROP forms, D = 64): with P~ = keep ? P : 0 and the forward's
 //   O = scale * P~ V, dV^T += dO^T P~ (scaled where the fp32 sum leaves) and dS = P (keep ? scale * dP : 0 - delta);
 //   delta is unchanged, since O carries the dropped, scaled probabilities. The keep test takes the absolute query row
 //   and key; the queries' row keys come from a table written beside delta (flash_rowkey_kernel).
+//
+// Masks: a call masks at most one thing beyond causal / kv_lens, its AttnMask kind (launchers.h): Plain, Drop, Doc
+// (document boundaries inside the causal triangle) or Span (bidirectional spans). The three tiled kernels take the
+// kind as one template argument; Doc and Span read one table pair (mask_lo, mask_hi) through MaskRow, whose clamps are
+// the only guard between device tables and trip counts.
+// Host side: flash_plan says, for a shape and a kind, whether the kernels take the call and which of them run
+// (forward tile and stage buffers; one-block or three-kernel backward, its tile, the dQ's QS, the dK/dV split, the
+// row-key table). launch_flash_fwd / launch_flash_bwd throw its reason or look the plan's form up in the tables of
+// instantiations (kFwdForms, kBwdForms); the binding sizes its workspaces from the same plan.
 #include <algorithm>
 #include <stdexcept>
+#include <string>
 #include <type_traits>
 #include <cstdlib>
 
@@ -110,6 +120,26 @@ __device__ __forceinline__ const uint16_t* kh_src(const uint16_t* base, long rst
   return base + (long)gr * rstride + half * 64 + c * 8;
 }
 
+// One batch row of the Doc / Span table pair (int32 [n], n = Sq = Sk), read through the clamps lo into [0, i] and hi
+// into [i + 1, n] with i itself clamped to the row. The tables are device data the host never reads, and the clamps are
+// all that stands between them and a trip count or an address: after them lo_of(i) <= i < hi_of(i), so a tile range
+// [lo_of(first) / TILE, ceil(hi_of(last) / TILE)) stays inside the row's tiles and is never empty. A wave-uniform i
+// reads through a scalar load.
+struct MaskRow {
+  const int *lo, *hi;
+  int n;
+  __device__ __forceinline__ MaskRow(const int* lo_, const int* hi_, int b, int n_)
+      : lo(lo_ + (long)b * n_), hi(hi_ + (long)b * n_), n(n_) {}
+  __device__ __forceinline__ int lo_of(int i) const {
+    const int ic = min(i, n - 1);
+    return max(0, min(lo[ic], ic));
+  }
+  __device__ __forceinline__ int hi_of(int i) const {
+    const int ic = min(i, n - 1);
+    return min(n, max(hi[ic], ic + 1));
+  }
+};
+
 // =============================================================================== forward
 // NB: K/V stage buffers (1: every key in one tile, Sk <= TILE -- the short-sequence form, no second buffer).
 // QS: 16-query sets per wave (2: 128-query blocks. 1 -- 64-query blocks, 110 VGPRs / 4 blocks per CU -- measured
@@ -117,28 +147,28 @@ __device__ __forceinline__ const uint16_t* kh_src(const uint16_t* base, long rst
 // DROP: dropout on the probabilities (rng.h; row = (b * Hq + h) * Sq + query, col = key). The lane's QS rowkeys are
 // computed once; after the row sum (l keeps the undropped sum) each probability is kept or zeroed on its way into the
 // PV product, and the scale is folded into the epilogue's 1 / l.
-// DOC: document-boundary mask inside the causal triangle (query i sees the keys doc_lo[i] <= j <= i; NB = 2 forms).
+// DOC: document-boundary mask inside the causal triangle (query i sees the keys mask_lo[i] <= j <= i; NB = 2 forms).
 // The tables ascend along the row, so the block's smallest lo is that of its first query and its largest that of its
 // last valid one: the key tiles start at the first one's tile, the tiles below the second are masked, and a wave
-// skips a tile that ends at or below the lo of its first query. Every lo is clamped into [0, query] before use, so no
-// table content moves a trip count outside [0, ntiles] or an address outside the tensors.
-// SPAN: bidirectional span mask (query i sees the keys span_lo[i] <= j < span_hi[i]; non-causal self-attention, D = 64,
+// skips a tile that ends at or below the lo of its first query (every lo through MaskRow's clamp).
+// SPAN: bidirectional span mask (query i sees the keys mask_lo[i] <= j < mask_hi[i]; non-causal self-attention, D = 64,
 // NB = 2 forms). Both tables ascend along the row, so the block's key tiles are [lo(first query) / TILE,
 // ceil(hi(last query) / TILE)); the tiles from lo(last query) up to hi(first query) lie inside every query's span and
 // run the mask-free body, the others are masked per score, and a wave skips a tile outside [lo(its first query),
-// hi(its last query)). They run in the DOC forms' order: mask-free, leading, trailing. lo is clamped into [0, query]
-// and hi into [query + 1, Sq] before use, so the tile range stays inside [0, ntiles) and is never empty.
-template <int D, int TILE, int NB = 2, int QS = 2, bool DROP = false, bool DOC = false, bool SPAN = false>
-// (DROP on the one-tile form: 2 blocks per CU -- the mask's integer temporaries beside the 128-key score tile do not
+// hi(its last query)). They run in the DOC forms' order: mask-free, leading, trailing.
+// Blocks per CU. DROP on the one-tile form: 2 -- the mask's integer temporaries beside the 128-key score tile do not
 // fit the 168 registers of 3. On 64-key tiles they do: bounded to 3 blocks per CU like the plain form, which left
-// alone took 174 registers)
-// (DOC on 64-key tiles at D = 64: bounded to the 3 blocks per CU the plain form reaches; left alone it took 194)
-// (SPAN on 64-key tiles: the same bound)
-__global__ void __launch_bounds__(FA_THREADS,
-                                  NB == 1 && !DROP ? (QS == 1 ? 4 : 3)
-                                                   : ((DROP || ((DOC || SPAN) && D == 64)) && TILE == 64 ? 3 : 2))
-flash_fwd_kernel(AttnFwdArgs a) {
-  static_assert(!SPAN || (D == 64 && NB == 2 && !DROP && !DOC), "the span forms: D = 64, multi-tile, no dropout");
+// alone took 174 registers. DOC on 64-key tiles at D = 64: bounded to the 3 the plain form reaches (left alone it took
+// 194), and SPAN on 64-key tiles the same.
+template <int D, int TILE, int NB, int QS, AttnMask M>
+constexpr int fwd_blocks_per_cu() {
+  constexpr bool DROP = M == AttnMask::Drop, TAB = M == AttnMask::Doc || M == AttnMask::Span;
+  return NB == 1 && !DROP ? (QS == 1 ? 4 : 3) : ((DROP || (TAB && D == 64)) && TILE == 64 ? 3 : 2);
+}
+template <int D, int TILE, int NB = 2, int QS = 2, AttnMask M = AttnMask::Plain>
+__global__ void __launch_bounds__(FA_THREADS, (fwd_blocks_per_cu<D, TILE, NB, QS, M>())) flash_fwd_kernel(AttnFwdArgs a) {
+  constexpr bool DROP = M == AttnMask::Drop, DOC = M == AttnMask::Doc, SPAN = M == AttnMask::Span;
+  static_assert(!SPAN || (D == 64 && NB == 2), "the span forms: D = 64, multi-tile");
   constexpr bool TAB = DOC || SPAN;  // the tiles come from a mask table and run out of key order
   constexpr int BM = 64 * QS;  // queries per block
   constexpr int FA_BN = TILE;  // keys per iteration
@@ -168,46 +198,31 @@ flash_fwd_kernel(AttnFwdArgs a) {
   // (block- / wave-uniform: scalar loads), lo of the lane's queries
   int t0 = 0, tlo = 0, lo_w0 = 0, lo_w1 = 0, lo_q[QS];
   if constexpr (DOC) {
-    const int* lop = a.doc_lo + (long)b * a.Sq;
-    const int qe = a.Sq - 1;
-    auto lo_of = [&](int qi) {
-      const int qc = min(qi, qe);
-      return max(0, min(lop[qc], qc));
-    };
-    t0 = lo_of(q0) / FA_BN;  // q0 < kv_stop, so t0 < ntiles
-    tlo = min((lo_of(q0 + BM - 1) + FA_BN - 1) / FA_BN, ntiles);
-    lo_w0 = lo_of(q0w);
-    lo_w1 = lo_of(q0w + 16 * QS - 1);
+    const MaskRow mr(a.mask_lo, a.mask_hi, b, a.Sq);
+    t0 = mr.lo_of(q0) / FA_BN;  // q0 < kv_stop, so t0 < ntiles
+    tlo = min((mr.lo_of(q0 + BM - 1) + FA_BN - 1) / FA_BN, ntiles);
+    lo_w0 = mr.lo_of(q0w);
+    lo_w1 = mr.lo_of(q0w + 16 * QS - 1);
 #pragma unroll
-    for (int qs = 0; qs < QS; ++qs) lo_q[qs] = lo_of(q0w + qs * 16 + li);
+    for (int qs = 0; qs < QS; ++qs) lo_q[qs] = mr.lo_of(q0w + qs * 16 + li);
   }
   // (SPAN) one past the block's last key tile, the first tile past the mask-free ones, hi of the wave's first and last
   // query, hi of the lane's queries
   int tend = ntiles, thi = 0, hi_w0 = 0, hi_w1 = 0, hi_q[QS];
   if constexpr (SPAN) {
-    const int* lop = a.span_lo + (long)b * a.Sq;
-    const int* hip = a.span_hi + (long)b * a.Sq;
-    const int qe = a.Sq - 1;
-    auto lo_of = [&](int qi) {
-      const int qc = min(qi, qe);
-      return max(0, min(lop[qc], qc));
-    };
-    auto hi_of = [&](int qi) {
-      const int qc = min(qi, qe);
-      return min(a.Sq, max(hip[qc], qc + 1));
-    };
-    t0 = lo_of(q0) / FA_BN;  // lo <= q0, hi > q0: t0 < tend <= ntiles
-    tend = min(ntiles, (hi_of(q0 + BM - 1) + FA_BN - 1) / FA_BN);
-    tlo = (lo_of(q0 + BM - 1) + FA_BN - 1) / FA_BN;
-    thi = hi_of(q0) / FA_BN;
-    lo_w0 = lo_of(q0w);
-    lo_w1 = lo_of(q0w + 16 * QS - 1);
-    hi_w0 = hi_of(q0w);
-    hi_w1 = hi_of(q0w + 16 * QS - 1);
+    const MaskRow mr(a.mask_lo, a.mask_hi, b, a.Sq);
+    t0 = mr.lo_of(q0) / FA_BN;  // t0 < tend <= ntiles
+    tend = min(ntiles, (mr.hi_of(q0 + BM - 1) + FA_BN - 1) / FA_BN);
+    tlo = (mr.lo_of(q0 + BM - 1) + FA_BN - 1) / FA_BN;
+    thi = mr.hi_of(q0) / FA_BN;
+    lo_w0 = mr.lo_of(q0w);
+    lo_w1 = mr.lo_of(q0w + 16 * QS - 1);
+    hi_w0 = mr.hi_of(q0w);
+    hi_w1 = mr.hi_of(q0w + 16 * QS - 1);
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) {
-      lo_q[qs] = lo_of(q0w + qs * 16 + li);
-      hi_q[qs] = hi_of(q0w + qs * 16 + li);
+      lo_q[qs] = mr.lo_of(q0w + qs * 16 + li);
+      hi_q[qs] = mr.hi_of(q0w + qs * 16 + li);
     }
   }
 
@@ -504,15 +519,16 @@ __global__ void __launch_bounds__(256) flash_rowkey_kernel(uint32_t* rowkey, Dro
 // more -- a whole wave's 64 x 16 B, which also keeps the stages 1 KB aligned), P~ = keep ? P : 0 feeds dV,
 // dS = P (scale * keep * dP - delta) feeds dK, and dV takes drop.scale where the fp32 accumulator leaves (the bf16
 // copy-out here, or flash_dkv_reduce_kernel behind the split partials).
-// DOC: the document mask (key j is seen by the queries j <= i < doc_hi[j]; hi ascends along the row): the query walk
-// of a key block ends at the tile holding the last query of its last valid key's document, and the lane's hi, clamped
-// into [key + 1, Sq], joins the mask test.
-// SPAN: the span mask (key j is seen by the queries span_lo[j] <= i < span_hi[j], the tables ascending): the query
-// walk of a key block is [lo(first key) / TILE, ceil(hi(last key) / TILE)), never empty since lo <= key < hi after
-// the clamps, and the lane's lo and hi replace the causal test.
-template <int D, int TILE, bool DROP = false, bool DOC = false, bool SPAN = false>
+// DOC: the document mask (key j is seen by the queries j <= i < mask_hi[j]; hi ascends along the row): the query walk
+// of a key block ends at the tile holding the last query of its last valid key's document, and the lane's hi joins
+// the mask test.
+// SPAN: the span mask (key j is seen by the queries mask_lo[j] <= i < mask_hi[j], the tables ascending): the query
+// walk of a key block is [lo(first key) / TILE, ceil(hi(last key) / TILE)), and the lane's lo and hi replace the
+// causal test. (Both through MaskRow's clamps, indexed by key: Sq == Sk.)
+template <int D, int TILE, AttnMask M = AttnMask::Plain>
 __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArgs a) {
-  static_assert(!SPAN || (D == 64 && !DROP && !DOC), "the span forms: D = 64, no dropout");
+  constexpr bool DROP = M == AttnMask::Drop, DOC = M == AttnMask::Doc, SPAN = M == AttnMask::Span;
+  static_assert(!SPAN || D == 64, "the span forms: D = 64");
   constexpr int ND = D / 16, NK = D / 32;
   constexpr int FB_BM = TILE;              // queries per iteration
   constexpr int NQ = FB_BM / 16;           // 16-query subtiles
@@ -548,33 +564,20 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_dkv_kernel(AttnBwdArg
   int nqt = (a.Sq + FB_BM - 1) / FB_BM;
   int hi_k0 = 0, hi_key = 0;  // (DOC) hi of the block's first key (its smallest) and of the lane's key
   if constexpr (DOC) {
-    const int* hip = a.doc_hi + (long)b * a.Sq;
-    auto hi_of = [&](int key) {
-      const int kc = min(key, a.Sk - 1);
-      return min(a.Sq, max(hip[kc], kc + 1));
-    };
-    hi_k0 = hi_of(k0);
-    hi_key = hi_of(kw + li);
-    nqt = min(nqt, (hi_of(k0 + FB_BN - 1) + FB_BM - 1) / FB_BM);  // > qt0: that hi lies past k0
+    const MaskRow mr(a.mask_lo, a.mask_hi, b, a.Sq);
+    hi_k0 = mr.hi_of(k0);
+    hi_key = mr.hi_of(kw + li);
+    nqt = min(nqt, (mr.hi_of(k0 + FB_BN - 1) + FB_BM - 1) / FB_BM);  // > qt0: that hi lies past k0
   }
   int lo_k1 = 0, lo_key = 0;  // (SPAN) lo of the block's last key (its largest) and of the lane's key; hi as DOC's
   if constexpr (SPAN) {
-    const int* lop = a.span_lo + (long)b * a.Sq;
-    const int* hip = a.span_hi + (long)b * a.Sq;
-    auto lo_of = [&](int key) {
-      const int kc = min(key, a.Sk - 1);
-      return max(0, min(lop[kc], kc));
-    };
-    auto hi_of = [&](int key) {
-      const int kc = min(key, a.Sk - 1);
-      return min(a.Sq, max(hip[kc], kc + 1));
-    };
-    hi_k0 = hi_of(k0);
-    hi_key = hi_of(kw + li);
-    lo_k1 = lo_of(k0 + FB_BN - 1);
-    lo_key = lo_of(kw + li);
-    qt0 = lo_of(k0) / FB_BM;  // lo <= k0 < hi: qt0 < nqt
-    nqt = min(nqt, (hi_of(k0 + FB_BN - 1) + FB_BM - 1) / FB_BM);
+    const MaskRow mr(a.mask_lo, a.mask_hi, b, a.Sq);
+    hi_k0 = mr.hi_of(k0);
+    hi_key = mr.hi_of(kw + li);
+    lo_k1 = mr.lo_of(k0 + FB_BN - 1);
+    lo_key = mr.lo_of(kw + li);
+    qt0 = mr.lo_of(k0) / FB_BM;  // qt0 < nqt
+    nqt = min(nqt, (mr.hi_of(k0 + FB_BN - 1) + FB_BM - 1) / FB_BM);
   }
   const int per_head = nqt - qt0;
   const int total = (k0 < kv_end && per_head > 0) ? rep * per_head : 0;
@@ -808,9 +811,10 @@ __global__ void __launch_bounds__(256) flash_dkv_reduce_kernel(AttnBwdArgs a) {
 // SPAN: the forward's span mask: the key tiles [lo(first query) / TILE, ceil(hi(last query) / TILE)) in key order, a
 // wave skips a tile outside [lo(its first query), hi(its last query)), and the lane's clamped lo and hi make the
 // per-score select.
-template <int D, int TILE, int QS, bool DROP = false, bool DOC = false, bool SPAN = false>
+template <int D, int TILE, int QS, AttnMask M = AttnMask::Plain>
 __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 : 2) flash_bwd_dq_kernel(AttnBwdArgs a) {
-  static_assert(!SPAN || (D == 64 && QS == 1 && !DROP && !DOC), "the span forms: D = 64, QS = 1, no dropout");
+  constexpr bool DROP = M == AttnMask::Drop, DOC = M == AttnMask::Doc, SPAN = M == AttnMask::Span;
+  static_assert(!SPAN || (D == 64 && QS == 1), "the span forms: D = 64, QS = 1");
   constexpr int ND = D / 16, NK = D / 32;
   constexpr int FB_BN = TILE;  // keys per iteration
   constexpr int NI = FB_BN / 16;
@@ -837,41 +841,26 @@ __global__ void __launch_bounds__(FA_THREADS, (QS == 2 && D * TILE >= 8192) ? 1 
   const int ntiles = kv_stop > 0 ? (kv_stop + FB_BN - 1) / FB_BN : 0;
   int t0 = 0, lo_w0 = 0, lo_w1 = 0, lo_q[QS];  // (DOC) as the forward's
   if constexpr (DOC) {
-    const int* lop = a.doc_lo + (long)b * a.Sq;
-    const int qe = a.Sq - 1;
-    auto lo_of = [&](int qi) {
-      const int qc = min(qi, qe);
-      return max(0, min(lop[qc], qc));
-    };
-    t0 = lo_of(q0) / FB_BN;  // q0 < kv_stop, so t0 < ntiles
-    lo_w0 = lo_of(q0w);
-    lo_w1 = lo_of(q0w + QW - 1);
+    const MaskRow mr(a.mask_lo, a.mask_hi, b, a.Sq);
+    t0 = mr.lo_of(q0) / FB_BN;  // q0 < kv_stop, so t0 < ntiles
+    lo_w0 = mr.lo_of(q0w);
+    lo_w1 = mr.lo_of(q0w + QW - 1);
 #pragma unroll
-    for (int qs = 0; qs < QS; ++qs) lo_q[qs] = lo_of(q0w + 16 * qs + li);
+    for (int qs = 0; qs < QS; ++qs) lo_q[qs] = mr.lo_of(q0w + 16 * qs + li);
   }
   int tend = ntiles, hi_w0 = 0, hi_w1 = 0, hi_q[QS];  // (SPAN) as the forward's
   if constexpr (SPAN) {
-    const int* lop = a.span_lo + (long)b * a.Sq;
-    const int* hip = a.span_hi + (long)b * a.Sq;
-    const int qe = a.Sq - 1;
-    auto lo_of = [&](int qi) {
-      const int qc = min(qi, qe);
-      return max(0, min(lop[qc], qc));
-    };
-    auto hi_of = [&](int qi) {
-      const int qc = min(qi, qe);
-      return min(a.Sq, max(hip[qc], qc + 1));
-    };
-    t0 = lo_of(q0) / FB_BN;  // lo <= q0 < hi: t0 < tend <= ntiles
-    tend = min(ntiles, (hi_of(q0 + BMQ - 1) + FB_BN - 1) / FB_BN);
-    lo_w0 = lo_of(q0w);
-    lo_w1 = lo_of(q0w + QW - 1);
-    hi_w0 = hi_of(q0w);
-    hi_w1 = hi_of(q0w + QW - 1);
+    const MaskRow mr(a.mask_lo, a.mask_hi, b, a.Sq);
+    t0 = mr.lo_of(q0) / FB_BN;  // t0 < tend <= ntiles
+    tend = min(ntiles, (mr.hi_of(q0 + BMQ - 1) + FB_BN - 1) / FB_BN);
+    lo_w0 = mr.lo_of(q0w);
+    lo_w1 = mr.lo_of(q0w + QW - 1);
+    hi_w0 = mr.hi_of(q0w);
+    hi_w1 = mr.hi_of(q0w + QW - 1);
 #pragma unroll
     for (int qs = 0; qs < QS; ++qs) {
-      lo_q[qs] = lo_of(q0w + 16 * qs + li);
-      hi_q[qs] = hi_of(q0w + 16 * qs + li);
+      lo_q[qs] = mr.lo_of(q0w + 16 * qs + li);
+      hi_q[qs] = mr.hi_of(q0w + 16 * qs + li);
     }
   }
 
@@ -1311,240 +1300,184 @@ __global__ void __launch_bounds__(FA_THREADS, 2) flash_bwd_short_kernel(AttnBwdA
   }
 }
 
-bool flash_bwd_one_block(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split) {
-  static const bool on = [] {
-    const char* e = std::getenv("K8S_AMD_FA_SHORT_BWD");
-    return !(e && e[0] == '0');
-  }();
-  return on && D == 64 && Sq > 0 && Sk > 0 && Sq <= FS_S && Sk <= FS_S && Hq == Hkv && dkv_split == 1;
-}
-
-// Dropout on the probabilities is fused for the one-block shapes and, in the multi-tile forward and the three-kernel
-// backward, for D = 64 with Sq and Sk multiples of 64 (BERT's 128 / 256 / 384 / 512; key ends inside a tile still
-// come from kv_lens and causal diagonals). Other lengths above 128 and D = 128 run the reference composition, counted.
-bool flash_dropout_fused(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split) {
-  if (flash_bwd_one_block(D, Sq, Sk, Hq, Hkv, dkv_split)) return true;
-  return D == 64 && Sq > 0 && Sk > 0 && Sq % 64 == 0 && Sk % 64 == 0 && Hkv > 0 && Hq % Hkv == 0;
-}
-
-// =============================================================================== launchers
-// D = 64 with long sequences: 128-wide key / query steps (same MFMA work per barrier as D = 128)
-static bool big_tile(int D, int S) { return D == 64 && S >= 1024; }
-
-// what the DOC forms are defined for
-static bool flash_doc_ok(const int* lo, const int* hi, int Sq, int Sk, int causal, const int* kv_lens,
-                         const void* drop_state) {
-  return lo && hi && causal && Sq == Sk && !kv_lens && !drop_state;
-}
-
-// what the SPAN forms are defined for: both tables, non-causal self-attention at D = 64, nothing else masked, a tile
-// they are instantiated with and a shape inside their index limits (flash_span_ok)
-int flash_span_tile(int S) {
-  (void)S;  // the 128-key form is instantiated and selectable (span_tile); every length takes the 64-key tiles by default
-  return 64;
-}
-
-bool flash_span_ok(int D, long B, long Sq, long Sk, long Hq, long max_token_stride) {
-  return D == 64 && B > 0 && Hq > 0 && Sq > 0 && Sq == Sk && Sq < (1L << 24) && B * Hq * Sq < (1L << 31) &&
-         max_token_stride < (1L << 24);
-}
-
-template <class Args>
-static bool flash_span_args_ok(const Args& a, int D, long max_token_stride) {
-  return a.span_lo && a.span_hi && !a.doc_lo && !a.doc_hi && !a.causal && !a.kv_lens && !a.drop.state &&
-         (a.span_tile == 0 || a.span_tile == 64 || a.span_tile == 128) &&
-         flash_span_ok(D, a.B, a.Sq, a.Sk, a.Hq, max_token_stride);
-}
-
+// =============================================================================== plan
 // dK/dV chunks per key block: causal key blocks carry from 1 to Sq / 64 query tiles of work, so with one block per
 // key block the first ones ran long after the rest of the chip had drained. Split each key block's (head, query tile)
 // walk into chunks (fp32 partials + a reduce pass) while the grid stays small enough for the partials to be cheap.
-int flash_dkv_splits(int B, int Sq, int Sk, int Hkv, int causal) {
+static int dkv_splits(long B, long Sq, long Sk, long Hkv, bool causal) {
   if (!causal) return 1;
-  const long nblk = (long)((Sk + FB_BN - 1) / FB_BN) * Hkv * B;
-  const int per_block = (Sq + 63) / 64;  // query tiles of the heaviest key block (per query head)
+  const long nblk = (Sk + FB_BN - 1) / FB_BN * Hkv * B;
+  const long per_block = (Sq + 63) / 64;  // query tiles of the heaviest key block (per query head)
   if (per_block < 8) return 1;
   // measured at 512 key blocks (Llama-3-8B s4096 / s2048 b2): 2 chunks 585 / 357 us, 4 chunks 601 / 367, 8 chunks 668 / 435
   const long cus = planner_cus();  // thresholds measured on 256 CUs: 1024 and 384 key blocks
   return nblk >= 4 * cus ? 1 : (2 * nblk >= 3 * cus ? 2 : 4);
 }
 
-// D = 64, Sk <= 128: every key in one 128-key tile, one stage buffer (K8S_AMD_FA_ONE_TILE=0 keeps the 64-key tiles)
-static bool fwd_one_tile() {
-  static const bool on = [] {
-    const char* e = std::getenv("K8S_AMD_FA_ONE_TILE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
+static bool env_on(const char* name) {  // unset, or anything but a leading '0'
+  const char* e = std::getenv(name);
+  return !(e && e[0] == '0');
 }
+
+FlashPlan flash_plan(int D, long B, long Sq, long Sk, long Hq, long Hkv, bool causal, bool has_kv_lens, AttnMask mask,
+                     int span_tile, long max_token_stride, bool want_dbias) {
+  // K8S_AMD_FA_ONE_TILE=0 keeps the 64-key tiles in the short forward, K8S_AMD_FA_SHORT_BWD=0 the three-kernel backward
+  static const bool one_tile_on = env_on("K8S_AMD_FA_ONE_TILE"), short_bwd_on = env_on("K8S_AMD_FA_SHORT_BWD");
+  FlashPlan p;
+  auto no = [&p](const char* why) {
+    p.ok = false;
+    p.reason = why;
+    return p;
+  };
+  if (!((D == 64 || D == 128) && B > 0 && Sq > 0 && Sk > 0 && Hkv > 0 && Hq > 0 && Hq % Hkv == 0))
+    return no("the flash kernels take head dim 64 or 128, non-empty operands and Hq a multiple of Hkv");
+  const bool drop = mask == AttnMask::Drop, doc = mask == AttnMask::Doc, span = mask == AttnMask::Span;
+  // the whole backward of one (batch, head) in one block (flash_bwd_short_kernel; such a shape never splits dK/dV).
+  // A table mask has no such form, and so no one-tile forward and no QS = 2 dQ either.
+  p.bwd.one_block = short_bwd_on && !doc && !span && D == 64 && Sq <= FS_S && Sk <= FS_S && Hq == Hkv;
+  // The Span forms index Sq < 2^24, B * Hq * Sq < 2^31 (grid sizes and the delta kernel's row split are 32-bit) and
+  // token strides below 2^24 elements (a tile row times the stride is a 32-bit product; batch and head strides are
+  // multiplied in 64 bits). One row of 131,072 tokens is far inside.
+  if (span && (causal || has_kv_lens || Sq != Sk || D != 64 || (span_tile != 0 && span_tile != 64 && span_tile != 128) ||
+               Sq >= (1L << 24) || B * Hq * Sq >= (1L << 31) || max_token_stride >= (1L << 24)))
+    return no("a span mask needs non-causal self-attention at head dim 64 without kv_lens, a span_tile of 0, 64 or 128, "
+              "Sq < 2^24, B * Hq * Sq < 2^31 and token strides below 2^24 elements");
+  if (!span && span_tile != 0) return no("span_tile needs a span mask");
+  if (doc && !(causal && Sq == Sk && !has_kv_lens))
+    return no("a document mask needs causal self-attention (Sq == Sk) without kv_lens");
+  // Dropout is fused for the one-block shapes and, in the multi-tile forward and the three-kernel backward, for D = 64
+  // with Sq and Sk multiples of 64 (BERT's 128 / 256 / 384 / 512; key ends inside a tile still come from kv_lens and
+  // causal diagonals). Other lengths above 128 and D = 128 run the reference composition, counted.
+  if (drop && !(p.bwd.one_block || (D == 64 && Sq % 64 == 0 && Sk % 64 == 0)))
+    return no("dropout on the probabilities needs head dim 64 and either Sq, Sk <= 128 with Hq == Hkv or Sq and Sk "
+              "multiples of 64");
+  if (want_dbias && !p.bwd.one_block)
+    return no("the bias gradient needs the one-block backward: head dim 64, Sq, Sk <= 128, Hq == Hkv and no document "
+              "or span mask");
+
+  // D = 64 with long sequences: 128-wide key / query steps (same MFMA work per barrier as D = 128); the forward steps
+  // over keys, the three-kernel backward's dK/dV over queries. The Span forms take 64 at every length unless
+  // span_tile selects their 128-wide instantiation.
+  auto big_tile = [D](long S) { return D == 64 && S >= 1024; };
+  if (span) {
+    p.fwd.tile = span_tile ? span_tile : 64;
+  } else if (big_tile(Sk)) {
+    p.fwd.tile = 128;
+  } else if (D == 64 && !doc && Sk <= 128 && one_tile_on) {  // every key in one 128-key tile, one stage buffer
+    p.fwd.tile = 128;
+    p.fwd.nb = 1;
+  }
+  if (p.bwd.one_block) {
+    p.bwd.tile = p.bwd.qs = 0;  // (of the three kernels)
+    return p;
+  }
+  p.bwd.tile = span ? p.fwd.tile : (big_tile(Sq) ? 128 : 64);
+  // dQ: QS = 2 (32 queries per wave, 128 per block) when the grid still fills the chip. With D x TILE = 8192
+  // (D = 128, or D = 64 on 128-key tiles) that form needs ~320 VGPRs (one wave per SIMD) and measured slower there
+  // (round 3), so those keep QS = 1.
+  if (D == 64 && p.bwd.tile == 64 && !doc && !span && (Sq + 127) / 128 * Hq * B >= 2L * planner_cus()) p.bwd.qs = 2;
+  p.bwd.dkv_split = dkv_splits(B, Sq, Sk, Hkv, causal);  // (1 for every non-causal call, so for every span mask)
+  p.bwd.needs_rowkey = drop;
+  return p;
+}
+
+FlashPlan flash_plan(const AttnFwdArgs& a, int D) {
+  return flash_plan(D, a.B, a.Sq, a.Sk, a.Hq, a.Hkv, a.causal != 0, a.kv_lens != nullptr, a.mask, a.span_tile,
+                    std::max({a.sqs, a.sks, a.svs, a.sos}), false);
+}
+
+FlashPlan flash_plan(const AttnBwdArgs& a, int D, long sos, bool want_dbias) {
+  return flash_plan(D, a.B, a.Sq, a.Sk, a.Hq, a.Hkv, a.causal != 0, a.kv_lens != nullptr, a.mask, a.span_tile,
+                    std::max({a.sqs, a.sks, a.svs, a.sds, sos, a.sgqs, a.sgks, a.sgvs}), want_dbias);
+}
+
+// =============================================================================== launchers
+// what the plan cannot see: the pointers behind the mask kind
+template <class Args>
+static void check_plan(const Args& a, const FlashPlan& p, const char* who) {
+  if (!p.ok) throw std::runtime_error(std::string(who) + ": " + p.reason);
+  const bool tab = a.mask == AttnMask::Doc || a.mask == AttnMask::Span;
+  if ((a.mask_lo != nullptr) != tab || (a.mask_hi != nullptr) != tab ||
+      (a.drop.state != nullptr) != (a.mask == AttnMask::Drop))
+    throw std::runtime_error(std::string(who) + ": a document or span mask needs both tables, dropout its state, and "
+                                                "no other kind may carry either");
+}
+
+// every instantiation of the tiled kernels: (D, tile, NB | QS, mask kind) as the plan names them
+struct FwdForm {
+  int D, tile, nb;
+  AttnMask mask;
+  void (*kernel)(AttnFwdArgs);
+};
+#define K8S_FWD_FORM(D, TILE, NB, M) {D, TILE, NB, AttnMask::M, flash_fwd_kernel<D, TILE, NB, 2, AttnMask::M>}
+static const FwdForm kFwdForms[] = {
+    K8S_FWD_FORM(128, 64, 2, Plain), K8S_FWD_FORM(64, 128, 2, Plain), K8S_FWD_FORM(64, 128, 1, Plain),
+    K8S_FWD_FORM(64, 64, 2, Plain),  K8S_FWD_FORM(64, 128, 2, Drop),  K8S_FWD_FORM(64, 128, 1, Drop),
+    K8S_FWD_FORM(64, 64, 2, Drop),   K8S_FWD_FORM(128, 64, 2, Doc),   K8S_FWD_FORM(64, 128, 2, Doc),
+    K8S_FWD_FORM(64, 64, 2, Doc),    K8S_FWD_FORM(64, 128, 2, Span),  K8S_FWD_FORM(64, 64, 2, Span)};
+#undef K8S_FWD_FORM
+struct BwdForm {
+  int D, tile, qs;
+  AttnMask mask;
+  void (*dkv)(AttnBwdArgs);
+  void (*dq)(AttnBwdArgs);
+};
+#define K8S_BWD_FORM(D, TILE, QS, M) \
+  {D, TILE, QS, AttnMask::M, flash_bwd_dkv_kernel<D, TILE, AttnMask::M>, flash_bwd_dq_kernel<D, TILE, QS, AttnMask::M>}
+static const BwdForm kBwdForms[] = {
+    K8S_BWD_FORM(128, 64, 1, Plain), K8S_BWD_FORM(64, 128, 1, Plain), K8S_BWD_FORM(64, 64, 1, Plain),
+    K8S_BWD_FORM(64, 64, 2, Plain),  K8S_BWD_FORM(64, 128, 1, Drop),  K8S_BWD_FORM(64, 64, 1, Drop),
+    K8S_BWD_FORM(64, 64, 2, Drop),   K8S_BWD_FORM(128, 64, 1, Doc),   K8S_BWD_FORM(64, 128, 1, Doc),
+    K8S_BWD_FORM(64, 64, 1, Doc),    K8S_BWD_FORM(64, 128, 1, Span),  K8S_BWD_FORM(64, 64, 1, Span)};
+#undef K8S_BWD_FORM
 
 void launch_flash_fwd(const AttnFwdArgs& a, int D, hipStream_t st) {
-  const int nqb = (a.Sq + FA_BM - 1) / FA_BM;
-  const dim3 grid(nqb * a.Hq * a.B), blk(FA_THREADS);
-  if (a.span_lo || a.span_hi) {  // the SPAN forms: multi-tile only, 64-key tiles unless span_tile asks for 128
-    if (!flash_span_args_ok(a, D, std::max({a.sqs, a.sks, a.svs, a.sos})))
-      throw std::runtime_error("flash_fwd: a span mask needs both tables, non-causal self-attention at head dim 64, no "
-                               "kv_lens, no dropout, no document mask and a shape of flash_span_ok");
-    if ((a.span_tile ? a.span_tile : flash_span_tile(a.Sk)) == 128)
-      hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 2, 2, false, false, true>), grid, blk, 0, st, a);
-    else
-      hipLaunchKernelGGL((flash_fwd_kernel<64, 64, 2, 2, false, false, true>), grid, blk, 0, st, a);
-    return;
-  }
-  if (a.doc_lo || a.doc_hi) {  // the DOC forms: multi-tile only (a short sequence takes the 64-key tiles)
-    if (!flash_doc_ok(a.doc_lo, a.doc_hi, a.Sq, a.Sk, a.causal, a.kv_lens, a.drop.state))
-      throw std::runtime_error("flash_fwd: a document mask needs both tables, causal self-attention, no kv_lens and "
-                               "no dropout");
-    if (D == 128) hipLaunchKernelGGL((flash_fwd_kernel<128, 64, 2, 2, false, true>), grid, blk, 0, st, a);
-    else if (big_tile(D, a.Sk)) hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 2, 2, false, true>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((flash_fwd_kernel<64, 64, 2, 2, false, true>), grid, blk, 0, st, a);
-    return;
-  }
-  if (a.drop.state) {  // the DROP form of what the plain dispatch below picks at D = 64
-    if (!flash_dropout_fused(D, a.Sq, a.Sk, a.Hq, a.Hkv, 1))
-      throw std::runtime_error("flash_fwd: dropout needs a shape of flash_dropout_fused");
-    if (big_tile(D, a.Sk)) hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 2, 2, true>), grid, blk, 0, st, a);
-    else if (a.Sk <= 128 && fwd_one_tile())
-      hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 1, 2, true>), grid, blk, 0, st, a);
-    else hipLaunchKernelGGL((flash_fwd_kernel<64, 64, 2, 2, true>), grid, blk, 0, st, a);
-    return;
-  }
-  if (D == 128) hipLaunchKernelGGL((flash_fwd_kernel<128, 64>), grid, blk, 0, st, a);
-  else if (big_tile(D, a.Sk)) hipLaunchKernelGGL((flash_fwd_kernel<64, 128>), grid, blk, 0, st, a);
-  else if (a.Sk <= 128 && fwd_one_tile()) hipLaunchKernelGGL((flash_fwd_kernel<64, 128, 1>), grid, blk, 0, st, a);
-  else hipLaunchKernelGGL((flash_fwd_kernel<64, 64>), grid, blk, 0, st, a);
-}
-
-// the three-kernel backward with dropout (D = 64): the row-key table beside delta, then the DROP forms of what the
-// plain dispatch in launch_flash_bwd picks
-static void launch_flash_bwd_drop(const AttnBwdArgs& a, const uint16_t* o, long sob, long sos, long soh,
-                                  hipStream_t st) {
-  const long R = (long)a.B * a.Sq * a.Hq;
-  hipLaunchKernelGGL(flash_delta_kernel<64>, dim3((unsigned)((R * 8 + 255) / 256)), dim3(256), 0, st, o, sob, sos, soh,
-                     a.dO, a.sdb, a.sds, a.sdh, a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
-  hipLaunchKernelGGL(flash_rowkey_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, a.rowkey, a.drop, R,
-                     a.Sq, a.lse_ld);
-  const dim3 gkv(((a.Sk + FB_BN - 1) / FB_BN) * a.Hkv * a.B * a.dkv_split), blk(FA_THREADS);
-  const bool big = big_tile(64, a.Sq);
-  const bool qs2 = !big && (long)((a.Sq + 127) / 128) * a.Hq * a.B >= 2L * planner_cus();
-  const dim3 gq(((a.Sq + (qs2 ? 127 : 63)) / (qs2 ? 128 : 64)) * a.Hq * a.B);
-  if (big) {
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 128, true>), gkv, blk, 0, st, a);
-    hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 128, 1, true>), gq, blk, 0, st, a);
-  } else {
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 64, true>), gkv, blk, 0, st, a);
-    if (qs2) hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 2, true>), gq, blk, 0, st, a);
-    else hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 1, true>), gq, blk, 0, st, a);
-  }
-  if (a.dkv_split > 1) {
-    const long n = (long)a.B * a.Hkv * a.Sk * 8;
-    hipLaunchKernelGGL((flash_dkv_reduce_kernel<64, true>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
-  }
+  const FlashPlan p = flash_plan(a, D);
+  check_plan(a, p, "flash_fwd");
+  const dim3 grid(((a.Sq + FA_BM - 1) / FA_BM) * a.Hq * a.B), blk(FA_THREADS);
+  for (const FwdForm& f : kFwdForms)
+    if (f.D == D && f.tile == p.fwd.tile && f.nb == p.fwd.nb && f.mask == a.mask) {
+      hipLaunchKernelGGL(f.kernel, grid, blk, 0, st, a);
+      return;
+    }
+  throw std::logic_error("flash_fwd: the plan names a form that is not instantiated");
 }
 
 void launch_flash_bwd(const AttnBwdArgs& a, int D, const uint16_t* o, long sob, long sos, long soh,
                       hipStream_t st) {
-  if (a.span_lo || a.span_hi) {
-    // the SPAN forms: never the one-block kernel (so no column partials), never the QS = 2 dQ, one chunk per key block
-    if (!flash_span_args_ok(a, D, std::max({a.sqs, a.sks, a.svs, a.sds, sos, a.sgqs, a.sgks, a.sgvs})) || a.cpart ||
-        a.dkv_split != 1)
-      throw std::runtime_error("flash_bwd: a span mask needs both tables, non-causal self-attention at head dim 64, no "
-                               "kv_lens, no dropout, no document mask, no bias gradient and a shape of flash_span_ok");
-    const long R = (long)a.B * a.Sq * a.Hq;
-    const dim3 gkv(((a.Sk + FB_BN - 1) / FB_BN) * a.Hkv * a.B), gq(((a.Sq + 63) / 64) * a.Hq * a.B), blk(FA_THREADS);
-    hipLaunchKernelGGL(flash_delta_kernel<64>, dim3((unsigned)((R * 8 + 255) / 256)), dim3(256), 0, st, o, sob, sos, soh,
-                       a.dO, a.sdb, a.sds, a.sdh, a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
-    if ((a.span_tile ? a.span_tile : flash_span_tile(a.Sk)) == 128) {
-      hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 128, false, false, true>), gkv, blk, 0, st, a);
-      hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 128, 1, false, false, true>), gq, blk, 0, st, a);
-    } else {
-      hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 64, false, false, true>), gkv, blk, 0, st, a);
-      hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 1, false, false, true>), gq, blk, 0, st, a);
-    }
+  const FlashPlan p = flash_plan(a, D, sos, a.cpart != nullptr);
+  check_plan(a, p, "flash_bwd");
+  const FlashPlan::Bwd& w = p.bwd;
+  if (a.dkv_split != w.dkv_split || (w.dkv_split > 1 && !a.dkv_ws) || (w.needs_rowkey && !a.rowkey))
+    throw std::runtime_error("flash_bwd: dkv_split and the dK/dV and row-key workspaces must follow flash_plan");
+  const bool drop = a.mask == AttnMask::Drop;
+  const dim3 blk(FA_THREADS), b256(256);
+  if (w.one_block) {
+    const auto kernel = drop ? flash_bwd_short_kernel<true> : flash_bwd_short_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(a.B * a.Hq)), blk, 0, st, a, o, sob, sos, soh);
     return;
   }
-  if (a.doc_lo || a.doc_hi) {
-    // the DOC forms: never the one-block kernel (so no column partials) and never the QS = 2 dQ
-    if (!flash_doc_ok(a.doc_lo, a.doc_hi, a.Sq, a.Sk, a.causal, a.kv_lens, a.drop.state) || a.cpart)
-      throw std::runtime_error("flash_bwd: a document mask needs both tables, causal self-attention, no kv_lens, no "
-                               "dropout and no bias gradient");
-    const long R = (long)a.B * a.Sq * a.Hq;
-    const dim3 dgrid((unsigned)((R * (D / 8) + 255) / 256)), blk(FA_THREADS);
-    const dim3 gkv(((a.Sk + FB_BN - 1) / FB_BN) * a.Hkv * a.B * a.dkv_split), gq(((a.Sq + 63) / 64) * a.Hq * a.B);
-    if (D == 128) {
-      hipLaunchKernelGGL(flash_delta_kernel<128>, dgrid, dim3(256), 0, st, o, sob, sos, soh, a.dO, a.sdb, a.sds, a.sdh,
-                         a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
-      hipLaunchKernelGGL((flash_bwd_dkv_kernel<128, 64, false, true>), gkv, blk, 0, st, a);
-      hipLaunchKernelGGL((flash_bwd_dq_kernel<128, 64, 1, false, true>), gq, blk, 0, st, a);
-    } else {
-      hipLaunchKernelGGL(flash_delta_kernel<64>, dgrid, dim3(256), 0, st, o, sob, sos, soh, a.dO, a.sdb, a.sds, a.sdh,
-                         a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
-      if (big_tile(D, a.Sq)) {
-        hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 128, false, true>), gkv, blk, 0, st, a);
-        hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 128, 1, false, true>), gq, blk, 0, st, a);
-      } else {
-        hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 64, false, true>), gkv, blk, 0, st, a);
-        hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 1, false, true>), gq, blk, 0, st, a);
-      }
-    }
-    if (a.dkv_split > 1) {
-      const long n = (long)a.B * a.Hkv * a.Sk * (D / 8);
-      const dim3 rg((unsigned)((n + 255) / 256));
-      if (D == 128) hipLaunchKernelGGL(flash_dkv_reduce_kernel<128>, rg, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL(flash_dkv_reduce_kernel<64>, rg, dim3(256), 0, st, a);
-    }
-    return;
-  }
-  if (flash_bwd_one_block(D, a.Sq, a.Sk, a.Hq, a.Hkv, a.dkv_split)) {
-    if ((long)a.B * a.Hq > 0) {
-      if (a.drop.state)
-        hipLaunchKernelGGL(flash_bwd_short_kernel<true>, dim3((unsigned)(a.B * a.Hq)), dim3(FA_THREADS), 0, st, a, o,
-                           sob, sos, soh);
-      else
-        hipLaunchKernelGGL(flash_bwd_short_kernel<false>, dim3((unsigned)(a.B * a.Hq)), dim3(FA_THREADS), 0, st, a, o,
-                           sob, sos, soh);
-    }
-    return;
-  }
-  if (a.drop.state) {
-    if (!flash_dropout_fused(D, a.Sq, a.Sk, a.Hq, a.Hkv, a.dkv_split) || !a.rowkey)
-      throw std::runtime_error("flash_bwd: dropout needs a shape of flash_dropout_fused and the row-key workspace");
-    launch_flash_bwd_drop(a, o, sob, sos, soh, st);
-    return;
-  }
+  const BwdForm* form = nullptr;
+  for (const BwdForm& f : kBwdForms)
+    if (f.D == D && f.tile == w.tile && f.qs == w.qs && f.mask == a.mask) form = &f;
+  if (!form) throw std::logic_error("flash_bwd: the plan names a form that is not instantiated");
   const long R = (long)a.B * a.Sq * a.Hq;
-  const int lpr = D / 8;
-  const dim3 dgrid((unsigned)((R * lpr + 255) / 256));
-  if (D == 128)
-    hipLaunchKernelGGL(flash_delta_kernel<128>, dgrid, dim3(256), 0, st, o, sob, sos, soh, a.dO, a.sdb, a.sds, a.sdh,
-                       a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
-  else
-    hipLaunchKernelGGL(flash_delta_kernel<64>, dgrid, dim3(256), 0, st, o, sob, sos, soh, a.dO, a.sdb, a.sds, a.sdh,
-                       a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
-  // dK/dV blocks own 64 keys at any D, split into a.dkv_split chunks (flash_dkv_splits)
-  const dim3 gkv(((a.Sk + FB_BN - 1) / FB_BN) * a.Hkv * a.B * a.dkv_split);
-  // dQ: QS = 2 (32 queries per wave, 128 per block) when the grid still fills the chip. With D x TILE = 8192
-  // (D = 128, or D = 64 on 128-key tiles) that form needs ~320 VGPRs (one wave per SIMD) and measured slower there
-  // (round 3), so those keep QS = 1.
-  const bool small = D == 64 && !big_tile(D, a.Sq);
-  const bool qs2 = small && (long)((a.Sq + 127) / 128) * a.Hq * a.B >= 2L * planner_cus();
-  const dim3 gq(((a.Sq + (qs2 ? 127 : 63)) / (qs2 ? 128 : 64)) * a.Hq * a.B), blk(FA_THREADS);
-  if (D == 128) {
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<128, 64>), gkv, blk, 0, st, a);
-    hipLaunchKernelGGL((flash_bwd_dq_kernel<128, 64, 1>), gq, blk, 0, st, a);
-  } else if (big_tile(D, a.Sq)) {
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 128>), gkv, blk, 0, st, a);
-    hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 128, 1>), gq, blk, 0, st, a);
-  } else {
-    hipLaunchKernelGGL((flash_bwd_dkv_kernel<64, 64>), gkv, blk, 0, st, a);
-    if (qs2) hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 2>), gq, blk, 0, st, a);
-    else hipLaunchKernelGGL((flash_bwd_dq_kernel<64, 64, 1>), gq, blk, 0, st, a);
-  }
-  if (a.dkv_split > 1) {
+  const auto delta = D == 128 ? flash_delta_kernel<128> : flash_delta_kernel<64>;
+  hipLaunchKernelGGL(delta, dim3((unsigned)((R * (D / 8) + 255) / 256)), b256, 0, st, o, sob, sos, soh, a.dO, a.sdb,
+                     a.sds, a.sdh, a.delta, a.B, a.Sq, a.Hq, a.lse_ld);
+  if (w.needs_rowkey)
+    hipLaunchKernelGGL(flash_rowkey_kernel, dim3((unsigned)((R + 255) / 256)), b256, 0, st, a.rowkey, a.drop, R, a.Sq,
+                       a.lse_ld);
+  // dK/dV blocks own 64 keys at any D, split into dkv_split chunks; dQ blocks own 64 QS queries
+  const dim3 gkv(((a.Sk + FB_BN - 1) / FB_BN) * a.Hkv * a.B * w.dkv_split);
+  const dim3 gq(((a.Sq + 64 * w.qs - 1) / (64 * w.qs)) * a.Hq * a.B);
+  hipLaunchKernelGGL(form->dkv, gkv, blk, 0, st, a);
+  hipLaunchKernelGGL(form->dq, gq, blk, 0, st, a);
+  if (w.dkv_split > 1) {
     const long n = (long)a.B * a.Hkv * a.Sk * (D / 8);
-    const dim3 rg((unsigned)((n + 255) / 256));
-    if (D == 128) hipLaunchKernelGGL(flash_dkv_reduce_kernel<128>, rg, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(flash_dkv_reduce_kernel<64>, rg, dim3(256), 0, st, a);
+    const auto reduce = D == 128 ? flash_dkv_reduce_kernel<128, false>
+                                 : (drop ? flash_dkv_reduce_kernel<64, true> : flash_dkv_reduce_kernel<64, false>);
+    hipLaunchKernelGGL(reduce, dim3((unsigned)((n + 255) / 256)), b256, 0, st, a);
   }
 }
 

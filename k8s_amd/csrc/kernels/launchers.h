@@ -349,6 +349,8 @@ void launch_act_bwd_colsum(int act, const uint16_t* dy, const uint16_t* pre, uin
                            float* out, bool accumulate, hipStream_t st);
 
 // ---- K5 flash attention (attention.hip). q [B,Sq,Hq,D], k/v [B,Sk,Hkv,D] (strided, last dim contiguous)
+// what a call masks beyond causal / kv_lens: at most one of dropout on the probabilities, a document mask, a span mask
+enum class AttnMask { Plain, Drop, Doc, Span };
 struct AttnFwdArgs {
   const uint16_t *q, *k, *v;
   uint16_t* o;
@@ -358,18 +360,17 @@ struct AttnFwdArgs {
   long lse_ld;         // row stride of lse (Sq rounded up to 64)
   int B, Sq, Sk, Hq, Hkv, causal;
   float scale_log2;
-  // dropout on the probabilities (the shapes of flash_dropout_fused): row = (b * Hq + h) * Sq + q, col = key
+  // dropout on the probabilities (AttnMask::Drop, the shapes flash_plan takes): row = (b * Hq + h) * Sq + q, col = key
   DropArgs drop;
-  // document-boundary mask (the DOC forms; causal self-attention only): int32 [B, Sq], query i sees the keys
-  // doc_lo[i] <= j <= i, and hi[j] is one past the last query that sees key j. Both or neither; device data the
-  // kernels clamp before use.
-  const int* doc_lo = nullptr;
-  const int* doc_hi = nullptr;
-  // span mask (the SPAN forms; non-causal self-attention at D = 64 only): int32 [B, Sq], query i sees the keys
-  // span_lo[i] <= j < span_hi[i]. Both or neither; clamped by the kernels before use. span_tile: keys per tile of the
-  // span forms, 64 or 128 (0: the dispatch's default, flash_span_tile).
-  const int* span_lo = nullptr;
-  const int* span_hi = nullptr;
+  // What is masked beyond causal / kv_lens, and the one table pair of the Doc and Span kinds: int32 [B, Sq], both or
+  // neither; device data the kernels clamp before use (MaskRow).
+  // Doc (causal self-attention only): query i sees the keys mask_lo[i] <= j <= i, and mask_hi[j] is one past the last
+  // query that sees key j. The forward and the dQ kernel read lo, the dK/dV kernel hi.
+  // Span (non-causal self-attention at D = 64 only): query i sees the keys mask_lo[i] <= j < mask_hi[i]. Every kernel
+  // reads both. span_tile: keys per tile of the Span forms, 64 or 128 (0: the plan's default).
+  AttnMask mask = AttnMask::Plain;
+  const int* mask_lo = nullptr;
+  const int* mask_hi = nullptr;
   int span_tile = 0;
 };
 struct AttnBwdArgs {
@@ -385,35 +386,47 @@ struct AttnBwdArgs {
   long lse_ld;
   int B, Sq, Sk, Hq, Hkv, causal;
   float scale_log2, scale;
-  // dK/dV split into dkv_split chunks per key block (flash_dkv_splits): fp32 partials [dkv_split][2][B][Hkv][Sk][D]
+  // dK/dV split into dkv_split chunks per key block (FlashPlan): fp32 partials [dkv_split][2][B][Hkv][Sk][D]
   int dkv_split = 1;
   float* dkv_ws = nullptr;
-  // one-block short-sequence form only (flash_bwd_one_block): per-batch column sums of the packed QKV gradient,
+  // one-block short-sequence form only (FlashPlan::Bwd::one_block): per-batch column sums of the packed QKV gradient,
   // fp32 [B][cpart_ld] (the projection's bias gradient once folded over B)
   float* cpart = nullptr;
   int cpart_ld = 0;
   DropArgs drop;  // as the forward's
   // dropout on the three-kernel form: the queries' row keys, [B, Hq, lse_ld] scratch next to delta (written by the
-  // delta kernel from the device [seed, step] pair, read by the dK/dV and dQ kernels)
+  // row-key kernel from the device [seed, step] pair, read by the dK/dV and dQ kernels)
   uint32_t* rowkey = nullptr;
-  const int* doc_lo = nullptr;  // as the forward's (the dQ kernel reads lo, the dK/dV kernel hi)
-  const int* doc_hi = nullptr;
-  const int* span_lo = nullptr;  // as the forward's (every kernel reads both)
-  const int* span_hi = nullptr;
+  AttnMask mask = AttnMask::Plain;  // as the forward's, with its table pair
+  const int* mask_lo = nullptr;
+  const int* mask_hi = nullptr;
   int span_tile = 0;
 };
-// keys (queries in the dK/dV kernel) per tile of the span forms when span_tile is 0
-int flash_span_tile(int S);
-// the span forms index this shape correctly: D = 64, Sq == Sk < 2^24, B * Hq * Sq < 2^31 (grid sizes and the delta
-// kernel's row split are 32-bit) and every token stride below 2^24 elements (a tile row times the stride is a 32-bit
-// product; batch and head strides are multiplied in 64 bits). One row of 131,072 tokens is far inside.
-bool flash_span_ok(int D, long B, long Sq, long Sk, long Hq, long max_token_stride);
-int flash_dkv_splits(int B, int Sq, int Sk, int Hkv, int causal);
-// the whole backward of one (batch, head) in one block (flash_bwd_short_kernel) applies to this shape
-bool flash_bwd_one_block(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split);
-// dropout on the probabilities is fused for this shape: the one-block form, or the long form (multi-tile forward and
-// three-kernel backward) at D = 64 with Sq and Sk multiples of 64
-bool flash_dropout_fused(int D, int Sq, int Sk, int Hq, int Hkv, int dkv_split);
+
+// Which kernels run for a shape, and whether the flash kernels take it at all: the one place that knows the tile
+// choice (128-key steps at D = 64 from 1024 tokens on; the forward picks by Sk, the backward by Sq), the one-tile
+// forward, the one-block backward, the QS = 2 dQ, the dK/dV split and the Span forms' index limits. A pure host
+// function of the shape (and planner_cus()); the launchers, the binding and Python all read it.
+struct FlashPlan {
+  bool ok = true;
+  const char* reason = "";  // one sentence when !ok
+  struct Fwd {
+    int tile = 64, nb = 2;  // keys per tile; stage buffers (1: the one-tile form, every key in one 128-key tile)
+  } fwd;
+  struct Bwd {
+    bool one_block = false;     // flash_bwd_short_kernel: the whole backward of a (batch, head) in one block
+    int tile = 64, qs = 1;      // (three kernels) queries / keys per step; 16-query sets per dQ wave
+    int dkv_split = 1;          // dK/dV chunks per key block (above 1: fp32 partials and the reduce kernel)
+    bool needs_rowkey = false;  // dropout on the three-kernel form: the row-key table beside delta
+  } bwd;
+};
+// max_token_stride: the largest token stride of any operand, in elements. want_dbias: the caller asks for the packed
+// projection's bias gradient (the one-block kernel's column partials).
+FlashPlan flash_plan(int D, long B, long Sq, long Sk, long Hq, long Hkv, bool causal, bool has_kv_lens, AttnMask mask,
+                     int span_tile, long max_token_stride, bool want_dbias);
+// the plan of a filled argument block (sos: o's token stride)
+FlashPlan flash_plan(const AttnFwdArgs& a, int D);
+FlashPlan flash_plan(const AttnBwdArgs& a, int D, long sos, bool want_dbias);
 // ResNet stem BatchNorm + ReLU + 3x3 / s2 / p1 max pool, fused (batchnorm.hip): forward from the conv's epilogue sums
 // (params = fp32 [2][C] scale | shift, idx = winner byte per pooled element); backward into dx of the conv output
 // (params = fp32 [4][C] workspace, work = pool_bn_workspace_floats(C))

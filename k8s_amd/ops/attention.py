@@ -10,11 +10,16 @@ views (e.g. column slices of the fused QKV projection) -- no copies. Head
 dims other than 64/128 and CPU tensors use an explicit matmul/softmax
 reference (no SDPA dispatch, so no Triton-built kernels run).
 
+A call masks at most one thing beyond ``causal`` / ``kv_lens``: ``dropout``, ``doc`` or ``span``. ``_mask_spec`` checks
+the combination once and returns one record (``_Mask``) that the autograd functions carry; whether the flash kernels
+take the call, and which of them run, is one question to the extension (``flash_plan``), and a call they do not take
+runs the reference with the same mask.
+
 ``dropout=(p, DropoutState, site)`` drops attention probabilities with the counter generator of
 ``csrc/kernels/rng.h`` (row = (b * Hq + h) * Sq + q, col = key): fused into the forward and the backward for the
-shapes of ``flash_dropout_fused`` -- head_dim 64 and either the one-block backward's shapes (Sq, Sk <= 128, Hq == Hkv)
-or Sq and Sk multiples of 64 (the multi-tile forward and the three-kernel backward); any other GPU shape runs the
-reference composition with the same mask, counted in ``DROPOUT_FALLBACKS`` and warned about once.
+shapes ``flash_plan`` takes with ``mask="drop"`` -- head_dim 64 and either the one-block backward's shapes (Sq, Sk <=
+128, Hq == Hkv) or Sq and Sk multiples of 64 (the multi-tile forward and the three-kernel backward); any other GPU
+shape runs the reference composition with the same mask, counted in ``DROPOUT_FALLBACKS`` and warned about once.
 
 ``doc=(lo, hi)``: a document-boundary mask inside the causal triangle, for rows that pack several documents. ``lo`` and
 ``hi`` are int32 [B, S]: ``lo[b, i]`` is the row index of the first token of token ``i``'s document and ``hi[b, i]`` one
@@ -35,7 +40,7 @@ from __future__ import annotations
 
 import math
 import warnings
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -60,15 +65,6 @@ def _drop_spec(dropout):
     from k8s_amd.ops import nn as _nn
 
     return _nn._drop_spec(dropout, "attention")
-
-
-def _drop_fused(q, k, v, causal) -> bool:
-    """The fused dropout path takes this call: the flash kernels' operand contract and a ``flash_dropout_fused``
-    shape."""
-    if not _flash_ok(q, k, v):
-        return False
-    B, Sq, Hq, D = q.shape
-    return bool(_load().flash_dropout_fused(D, Sq, k.shape[1], Hq, k.shape[2], causal, B))
 
 
 def _flash_ok(q, k, v) -> bool:
@@ -127,73 +123,88 @@ def span_bounds(starts: torch.Tensor):
         raise ValueError(str(e).replace("doc_starts", "starts")) from None
 
 
-def _span_spec(span, B, Sq, Sk, causal, kv_lens, dropout, doc, who="attention"):
-    """The checked ``(lo, hi)`` of a ``span=`` argument (None when off): non-causal self-attention, nothing else
-    masked."""
-    if span is None:
-        return None
-    if causal:
-        raise ValueError("%s: a span mask is bidirectional and cannot be combined with causal=True" % who)
-    if Sq != Sk:
-        raise ValueError("%s: a span mask is defined for self-attention (Sq == Sk) only" % who)
-    if kv_lens is not None:
-        raise ValueError("%s: a span mask cannot be combined with kv_lens" % who)
-    if dropout is not None:
-        raise ValueError("%s: a span mask cannot be combined with dropout" % who)
+class _Mask(NamedTuple):
+    """What a call masks beyond ``causal`` / ``kv_lens``: at most one kind (the extension's names), its ``(lo, hi)``
+    tables (doc, span) or its dropout spec ``(p, thr, scale, state, site)`` (drop)."""
+    kind: str = "plain"
+    lo: Optional[torch.Tensor] = None
+    hi: Optional[torch.Tensor] = None
+    drop: Optional[tuple] = None
+
+
+def _mask_spec(causal, kv_lens, dropout, doc, span, B, Sq, Sk, who="attention") -> _Mask:
+    """The checked mask of an ``attention`` / ``attention_qkv`` call. Every combination the masks do not have is a
+    ``ValueError`` here: a span mask is non-causal self-attention with nothing else masked, a document mask causal
+    self-attention without ``kv_lens`` or dropout."""
+    qkv = who == "attention_qkv"
+
+    def bad(msg):
+        raise ValueError("%s: %s" % (who, msg))
+
+    def check_span():
+        if span is None:
+            return
+        if causal:
+            bad("a span mask is bidirectional and cannot be combined with causal=True")
+        if Sq != Sk:
+            bad("a span mask is defined for self-attention (Sq == Sk) only")
+        if kv_lens is not None:
+            bad("a span mask cannot be combined with kv_lens")
+        if dropout is not None:
+            bad("a span mask cannot be combined with dropout")
+        if doc is not None:
+            bad("a span mask cannot be combined with a document mask")
+        if not isinstance(span, (tuple, list)) or len(span) != 2 or span[0] is None or span[1] is None:
+            bad("span = (lo, hi) needs both tables")
+        if span[0].dtype != torch.int32 or span[1].dtype != torch.int32:
+            bad("span = (lo, hi) must be int32 tensors (ops.attention.span_bounds)")
+        if tuple(span[0].shape) != (B, Sq) or tuple(span[1].shape) != (B, Sq):
+            bad("span = (lo, hi) must have the shape [B, S] of the queries")
+
+    def check_doc():
+        if doc is None:
+            return
+        if qkv and (not causal or kv_lens is not None or dropout is not None):
+            bad("a document mask needs causal=True and takes neither kv_lens nor dropout")
+        if not causal or Sq != Sk:
+            bad("a document mask is defined for causal self-attention (Sq == Sk) only")
+        if kv_lens is not None or dropout is not None:
+            bad("a document mask cannot be combined with kv_lens or dropout")
+        if any(tuple(t.shape) != (B, Sq) or t.dtype != torch.int32 for t in doc):
+            bad("doc = (lo, hi) must be two int32 [B, S] tensors (ops.attention.doc_bounds)")
+
+    # (the order conflicts are reported in: attention_qkv reads the dropout tuple first and the document mask second)
+    drop = _drop_spec(dropout) if qkv else None
+    for check in (check_doc, check_span) if qkv else (check_span, check_doc):
+        check()
+    if span is not None:
+        return _Mask("span", span[0], span[1])
     if doc is not None:
-        raise ValueError("%s: a span mask cannot be combined with a document mask" % who)
-    if not isinstance(span, (tuple, list)) or len(span) != 2 or span[0] is None or span[1] is None:
-        raise ValueError("%s: span = (lo, hi) needs both tables" % who)
-    lo, hi = span
-    if lo.dtype != torch.int32 or hi.dtype != torch.int32:
-        raise ValueError("%s: span = (lo, hi) must be int32 tensors (ops.attention.span_bounds)" % who)
-    if tuple(lo.shape) != (B, Sq) or tuple(hi.shape) != (B, Sq):
-        raise ValueError("%s: span = (lo, hi) must have the shape [B, S] of the queries" % who)
-    return lo, hi
+        return _Mask("doc", doc[0], doc[1])
+    drop = drop if qkv else _drop_spec(dropout)
+    return _Mask("drop", drop=drop) if drop is not None else _Mask()
 
 
-# keys per tile of the SPAN kernels: None takes the dispatch's default (flash_span_tile), 64 / 128 select a form
+# keys per tile of the SPAN kernels: None takes the plan's default, 64 / 128 select a form
 SPAN_TILE = None
 
 
-def _span_kw(span, device) -> dict:
-    """flash_fwd / flash_bwd keyword arguments of a span mask; none when off."""
-    if span is None:
+def _mask_kw(mask: _Mask, device) -> dict:
+    """flash_fwd / flash_bwd keyword arguments of a mask; none for a plain call."""
+    if mask.kind == "drop":
+        _, thr, scale, state, site = mask.drop
+        return {"drop_state": state.tensor, "drop_thr": thr, "drop_scale": scale, "drop_site": site}
+    if mask.kind == "plain":
         return {}
-    kw = {"span_lo": span[0].to(device).contiguous(), "span_hi": span[1].to(device).contiguous()}
-    if SPAN_TILE is not None:
+    kw = {mask.kind + "_lo": mask.lo.to(device).contiguous(), mask.kind + "_hi": mask.hi.to(device).contiguous()}
+    if mask.kind == "span" and SPAN_TILE is not None:
         kw["span_tile"] = int(SPAN_TILE)
     return kw
 
 
-def _span_flash_ok(q, k, v) -> bool:
-    """The SPAN kernels take this call: the flash contract at head_dim 64 inside their index limits."""
-    if q.shape[-1] != 64 or not _flash_ok(q, k, v):
-        return False
-    B, S, Hq, _ = q.shape
-    return bool(_load().flash_span_ok(64, B, S, k.shape[1], Hq, max(t.stride(1) for t in (q, k, v))))
-
-
-def _doc_spec(doc, q, k, causal, kv_lens, dropout):
-    """The checked ``(lo, hi)`` of a ``doc=`` argument (None when off): causal self-attention, nothing else masked."""
-    if doc is None:
-        return None
-    if not causal or q.shape[1] != k.shape[1]:
-        raise ValueError("attention: a document mask is defined for causal self-attention (Sq == Sk) only")
-    if kv_lens is not None or dropout is not None:
-        raise ValueError("attention: a document mask cannot be combined with kv_lens or dropout")
-    lo, hi = doc
-    shape = (q.shape[0], q.shape[1])
-    if tuple(lo.shape) != shape or tuple(hi.shape) != shape or lo.dtype != torch.int32 or hi.dtype != torch.int32:
-        raise ValueError("attention: doc = (lo, hi) must be two int32 [B, S] tensors (ops.attention.doc_bounds)")
-    return lo, hi
-
-
-def _doc_kw(doc, device) -> dict:
-    """flash_fwd / flash_bwd keyword arguments of a document mask; none when off."""
-    if doc is None:
-        return {}
-    return {"doc_lo": doc[0].to(device).contiguous(), "doc_hi": doc[1].to(device).contiguous()}
+def _plan(kind, D, B, Sq, Sk, Hq, Hkv, causal, has_lens, max_token_stride) -> dict:
+    """The extension's plan for a shape (``flash_plan``): whether the flash kernels take the call, and which run."""
+    return _load().flash_plan(D, B, Sq, Sk, Hq, Hkv, bool(causal), has_lens, kind, 0, max_token_stride)
 
 
 def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None,
@@ -234,29 +245,24 @@ def attention_reference(q, k, v, causal: bool, kv_lens: Optional[torch.Tensor] =
     return o.permute(0, 2, 1, 3).to(q.dtype)
 
 
-def _drop_kw(drop) -> dict:
-    """flash_fwd / flash_bwd keyword arguments of a dropout spec (p, thr, scale, state, site); none when off."""
-    if drop is None:
-        return {}
-    return {"drop_state": drop[3].tensor, "drop_thr": drop[1], "drop_scale": drop[2], "drop_site": drop[4]}
-
-
-def _ref_keep(drop, q, k):
-    if drop is None:
-        return None, 1.0
-    p, _, scale, state, site = drop
-    B, Sq, Hq, _ = q.shape
-    return ref.attention_keep(state.tensor.to(q.device), site, B, Hq, Sq, k.shape[1], p), scale
+def _ref_args(mask: _Mask, q, k) -> tuple:
+    """attention_reference's (keep, keep_scale, doc_lo, span_lo, span_hi) of a mask."""
+    if mask.kind == "drop":
+        p, _, scale, state, site = mask.drop
+        B, Sq, Hq, _ = q.shape
+        return ref.attention_keep(state.tensor.to(q.device), site, B, Hq, Sq, k.shape[1], p), scale, None, None, None
+    span = (mask.lo, mask.hi) if mask.kind == "span" else (None, None)
+    return (None, 1.0, mask.lo if mask.kind == "doc" else None) + span
 
 
 class _Flash(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None, doc=None, span=None):
+    def forward(ctx, q, k, v, causal, kv_lens, scale, mask=_Mask()):
         C = _load()
         if kv_lens is not None:
             kv_lens = kv_lens.to(device=q.device, dtype=torch.int32).contiguous()
-        ctx.drop = dict(_drop_kw(drop), **_doc_kw(doc, q.device), **_span_kw(span, q.device))
-        o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.drop)
+        ctx.mask_kw = _mask_kw(mask, q.device)
+        o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.mask_kw)
         ctx.save_for_backward(q, k, v, o, lse, kv_lens if kv_lens is not None else torch.empty(0))
         ctx.causal, ctx.scale, ctx.has_lens = causal, scale, kv_lens is not None
         return o
@@ -266,52 +272,41 @@ class _Flash(torch.autograd.Function):
         q, k, v, o, lse, lens = ctx.saved_tensors
         C = _load()
         dq, dk, dv = C.flash_bwd(do.contiguous(), q, k, v, o, lse, ctx.causal, lens if ctx.has_lens else None,
-                                 ctx.scale, **ctx.drop)
-        return dq, dk, dv, None, None, None, None, None, None
+                                 ctx.scale, **ctx.mask_kw)
+        return dq, dk, dv, None, None, None, None
 
 
 class _Reference(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal, kv_lens, scale, drop=None, doc=None, span=None):
+    def forward(ctx, q, k, v, causal, kv_lens, scale, mask=_Mask()):
         ctx.save_for_backward(q, k, v)
-        ctx.causal, ctx.kv_lens, ctx.scale, ctx.drop = causal, kv_lens, scale, drop
-        ctx.doc_lo = doc[0] if doc is not None else None
-        ctx.span = span if span is not None else (None, None)
+        ctx.causal, ctx.kv_lens, ctx.scale, ctx.mask = causal, kv_lens, scale, mask
         with torch.no_grad():
-            keep, ks = _ref_keep(drop, q, k)
-            return attention_reference(q, k, v, causal, kv_lens, scale, keep, ks, ctx.doc_lo, *ctx.span)
+            return attention_reference(q, k, v, causal, kv_lens, scale, *_ref_args(mask, q, k))
 
     @staticmethod
     def backward(ctx, do):
         q, k, v = ctx.saved_tensors
         with torch.enable_grad():
             qq, kk, vv = (t.detach().float().requires_grad_(True) for t in (q, k, v))
-            keep, ks = _ref_keep(ctx.drop, q, k)  # the forward's mask again (same seed, step and site)
-            o = attention_reference(qq, kk, vv, ctx.causal, ctx.kv_lens, ctx.scale, keep, ks, ctx.doc_lo, *ctx.span)
+            # (dropout: the forward's mask again -- same seed, step and site)
+            o = attention_reference(qq, kk, vv, ctx.causal, ctx.kv_lens, ctx.scale, *_ref_args(ctx.mask, q, k))
             dq, dk, dv = torch.autograd.grad(o, (qq, kk, vv), do.float())
-        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None, None, None, None
+        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None, None
 
 
 def attention(q, k, v, causal: bool = False, kv_lens: Optional[torch.Tensor] = None, scale: Optional[float] = None,
               dropout: Optional[tuple] = None, doc: Optional[tuple] = None, span: Optional[tuple] = None):
     scale = scale or 1.0 / math.sqrt(q.shape[-1])
-    span = _span_spec(span, q.shape[0], q.shape[1], k.shape[1], causal, kv_lens, dropout, doc)
-    if span is not None:  # the SPAN kernels, or the reference with the same mask: never a call that drops it
-        fn = _Flash if _span_flash_ok(q, k, v) else _Reference
-        return fn.apply(q, k, v, False, None, scale, None, None, span)
-    doc = _doc_spec(doc, q, k, causal, kv_lens, dropout)
-    if doc is not None:  # the DOC kernels, or the reference with the same mask: never a call that drops it
-        return (_Flash if _flash_ok(q, k, v) else _Reference).apply(q, k, v, causal, None, scale, None, doc)
-    drop = _drop_spec(dropout)
-    if drop is not None:
-        if _drop_fused(q, k, v, causal):
-            return _Flash.apply(q, k, v, causal, kv_lens, scale, drop)
-        if q.is_cuda:
-            _dropout_fallback(q, k)
-        return _Reference.apply(q, k, v, causal, kv_lens, scale, drop)
-    if _flash_ok(q, k, v):
-        return _Flash.apply(q, k, v, causal, kv_lens, scale)
-    return _Reference.apply(q, k, v, causal, kv_lens, scale)
+    B, Sq, Hq, D = q.shape
+    mask = _mask_spec(causal, kv_lens, dropout, doc, span, B, Sq, k.shape[1])
+    # the flash kernels, or the reference with the same mask: never a call that drops it
+    if _flash_ok(q, k, v) and _plan(mask.kind, D, B, Sq, k.shape[1], Hq, k.shape[2], causal, kv_lens is not None,
+                                    max(t.stride(1) for t in (q, k, v)))["ok"]:
+        return _Flash.apply(q, k, v, causal, kv_lens, scale, mask)
+    if mask.kind == "drop" and q.is_cuda:
+        _dropout_fallback(q, k)
+    return _Reference.apply(q, k, v, causal, kv_lens, scale, mask)
 
 
 class _FlashQKV(torch.autograd.Function):
@@ -322,7 +317,7 @@ class _FlashQKV(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, qkv, B, S, H, Hkv, D, causal, kv_lens, scale, pos, table, bias_link=None, rope_in_place=False,
-                rope_applied=False, drop=None, doc=None, span=None):
+                rope_applied=False, mask=_Mask()):
         C = _load()
         if kv_lens is not None:
             kv_lens = kv_lens.to(device=qkv.device, dtype=torch.int32).contiguous()
@@ -336,18 +331,18 @@ class _FlashQKV(torch.autograd.Function):
             C.rope_(x[:, : (H + Hkv) * D], pos, table, False)
         g = x.view(B, S, H + 2 * Hkv, D)
         q, k, v = g.narrow(2, 0, H), g.narrow(2, H, Hkv), g.narrow(2, H + Hkv, Hkv)
-        ctx.drop = dict(_drop_kw(drop), **_doc_kw(doc, qkv.device), **_span_kw(span, qkv.device))
-        o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.drop)
+        ctx.mask_kw = _mask_kw(mask, qkv.device)
+        o, lse = C.flash_fwd(q, k, v, causal, kv_lens, scale, **ctx.mask_kw)
         ctx.save_for_backward(x, o, lse, kv_lens if kv_lens is not None else torch.empty(0),
                               pos if pos is not None else torch.empty(0), table if table is not None else torch.empty(0))
-        ctx.meta = (B, S, H, Hkv, D, causal, scale, kv_lens is not None, pos is not None)
+        ctx.meta = (B, S, H, Hkv, D, causal, scale, kv_lens is not None, pos is not None, mask.kind)
         ctx.bias_link = bias_link
         return o
 
     @staticmethod
     def backward(ctx, do):
         x, o, lse, lens, pos, table = ctx.saved_tensors
-        B, S, H, Hkv, D, causal, scale, has_lens, has_rope = ctx.meta
+        B, S, H, Hkv, D, causal, scale, has_lens, has_rope, kind = ctx.meta
         C = _load()
         g = x.view(B, S, H + 2 * Hkv, D)
         q, k, v = g.narrow(2, 0, H), g.narrow(2, H, Hkv), g.narrow(2, H + Hkv, Hkv)
@@ -355,21 +350,20 @@ class _FlashQKV(torch.autograd.Function):
         # the projection's bias gradient (column sums of dqkv) from the one-block kernel (BiasLink); not with rope,
         # which rotates dqkv after the kernel
         bl, dsum, ss, lpb = ctx.bias_link, None, None, None
-        if bl is not None and bl.pb is not None and not has_rope and "doc_lo" not in ctx.drop and \
-                "span_lo" not in ctx.drop and \
-                C.flash_bwd_one_block(D, S, S, H, Hkv, causal, B):  # (a document or span mask has no one-block form)
+        if bl is not None and bl.pb is not None and not has_rope and \
+                _plan(kind, D, B, S, S, H, Hkv, causal, has_lens, x.shape[1])["bwd"]["one_block"]:
             lpb = bl.pb
             ss = lpb.store.slot_for_write(lpb)
             dsum = ss.view(lpb.shape) if ss is not None else torch.empty(lpb.shape, device=x.device,
                                                                          dtype=torch.float32)
         C.flash_bwd(do.contiguous(), q, k, v, o, lse, causal, lens if has_lens else None, scale, dqkv, dsum,
-                    **ctx.drop)
+                    **ctx.mask_kw)
         if dsum is not None:
             lpb.store.mark_written(lpb) if ss is not None else lpb.store.deposit(lpb, dsum)
             bl.done = True
         if has_rope:
             C.rope_(dqkv[:, : (H + Hkv) * D], pos, table, True)
-        return (dqkv,) + (None,) * 16
+        return (dqkv,) + (None,) * 14
 
 
 def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int, causal: bool = False,
@@ -388,8 +382,8 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
     since those would see the rotated values; ``tests/test_attention_gpu.py`` pins in place == copy bitwise.
     ``rope_applied``: q / k already rotated by the projection's epilogue (``ops.nn.linear_rope``); the backward still
     returns the gradient of the UN-rotated projection output (dqkv rotated back), which is what that linear's backward
-    takes. ``dropout`` = (p, DropoutState, site): dropout on the probabilities, fused on the ``flash_dropout_fused``
-    shapes (see the module docstring; the bias gradient stays a one-block feature); other shapes take the split +
+    takes. ``dropout`` = (p, DropoutState, site): dropout on the probabilities, fused on the shapes ``flash_plan``
+    takes (see the module docstring; the bias gradient stays a one-block feature); other shapes take the split +
     ``attention`` composition, which counts the fallback. ``doc`` = (lo, hi): the document mask of ``attention``
     (causal, no ``kv_lens``, no dropout); with ``rope`` the caller passes positions that restart at every document.
     ``span`` = (lo, hi): the span mask of ``attention`` (non-causal, no ``kv_lens``, no dropout, no ``doc``); the SPAN
@@ -397,24 +391,13 @@ def attention_qkv(qkv, B: int, S: int, heads: int, kv_heads: int, head_dim: int,
     D = head_dim
     scale = scale or 1.0 / math.sqrt(D)
     W = (heads + 2 * kv_heads) * D
-    drop = _drop_spec(dropout)
-    if doc is not None:
-        if not causal or kv_lens is not None or dropout is not None:
-            raise ValueError("attention_qkv: a document mask needs causal=True and takes neither kv_lens nor dropout")
-        if any(tuple(t.shape) != (B, S) or t.dtype != torch.int32 for t in doc):
-            raise ValueError("attention_qkv: doc = (lo, hi) must be two int32 [B, S] tensors "
-                             "(ops.attention.doc_bounds)")
+    mask = _mask_spec(causal, kv_lens, dropout, doc, span, B, S, S, "attention_qkv")
     fused = qkv.is_cuda and qkv.dtype == torch.bfloat16 and D in (64, 128) and qkv.shape[-1] == W and \
         W % 8 == 0 and qkv.is_contiguous()
-    if span is not None:
-        span = _span_spec(span, B, S, S, causal, kv_lens, dropout, doc, "attention_qkv")
-        fused = fused and D == 64 and bool(_load().flash_span_ok(64, B, S, S, heads, W))
-    if fused and drop is not None:
-        fused = bool(_load().flash_dropout_fused(D, S, S, heads, kv_heads, causal, B))
-    if fused:
+    if fused and _plan(mask.kind, D, B, S, S, heads, kv_heads, causal, kv_lens is not None, W)["ok"]:
         pos, table = rope if rope is not None else (None, None)
         return _FlashQKV.apply(qkv, B, S, heads, kv_heads, D, causal, kv_lens, scale, pos, table, bias_link,
-                               rope_in_place, rope_applied, drop, doc, span)
+                               rope_in_place, rope_applied, mask)
     if rope_applied:
         raise RuntimeError("attention_qkv: q / k rotated by the projection epilogue need the fused GPU path")
     q, k, v = qkv.split([heads * D, kv_heads * D, kv_heads * D], dim=-1)

@@ -70,6 +70,43 @@ def test_flash_fwd_bwd(cuda, B, S, Hq, Hkv, D, causal, lens):
     _close(vv.grad, torch.nan_to_num(vr.grad), 3e-2, "dV")
 
 
+# Routes of the plan (tests/test_attention_plan.py) that no case above launches, at their smallest shapes. The grid
+# rules are reached by planning for fewer compute units instead of a larger batch.
+@pytest.mark.parametrize("Sq,Sk,causal,cus,route", [
+    (1024, 128, False, 0, dict(fwd=(128, 1), tile=128, qs=1)),   # cross: the forward's tile by Sk, the backward's by Sq
+    (192, 192, False, 2, dict(fwd=(64, 2), tile=64, qs=2)),      # the QS = 2 dQ of a plain call
+    (512, 512, True, 4, dict(fwd=(64, 2), tile=64, dkv_split=1)),  # long causal walk, grid large enough: no dK/dV split
+])
+def test_flash_fwd_bwd_routes(cuda, Sq, Sk, causal, cus, route):
+    from k8s_amd.ops._ext import load
+
+    C = load()
+    B, H, D = 1, 2, 64
+    torch.manual_seed(0)
+    q = torch.randn(B, Sq, H, D, device=cuda).bfloat16()
+    k, v = (torch.randn(B, Sk, H, D, device=cuda).bfloat16() for _ in range(2))
+    scale = 1.0 / math.sqrt(D)
+    qr, kr, vr = (t.detach().float().requires_grad_(True) for t in (q, k, v))
+    ref = attention_reference(qr, kr, vr, causal, None, scale)
+    qq, kk, vv = (t.detach().clone().requires_grad_(True) for t in (q, k, v))
+    do = torch.randn_like(ref).bfloat16()
+    C.set_planner_cus(cus)
+    try:
+        p = C.flash_plan(D, B, Sq, Sk, H, H, causal=causal)
+        assert p["ok"] and not p["bwd"]["one_block"]
+        assert (p["fwd"]["tile"], p["fwd"]["nb"]) == route["fwd"], p
+        assert all(p["bwd"][x] == want for x, want in route.items() if x != "fwd"), p
+        out = _Flash.apply(qq, kk, vv, causal, None, scale)
+        out.backward(do)
+    finally:
+        C.set_planner_cus(0)
+    ref.backward(do.float())
+    _close(out, ref, 2e-2, "O")
+    _close(qq.grad, qr.grad, 3e-2, "dQ")
+    _close(kk.grad, kr.grad, 3e-2, "dK")
+    _close(vv.grad, vr.grad, 3e-2, "dV")
+
+
 def test_flash_lse(cuda):
     from k8s_amd.ops._ext import load
 
