@@ -4,7 +4,7 @@ kernels it feeds, at ResNet-50's real shape (batch 3072, 56x56, C 64 / K 256).
 
 In one process, interleaved per sample, every kernel timed on its own:
 
-    A  dual_apply        bn_bwd_dual_from_sums   read dy, mask, x3, xr; write dx3, dxr       (+ the two finals)
+    A  dual_apply        bn_bwd_dual (sums)      read dy, mask, x3, xr; write dx3, dxr       (+ the two finals)
        conv3_fused       bwd1x1_fused            read dx3, x2; write dz
        down_wgrad        conv_wgrad              read dxr, x
        down_dgrad        gemm_dgrad_bnstats_mask read dxr, addend, winner x, bits; write the addend
@@ -119,17 +119,17 @@ def main(argv=None) -> int:
         fin = dict(addend=addend, winner_x=xw, winner_bits=wbits, winner_mean=wmean)
         none5 = (None,) * 5
 
-        dx3, dxr = C_.bn_bwd_dual_from_sums(dy, mask, x3, *bnK, sumsK, xr, *bnKr, sumsKr)
-        params, params_r = C_.bn_bwd_dual_params(dy, mask, x3, *bnK, sumsK, xr, *bnKr, sumsKr)
+        dx3, dxr = C_.bn_bwd_dual(dy, mask, x3, *bnK, xr, *bnKr, sumsK, sumsKr)
+        params, params_r = C_.bn_bwd_dual_params(dy, mask, x3, *bnK, xr, *bnKr, sumsK, sumsKr)
         wide, narrow, bits = 2 * M * K, 2 * M * C, M * K // 8
         paths = {
-            "dual_apply": (lambda: C_.bn_bwd_dual_from_sums(dy, mask, x3, *bnK, sumsK, xr, *bnKr, sumsKr),
+            "dual_apply": (lambda: C_.bn_bwd_dual(dy, mask, x3, *bnK, xr, *bnKr, sumsK, sumsKr),
                            5 * wide + bits),
             "conv3_fused": (lambda: C_.bwd1x1_fused(dx3, x2, w3, *bn2, dw3, sums2, False), wide + 2 * narrow),
             "down_wgrad": (lambda: C_.conv_wgrad(x, dxr.view(N, H, H, K), dwd, 1, 0, 1, 0, False), wide + narrow),
             "down_dgrad": (lambda: C_.gemm_dgrad_bnstats_mask(dxr, wd, addend, xw, wbits, wmean, sumsp),
                            wide + 3 * narrow + M * C // 8),
-            "dual_params": (lambda: C_.bn_bwd_dual_params(dy, mask, x3, *bnK, sumsK, xr, *bnKr, sumsKr), 0),
+            "dual_params": (lambda: C_.bn_bwd_dual_params(dy, mask, x3, *bnK, xr, *bnKr, sumsK, sumsKr), 0),
             "conv3_onload": (lambda: C_.bwd1x1_fused(dy, x2, w3, *bn2, dw3, sums2, False, x3=x3, mask=mask,
                                                      params=params), 2 * wide + bits + 2 * narrow),
             "down_final_onload": (lambda: C_.bwd1x1_fused(dy, x.view(M, C), wd, *none5, dwd.view(K, C), sumsp, False,

@@ -1,5 +1,5 @@
-// BatchNorm (NHWC): forward / backward with their own reductions, the *_from_sums forms whose statistics come from a
-// convolution's epilogue, the two-BatchNorm (ResNet downsample block) forms and the stem's BN + ReLU + max pool.
+// BatchNorm (NHWC): forward / backward with their own reductions or with `sums` that come from a convolution's
+// epilogue, the two-BatchNorm (ResNet downsample block) forms and the stem's BN + ReLU + max pool.
 #include "binding/common.h"
 
 namespace k8s_amd::binding {
@@ -143,59 +143,71 @@ std::vector<Tensor> bn_relu_maxpool(Tensor x, Tensor sums, Tensor gamma, Tensor 
   return {y, idx, mean, invstd};
 }
 
+// One BatchNorm of a backward (launchers.h BnBwdSide) from its tensors, with the allocations it owns. sums (optional):
+// the reduction was already done by dy's producer (a data gradient's epilogue), leaving the final and apply passes --
+// and no workspace is allocated. pool: the stem's BN + max pool (its own workspace size; sums of exactly
+// conv_stat_replicas). s.dx stays null (a deferred apply pass) until the caller sets it.
+// The callers' channel checks differ and stay as they were: bn_bwd takes any C (bn_channels without mult8),
+// bn_bwd_params and bn_bwd_apply want C % 8 == 0, the two-BatchNorm forms want it only without sums.
+struct BwdSide {
+  k8s_amd::BnBwdSide s;
+  int nrep = 0;
+  Tensor params, work;
+};
+BwdSide bwd_side(const Tensor& x, const Tensor& mean, const Tensor& invstd, const Tensor& gamma, const Tensor& beta,
+                 const Tensor& dgamma, const Tensor& dbeta, const Tensor* sums, const char* sums_name, long M, int C,
+                 bool pool = false) {
+  check_bwd_vectors(mean, invstd, gamma, beta, dgamma, dbeta, C);
+  BwdSide b;
+  if (sums) b.nrep = check_stat_sums(*sums, C, sums_name, pool);
+  b.params = torch::empty({4 * C}, gamma.options());
+  if (!sums)
+    b.work = torch::empty({pool ? k8s_amd::pool_bn_workspace_floats(C) : k8s_amd::bn_workspace_floats(M, C)},
+                          gamma.options());
+  b.s.x = cbf(x);
+  b.s.mean = f32(mean); b.s.invstd = f32(invstd); b.s.gamma = f32(gamma); b.s.beta = f32(beta);
+  b.s.dgamma = f32(dgamma); b.s.dbeta = f32(dbeta);
+  b.s.sums = sums ? f32(*sums) : nullptr;
+  b.s.work = sums ? nullptr : f32(b.work);
+  b.s.params = f32(b.params);
+  return b;
+}
+const Tensor* opt_ptr(const OptTensor& t) { return t && t->defined() ? &*t : nullptr; }
+
 // Backward of bn_relu_maxpool: dx of the conv output x [N, H, W, C] from dpool / idx [N, ceil(H/2), ceil(W/2), C];
 // dgamma / dbeta written into the given fp32 tensors. sums (optional): the BatchNorm-backward sums already taken
 // (fp32 [conv_stat_replicas, 2, C] over g = bit ? dpool : 0 at the winners' x, by the data gradients into the pooled
 // output): the final and apply passes only.
-Tensor pool_bn_bwd_impl(const Tensor& dpool, const Tensor& idx, const Tensor& x, const Tensor& mean,
-                        const Tensor& invstd, const Tensor& gamma, const Tensor& beta, const Tensor& dgamma,
-                        const Tensor& dbeta, const Tensor* sums) {
+Tensor pool_bn_bwd(Tensor dpool, Tensor idx, Tensor x, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta,
+                   Tensor dgamma, Tensor dbeta, OptTensor sums) {
   check_bf16_dense(x, 4, "x");
   check_bf16_dense(dpool, 4, "dpool");
   check_cuda(idx, "idx"); check_dtype(idx, at::kByte, "idx");
   const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   TORCH_CHECK(dpool.sizes() == idx.sizes() && dpool.size(0) == N && dpool.size(1) == (H + 1) / 2 &&
                   dpool.size(2) == (W + 1) / 2 && dpool.size(3) == C, "dpool / idx shape mismatch");
-  check_bwd_vectors(mean, invstd, gamma, beta, dgamma, dbeta, C);
-  const int nrep = sums ? check_stat_sums(*sums, C, "sums", true) : 0;
+  BwdSide a = bwd_side(x, mean, invstd, gamma, beta, dgamma, dbeta, opt_ptr(sums), "sums", 0, C, true);
   auto dx = torch::empty_like(x);
-  auto params = torch::empty({4 * C}, gamma.options());
-  if (sums) {
-    launch_pool_bn_bwd_from_sums(cbf(dpool), idx.data_ptr<uint8_t>(), cbf(x), f32(mean), f32(invstd), f32(gamma),
-                                 f32(beta), bf(dx), f32(dgamma), f32(dbeta), f32(*sums), nrep, f32(params), N, H, W, C,
-                                 cur_stream());
-    return dx;
-  }
-  auto work = torch::empty({k8s_amd::pool_bn_workspace_floats(C)}, gamma.options());
-  launch_pool_bn_bwd(cbf(dpool), idx.data_ptr<uint8_t>(), cbf(x), f32(mean), f32(invstd), f32(gamma), f32(beta), bf(dx),
-                     f32(dgamma), f32(dbeta), f32(work), f32(params), N, H, W, C, cur_stream());
+  a.s.dx = bf(dx);
+  launch_pool_bn_bwd(cbf(dpool), idx.data_ptr<uint8_t>(), a.nrep, a.s, N, H, W, C, cur_stream());
   return dx;
-}
-Tensor pool_bn_bwd_from_sums(Tensor dpool, Tensor idx, Tensor x, Tensor mean, Tensor invstd, Tensor gamma,
-                             Tensor beta, Tensor dgamma, Tensor dbeta, Tensor sums) {
-  return pool_bn_bwd_impl(dpool, idx, x, mean, invstd, gamma, beta, dgamma, dbeta, &sums);
-}
-Tensor pool_bn_bwd(Tensor dpool, Tensor idx, Tensor x, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta,
-                   Tensor dgamma, Tensor dbeta) {
-  return pool_bn_bwd_impl(dpool, idx, x, mean, invstd, gamma, beta, dgamma, dbeta, nullptr);
 }
 
 // (dx, dres or empty); writes dgamma / dbeta into the given (flat-bucket view) tensors. The ReLU of the forward comes
 // from the packed `mask` (residual BN), is recomputed from x (`relu_x`), or -- given the BN output `y` -- is packed
-// from y first (compatibility; the trainer passes the mask). sums (optional, with the mask or relu_x): the reduction
-// was already done by dy's producer (a data gradient's epilogue), leaving the final and apply passes.
-std::vector<Tensor> bn_bwd_impl(const Tensor& dy, const Tensor& x, const OptTensor& y, const Tensor& mean,
-                                const Tensor& invstd, const Tensor& gamma, const Tensor& beta, bool relu_x,
-                                const Tensor& dgamma, const Tensor& dbeta, bool want_dres, const OptTensor& mask,
-                                const Tensor* sums) {
+// from y first (compatibility; the trainer passes the mask). sums (optional, with the mask or relu_x, not with y).
+std::vector<Tensor> bn_bwd(Tensor dy, Tensor x, OptTensor y, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta,
+                           bool relu_x, Tensor dgamma, Tensor dbeta, bool want_dres, OptTensor mask, OptTensor sums) {
   const int C = bn_channels(x, "x", false);
   const long M = x.numel() / C;
   check_same_shape(dy, x, "dy");
-  check_bwd_vectors(mean, invstd, gamma, beta, dgamma, dbeta, C);
   const bool has_mask = mask && mask->defined();
   TORCH_CHECK(!(relu_x && (y || has_mask)) && !(y && has_mask), "relu_x, y and the packed mask are exclusive");
+  const Tensor* pre = opt_ptr(sums);
+  TORCH_CHECK(!pre || has_mask || relu_x, "sums: with the packed mask or relu_x");
+  TORCH_CHECK(!pre || !want_dres || has_mask, "sums with relu_x: no dres");
   const uint8_t* mk = has_mask ? check_bit_mask(*mask, x.numel(), "mask") : nullptr;
-  const int nrep = sums ? check_stat_sums(*sums, C, "sums", false) : 0;
+  BwdSide a = bwd_side(x, mean, invstd, gamma, beta, dgamma, dbeta, pre, "sums", M, C);
   Tensor ymask;
   if (y) {
     check_same_shape(*y, x, "y");
@@ -206,56 +218,25 @@ std::vector<Tensor> bn_bwd_impl(const Tensor& dy, const Tensor& x, const OptTens
   }
   auto dx = torch::empty_like(x);
   Tensor dres = want_dres ? torch::empty_like(x) : Tensor();
-  uint16_t* dr = want_dres ? bf(dres) : nullptr;
-  auto params = torch::empty({4 * C}, gamma.options());
-  if (sums && mk) {
-    launch_bn_bwd_from_sums(cbf(dy), cbf(x), mk, f32(*sums), nrep, f32(mean), f32(invstd), f32(gamma), f32(beta),
-                            bf(dx), dr, f32(dgamma), f32(dbeta), f32(params), M, C, cur_stream());
-  } else if (sums) {
-    launch_bn_bwd_relu_from_sums(cbf(dy), cbf(x), f32(*sums), nrep, f32(mean), f32(invstd), f32(gamma), f32(beta),
-                                 bf(dx), f32(dgamma), f32(dbeta), f32(params), M, C, cur_stream());
-  } else {
-    auto work = torch::empty({k8s_amd::bn_workspace_floats(M, C)}, gamma.options());
-    launch_bn_bwd(cbf(dy), cbf(x), f32(mean), f32(invstd), f32(gamma), f32(beta), relu_x, bf(dx), dr, f32(dgamma),
-                  f32(dbeta), f32(work), f32(params), M, C, cur_stream(), mk);
-  }
+  a.s.dx = bf(dx);
+  launch_bn_bwd_params(cbf(dy), mk, relu_x, a.nrep, a.s, nullptr, M, C, cur_stream());
+  launch_bn_bwd_apply(cbf(dy), mk, relu_x, a.s, nullptr, want_dres ? bf(dres) : nullptr, M, C, cur_stream());
   return {dx, dres};
 }
-std::vector<Tensor> bn_bwd(Tensor dy, Tensor x, OptTensor y, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta,
-                           bool relu_x, Tensor dgamma, Tensor dbeta, bool want_dres, OptTensor mask) {
-  return bn_bwd_impl(dy, x, y, mean, invstd, gamma, beta, relu_x, dgamma, dbeta, want_dres, mask, nullptr);
-}
-// bn_bwd (relu_x: the ReLU recomputed from x) with the reduction done by dy's producer; returns (dx,)
-std::vector<Tensor> bn_bwd_relu_from_sums(Tensor dy, Tensor x, Tensor sums, Tensor mean, Tensor invstd, Tensor gamma,
-                                          Tensor beta, Tensor dgamma, Tensor dbeta) {
-  return {bn_bwd_impl(dy, x, {}, mean, invstd, gamma, beta, true, dgamma, dbeta, false, {}, &sums)[0]};
-}
-// bn_bwd (packed mask) with the reduction done by dy's producer (dgrad_short_bnstats sums); returns (dx, dres)
-std::vector<Tensor> bn_bwd_from_sums(Tensor dy, Tensor x, Tensor mask, Tensor sums, Tensor mean, Tensor invstd,
-                                     Tensor gamma, Tensor beta, Tensor dgamma, Tensor dbeta, bool want_dres) {
-  return bn_bwd_impl(dy, x, {}, mean, invstd, gamma, beta, false, dgamma, dbeta, want_dres, mask, &sums);
-}
 
-// The two halves of bn_bwd / bn_bwd_from_sums for a residual BatchNorm (packed mask), for a consumer of dx that applies
-// the backward as it loads (bwd1x1_fused with x3 / mask / params). bn_bwd_params: dgamma, dbeta and the params table
-// fp32 [sc | B | D | shift] -- from the producer's sums, or from its own reduce sweep without them. bn_bwd_apply: dx
-// from that table, the bits bn_bwd / bn_bwd_from_sums write.
+// The two halves of bn_bwd for a residual BatchNorm (packed mask), for a consumer of dx that applies the backward as it
+// loads (bwd1x1_fused with x3 / mask / params). bn_bwd_params: dgamma, dbeta and the params table fp32 [sc | B | D |
+// shift] -- from the producer's sums, or from its own reduce sweep without them. bn_bwd_apply: dx from that table, the
+// bits bn_bwd writes.
 Tensor bn_bwd_params(Tensor dy, Tensor x, Tensor mask, OptTensor sums, Tensor mean, Tensor invstd, Tensor gamma,
                      Tensor beta, Tensor dgamma, Tensor dbeta) {
   const int C = bn_channels(x, "x", true);
   const long M = x.numel() / C;
   check_same_shape(dy, x, "dy");
-  check_bwd_vectors(mean, invstd, gamma, beta, dgamma, dbeta, C);
   const uint8_t* mk = check_bit_mask(mask, x.numel(), "mask");
-  const bool pre = sums && sums->defined();
-  const int nrep = pre ? check_stat_sums(*sums, C, "sums", false) : 0;
-  auto params = torch::empty({4 * C}, gamma.options());
-  Tensor work;
-  if (!pre) work = torch::empty({k8s_amd::bn_workspace_floats(M, C)}, gamma.options());
-  launch_bn_bwd_params(cbf(dy), cbf(x), mk, pre ? f32(*sums) : nullptr, nrep, f32(mean), f32(invstd), f32(gamma),
-                       f32(beta), false, f32(dgamma), f32(dbeta), pre ? nullptr : f32(work), f32(params), M, C,
-                       cur_stream());
-  return params;
+  BwdSide a = bwd_side(x, mean, invstd, gamma, beta, dgamma, dbeta, opt_ptr(sums), "sums", M, C);
+  launch_bn_bwd_params(cbf(dy), mk, false, a.nrep, a.s, nullptr, M, C, cur_stream());
+  return a.params;
 }
 Tensor bn_bwd_apply(Tensor dy, Tensor x, Tensor mask, Tensor params) {
   const int C = bn_channels(x, "x", true);
@@ -264,87 +245,56 @@ Tensor bn_bwd_apply(Tensor dy, Tensor x, Tensor mask, Tensor params) {
   check_channel_f32(params, 4L * C, "params");
   TORCH_CHECK(params.device() == x.device(), "params: on x's device");
   auto dx = torch::empty_like(x);
-  launch_bn_bwd_apply_pass(cbf(dy), cbf(x), mk, f32(params), false, bf(dx), nullptr, x.numel() / C, C, cur_stream());
+  k8s_amd::BnBwdSide a;
+  a.x = cbf(x);
+  a.params = f32(params);
+  a.dx = bf(dx);
+  launch_bn_bwd_apply(cbf(dy), mk, false, a, nullptr, nullptr, x.numel() / C, C, cur_stream());
   return dx;
 }
 
-// Backward of bn_fwd_from_sums_dual: (dx, dx2) and both BatchNorms' dgamma / dbeta from one masked dy (dy and the
-// packed ReLU mask read once per pass). sums / sums2 (optional, together): the reduction done by dy's producer,
-// sums (sum g, sum g (x - mean)) and sums2 (slot 1: sum g (x2 - mean2)).
-std::vector<Tensor> bn_bwd_dual_impl(const Tensor& dy, const Tensor& mask, const Tensor& x, const Tensor& mean,
-                                     const Tensor& invstd, const Tensor& gamma, const Tensor& beta,
-                                     const Tensor& dgamma, const Tensor& dbeta, const Tensor* sums, const Tensor& x2,
-                                     const Tensor& mean2, const Tensor& invstd2, const Tensor& gamma2,
-                                     const Tensor& beta2, const Tensor& dgamma2, const Tensor& dbeta2,
-                                     const Tensor* sums2) {
-  const int C = bn_channels(x, "x", !sums);
-  const long M = x.numel() / C;
-  check_same_shape(dy, x, "dy");
-  check_same_shape(x2, x, "x2");
-  check_bwd_vectors(mean, invstd, gamma, beta, dgamma, dbeta, C);
-  check_bwd_vectors(mean2, invstd2, gamma2, beta2, dgamma2, dbeta2, C);
-  const uint8_t* mk = check_bit_mask(mask, x.numel(), "mask");
-  const int nrep = sums ? check_stat_sums(*sums, C, "sums", false) : 0;
-  TORCH_CHECK(!sums || check_stat_sums(*sums2, C, "sums2", false) == nrep, "sums / sums2: the same replica count");
-  auto dx = torch::empty_like(x), dx2 = torch::empty_like(x);
-  auto params = torch::empty({4 * C}, gamma.options()), params2 = torch::empty({4 * C}, gamma.options());
-  if (sums) {
-    launch_bn_bwd_dual_from_sums(cbf(dy), mk, cbf(x), f32(*sums), nrep, f32(mean), f32(invstd), f32(gamma), f32(beta),
-                                 bf(dx), f32(dgamma), f32(dbeta), f32(params), cbf(x2), f32(*sums2), f32(mean2),
-                                 f32(invstd2), f32(gamma2), f32(beta2), bf(dx2), f32(dgamma2), f32(dbeta2),
-                                 f32(params2), M, C, cur_stream());
-    return {dx, dx2};
-  }
-  auto work = torch::empty({k8s_amd::bn_workspace_floats(M, C)}, gamma.options());
-  auto work2 = torch::empty({k8s_amd::bn_workspace_floats(M, C)}, gamma.options());
-  launch_bn_bwd_dual(cbf(dy), mk, cbf(x), f32(mean), f32(invstd), f32(gamma), f32(beta), bf(dx), f32(dgamma),
-                     f32(dbeta), f32(work), f32(params), cbf(x2), f32(mean2), f32(invstd2), f32(gamma2), f32(beta2),
-                     bf(dx2), f32(dgamma2), f32(dbeta2), f32(work2), f32(params2), M, C, cur_stream());
-  return {dx, dx2};
-}
-// The first half of bn_bwd_dual / bn_bwd_dual_from_sums: dgamma / dbeta of both BatchNorms and the two params tables
-// fp32 [sc | B | D | shift], (params, params2). sums / sums2 (optional, together): the producer's reduction; without
-// them the dual reduce sweep runs here. bn_bwd_apply(dy, x, mask, params) and bn_bwd_apply(dy, x2, mask, params2) then
-// give the dx and dx2 bn_bwd_dual writes, bit for bit -- or a consumer applies a table on load (bwd1x1_fused).
-std::vector<Tensor> bn_bwd_dual_params(Tensor dy, Tensor mask, Tensor x, Tensor mean, Tensor invstd, Tensor gamma,
-                                       Tensor beta, Tensor dgamma, Tensor dbeta, OptTensor sums, Tensor x2,
-                                       Tensor mean2, Tensor invstd2, Tensor gamma2, Tensor beta2, Tensor dgamma2,
-                                       Tensor dbeta2, OptTensor sums2) {
-  const bool pre = sums && sums->defined();
-  TORCH_CHECK(pre == (sums2 && sums2->defined()), "sums and sums2 come together");
+// Backward of bn_fwd_from_sums_dual: both BatchNorms' dgamma / dbeta and params tables from one masked dy (dy and the
+// packed ReLU mask read once per pass). sums / sums2 (optional, together): the reduction done by dy's producer, sums
+// (sum g, sum g (x - mean)) and sums2 (slot 1: sum g (x2 - mean2)); without them the dual reduce sweep runs here.
+// want_dx: also the apply pass, (dx, dx2); else (params, params2), each [sc | B | D | shift], for
+// bn_bwd_apply(dy, x or x2, mask, ...) -- the same bits -- or a consumer that applies a table on load (bwd1x1_fused).
+std::vector<Tensor> bn_bwd_dual_impl(bool want_dx, const Tensor& dy, const Tensor& mask, const Tensor& x,
+                                     const Tensor& mean, const Tensor& invstd, const Tensor& gamma, const Tensor& beta,
+                                     const Tensor& dgamma, const Tensor& dbeta, const Tensor& x2, const Tensor& mean2,
+                                     const Tensor& invstd2, const Tensor& gamma2, const Tensor& beta2,
+                                     const Tensor& dgamma2, const Tensor& dbeta2, const OptTensor& sums,
+                                     const OptTensor& sums2) {
+  const Tensor *pre = opt_ptr(sums), *pre2 = opt_ptr(sums2);
+  TORCH_CHECK(!pre == !pre2, "sums and sums2 come together");
   const int C = bn_channels(x, "x", !pre);
   const long M = x.numel() / C;
   check_same_shape(dy, x, "dy");
   check_same_shape(x2, x, "x2");
-  check_bwd_vectors(mean, invstd, gamma, beta, dgamma, dbeta, C);
-  check_bwd_vectors(mean2, invstd2, gamma2, beta2, dgamma2, dbeta2, C);
   const uint8_t* mk = check_bit_mask(mask, x.numel(), "mask");
-  const int nrep = pre ? check_stat_sums(*sums, C, "sums", false) : 0;
-  TORCH_CHECK(!pre || check_stat_sums(*sums2, C, "sums2", false) == nrep, "sums / sums2: the same replica count");
-  auto params = torch::empty({4 * C}, gamma.options()), params2 = torch::empty({4 * C}, gamma.options());
-  Tensor work, work2;
-  if (!pre) {
-    work = torch::empty({k8s_amd::bn_workspace_floats(M, C)}, gamma.options());
-    work2 = torch::empty({k8s_amd::bn_workspace_floats(M, C)}, gamma.options());
-  }
-  launch_bn_bwd_dual_params(cbf(dy), mk, cbf(x), pre ? f32(*sums) : nullptr, nrep, f32(mean), f32(invstd), f32(gamma),
-                            f32(beta), f32(dgamma), f32(dbeta), pre ? nullptr : f32(work), f32(params), cbf(x2),
-                            pre ? f32(*sums2) : nullptr, f32(mean2), f32(invstd2), f32(gamma2), f32(beta2),
-                            f32(dgamma2), f32(dbeta2), pre ? nullptr : f32(work2), f32(params2), M, C, cur_stream());
-  return {params, params2};
+  BwdSide a = bwd_side(x, mean, invstd, gamma, beta, dgamma, dbeta, pre, "sums", M, C);
+  BwdSide b = bwd_side(x2, mean2, invstd2, gamma2, beta2, dgamma2, dbeta2, pre2, "sums2", M, C);
+  TORCH_CHECK(a.nrep == b.nrep, "sums / sums2: the same replica count");
+  launch_bn_bwd_params(cbf(dy), mk, false, a.nrep, a.s, &b.s, M, C, cur_stream());
+  if (!want_dx) return {a.params, b.params};
+  auto dx = torch::empty_like(x), dx2 = torch::empty_like(x);
+  a.s.dx = bf(dx);
+  b.s.dx = bf(dx2);
+  launch_bn_bwd_apply(cbf(dy), mk, false, a.s, &b.s, nullptr, M, C, cur_stream());
+  return {dx, dx2};
 }
 std::vector<Tensor> bn_bwd_dual(Tensor dy, Tensor mask, Tensor x, Tensor mean, Tensor invstd, Tensor gamma,
                                 Tensor beta, Tensor dgamma, Tensor dbeta, Tensor x2, Tensor mean2, Tensor invstd2,
-                                Tensor gamma2, Tensor beta2, Tensor dgamma2, Tensor dbeta2) {
-  return bn_bwd_dual_impl(dy, mask, x, mean, invstd, gamma, beta, dgamma, dbeta, nullptr, x2, mean2, invstd2, gamma2,
-                          beta2, dgamma2, dbeta2, nullptr);
+                                Tensor gamma2, Tensor beta2, Tensor dgamma2, Tensor dbeta2, OptTensor sums,
+                                OptTensor sums2) {
+  return bn_bwd_dual_impl(true, dy, mask, x, mean, invstd, gamma, beta, dgamma, dbeta, x2, mean2, invstd2, gamma2,
+                          beta2, dgamma2, dbeta2, sums, sums2);
 }
-std::vector<Tensor> bn_bwd_dual_from_sums(Tensor dy, Tensor mask, Tensor x, Tensor mean, Tensor invstd, Tensor gamma,
-                                          Tensor beta, Tensor dgamma, Tensor dbeta, Tensor sums, Tensor x2,
-                                          Tensor mean2, Tensor invstd2, Tensor gamma2, Tensor beta2, Tensor dgamma2,
-                                          Tensor dbeta2, Tensor sums2) {
-  return bn_bwd_dual_impl(dy, mask, x, mean, invstd, gamma, beta, dgamma, dbeta, &sums, x2, mean2, invstd2, gamma2,
-                          beta2, dgamma2, dbeta2, &sums2);
+std::vector<Tensor> bn_bwd_dual_params(Tensor dy, Tensor mask, Tensor x, Tensor mean, Tensor invstd, Tensor gamma,
+                                       Tensor beta, Tensor dgamma, Tensor dbeta, Tensor x2, Tensor mean2,
+                                       Tensor invstd2, Tensor gamma2, Tensor beta2, Tensor dgamma2, Tensor dbeta2,
+                                       OptTensor sums, OptTensor sums2) {
+  return bn_bwd_dual_impl(false, dy, mask, x, mean, invstd, gamma, beta, dgamma, dbeta, x2, mean2, invstd2, gamma2,
+                          beta2, dgamma2, dbeta2, sums, sums2);
 }
 
 }  // namespace
@@ -353,29 +303,29 @@ void bind_batchnorm(pybind11::module_& m) {
   m.def("bn_fwd", &bn_fwd, "x"_a, "res"_a, "gamma"_a, "beta"_a, "run_mean"_a, "run_var"_a, "training"_a, "momentum"_a,
         "eps"_a, "relu"_a, "want_mask"_a = false);
   m.def("bn_bwd", &bn_bwd, "dy"_a, "x"_a, "y"_a, "mean"_a, "invstd"_a, "gamma"_a, "beta"_a, "relu_x"_a, "dgamma"_a,
-        "dbeta"_a, "want_dres"_a, "mask"_a = py::none());
+        "dbeta"_a, "want_dres"_a, "mask"_a = py::none(), "sums"_a = py::none());
   m.def("bn_fwd_from_sums", &bn_fwd_from_sums, "x"_a, "res"_a, "gamma"_a, "beta"_a, "sums"_a, "run_mean"_a, "run_var"_a,
         "momentum"_a, "eps"_a, "relu"_a, "want_mask"_a = false, "want_sub2"_a = false);
-  m.def("bn_bwd_dual", &bn_bwd_dual, "both BatchNorm backwards of bn_fwd_from_sums_dual from one masked dy");
   m.def("bn_fwd_from_sums_dual", &bn_fwd_from_sums_dual, "relu(BN(x) + BN_r(xr)), statistics from conv sums");
   m.def("bn_finalize", &bn_finalize, "sums"_a, "gamma"_a, "beta"_a, "run_mean"_a, "run_var"_a, "count"_a, "momentum"_a,
         "eps"_a);
-  m.def("bn_bwd_relu_from_sums", &bn_bwd_relu_from_sums, "relu_x BatchNorm backward from a producer's sums");
-  m.def("bn_bwd_from_sums", &bn_bwd_from_sums, "BatchNorm backward from a producer's reduction sums (final + apply)");
   m.def("bn_bwd_params", &bn_bwd_params, "dy"_a, "x"_a, "mask"_a, "sums"_a, "mean"_a, "invstd"_a, "gamma"_a, "beta"_a,
         "dgamma"_a, "dbeta"_a, "first half of a masked BatchNorm backward: dgamma, dbeta, params [sc | B | D | shift]");
   m.def("bn_bwd_apply", &bn_bwd_apply, "dy"_a, "x"_a, "mask"_a, "params"_a,
         "second half of a masked BatchNorm backward: dx from bn_bwd_params' table");
-  m.def("bn_bwd_dual_from_sums", &bn_bwd_dual_from_sums, "bn_bwd_dual from a producer's reduction sums");
-  m.def("bn_bwd_dual_params", &bn_bwd_dual_params, "dy"_a, "mask"_a, "x"_a, "mean"_a, "invstd"_a, "gamma"_a, "beta"_a,
-        "dgamma"_a, "dbeta"_a, "sums"_a, "x2"_a, "mean2"_a, "invstd2"_a, "gamma2"_a, "beta2"_a, "dgamma2"_a,
-        "dbeta2"_a, "sums2"_a,
-        "first half of bn_bwd_dual(_from_sums): both dgamma / dbeta and (params, params2), each [sc | B | D | shift]");
+  auto def_dual = [&m](const char* name, auto fn, const char* doc) {
+    m.def(name, fn, "dy"_a, "mask"_a, "x"_a, "mean"_a, "invstd"_a, "gamma"_a, "beta"_a, "dgamma"_a, "dbeta"_a, "x2"_a,
+          "mean2"_a, "invstd2"_a, "gamma2"_a, "beta2"_a, "dgamma2"_a, "dbeta2"_a, "sums"_a = py::none(),
+          "sums2"_a = py::none(), doc);
+  };
+  def_dual("bn_bwd_dual", &bn_bwd_dual,
+           "both BatchNorm backwards of bn_fwd_from_sums_dual from one masked dy: (dx, dx2)");
+  def_dual("bn_bwd_dual_params", &bn_bwd_dual_params,
+           "first half of bn_bwd_dual: both dgamma / dbeta and (params, params2), each [sc | B | D | shift]");
   m.def("bn_relu_maxpool", &bn_relu_maxpool, "x"_a, "sums"_a, "gamma"_a, "beta"_a, "run_mean"_a, "run_var"_a,
         "momentum"_a, "eps"_a, "want_link"_a = false);
-  m.def("pool_bn_bwd_from_sums", &pool_bn_bwd_from_sums);
   m.def("pool_bn_bwd", &pool_bn_bwd, "dpool"_a, "idx"_a, "x"_a, "mean"_a, "invstd"_a, "gamma"_a, "beta"_a, "dgamma"_a,
-        "dbeta"_a);
+        "dbeta"_a, "sums"_a = py::none());
 }
 
 }  // namespace k8s_amd::binding

@@ -242,7 +242,7 @@ __device__ __forceinline__ void load_f8(const float* p, float (&o)[8]) {
   o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
 }
 
-// Block -> 4-KB chunk order of the flat passes (see stream_order_mode below). rev 0: address order. rev 1 / 2: the tensor as
+// Block -> 4-KB chunk order of the flat passes (see kOrderFwdApply below). rev 0: address order. rev 1 / 2: the tensor as
 // 8 contiguous bands swept concurrently (consecutive blocks in different bands), each descending (1) or ascending
 // (2) -- the shape in which the XCD-remapped GEMMs write their outputs (8 row bands in parallel, ascending); rev 3:
 // plain descending address order.
@@ -830,8 +830,10 @@ __global__ void __launch_bounds__(BN_THREADS) pool_bn_bwd_apply_kernel(
 // 12.61-12.64k with these fixed BatchNorm directions (forward apply descending behind its ascending conv, backward
 // reduce descending behind its dgrad, backward apply ascending behind the reduce), 12.51-12.53k when every streaming
 // launch, the GEMMs included, alternated direction (the GEMMs' reversed tile order costs more than the reuse buys).
-int stream_order_mode() { return 1; }
-int stream_dir(int fixed) { return fixed; }
+// The codes the kernels take: bn_block_order's `rev` for the flat passes, bn_bwd_reduce_kernel's `rev` for the reduce.
+constexpr int kOrderFwdApply = 1;  // 8 bands, each descending
+constexpr int kDirBwdReduce = 1;   // 8 bands, each descending
+constexpr int kOrderBwdApply = 2;  // 8 bands, each ascending
 
 static long bn_rows_per_block(long M, const BnGeom& g) {
   // ~1024 blocks in total (4 per CU: enough loads in flight to cover HBM latency), at most M / 64 row-blocks,
@@ -852,7 +854,7 @@ static int bn_reduce_blocks(long M, const BnGeom& g) {
   long nb = 4L * planner_cus() / g.grid_y;
   const long groups = (M + g.rows_per_iter - 1) / g.rows_per_iter;
   if (nb > groups) nb = groups;
-  if (stream_order_mode()) nb = nb < 8 ? 8 : nb & ~7L;  // banded order: a multiple of 8 blocks (one band each)
+  nb = nb < 8 ? 8 : nb & ~7L;  // banded order: a multiple of 8 blocks (one band each)
   return (int)(nb < 1 ? 1 : nb);
 }
 
@@ -871,8 +873,8 @@ static void launch_bn_apply(const uint16_t* x, const uint16_t* res, const float*
   if (nvec >= (1L << 31)) throw std::runtime_error("BatchNorm tensor too large (>= 2^31 vectors)");
   if (ysub && (M % ((long)H * W) != 0)) throw std::runtime_error("bn_apply subsample: M must be N * H * W");
   hipLaunchKernelGGL(bn_apply_kernel, dim3(cdiv(nvec, BN_THREADS)), dim3(BN_THREADS), 0, st, x, res, params, rparams,
-                     y, mask, (int)nvec, C, make_fastdiv(C / 8), (int)relu,
-                     stream_order_mode() ? (stream_dir(1) ? 1 : 2) : 0, ysub, make_fastdiv(W), make_fastdiv(H));
+                     y, mask, (int)nvec, C, make_fastdiv(C / 8), (int)relu, kOrderFwdApply, ysub, make_fastdiv(W),
+                     make_fastdiv(H));
 }
 
 void launch_bn_fwd(const uint16_t* x, const uint16_t* res, const float* gamma, const float* beta, uint16_t* y,
@@ -928,137 +930,58 @@ void launch_bn_finalize_sums(const float* gamma, const float* beta, const float*
                      momentum, save_mean, save_invstd, run_mean, run_var, gamma, beta, params);
 }
 
-static void launch_bn_bwd_apply(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* params,
-                                bool relu_x, uint16_t* dx, uint16_t* dres, long M, int C, hipStream_t st,
-                                int order = -1) {
-  const long nvec = M * C / 8;
-  if (nvec >= (1L << 31)) throw std::runtime_error("BatchNorm tensor too large (>= 2^31 vectors)");
-  if (order < 0) order = stream_order_mode() ? (stream_dir(0) ? 1 : 2) : 0;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(cdiv(nvec, BN_THREADS)), dim3(BN_THREADS), 0, st, dy, x, mask, params,
-                     (int)relu_x, dx, dres, (int)nvec, C, make_fastdiv(C / 8), order);
-}
-
-// The first half of a BatchNorm backward: dgamma, dbeta and the params table [sc | B | D | shift] that the apply pass
-// -- launch_bn_bwd_apply_pass, or a consumer of dx that applies it on load (bwd1x1_fused.hip) -- reads. sums: the
-// reduction done by dy's producer ([nrep][2][C]); null: the reduce sweep over dy and x here (work: bn_workspace_floats).
-void launch_bn_bwd_params(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* sums, int nrep,
-                          const float* mean, const float* invstd, const float* gamma, const float* beta, bool relu_x,
-                          float* dgamma, float* dbeta, float* work, float* params, long M, int C, hipStream_t st) {
-  if (sums) {
-    hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums, nrep, C, dgamma,
-                       dbeta, 1.f / (float)M, mean, invstd, gamma, beta, params);
+// The first half of a BatchNorm backward (launchers.h BnBwdSide): dgamma, dbeta and the params table that the apply
+// pass -- launch_bn_bwd_apply, or a consumer of dx that applies it on load (bwd1x1_fused.hip) -- reads.
+void launch_bn_bwd_params(const uint16_t* dy, const uint8_t* mask, bool relu_x, int nrep, const BnBwdSide& a,
+                          const BnBwdSide* b, long M, int C, hipStream_t st) {
+  if (b && (!mask || relu_x || !a.sums != !b->sums))
+    throw std::runtime_error("bn_bwd: two BatchNorms share a packed mask, and their sums come together");
+  const float inv_m = 1.f / (float)M;
+  if (a.sums) {  // sg: the sums whose slot 0 is sum g (the second BatchNorm's slot 0 is not written)
+    auto final_sums = [&](const float* sg, const BnBwdSide& s) {
+      hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sg, s.sums, nrep, C, s.dgamma,
+                         s.dbeta, inv_m, s.mean, s.invstd, s.gamma, s.beta, s.params);
+    };
+    final_sums(a.sums, a);
+    if (b) final_sums(a.sums, *b);
     return;
   }
   BnGeom g = bn_geom(C, M);
   const int nb = bn_reduce_blocks(M, g);
+  const dim3 grid(nb, g.grid_y), block(BN_THREADS);
   // (round 3: the residual-BN reduce in address order, and its apply descending behind it, measured slower than
   // the producer-opposite banded order -- 12.92k vs 13.06k img/s -- and were dropped)
-  const int rdir = stream_dir(1);
-  if (mask)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(nb, g.grid_y), dim3(BN_THREADS), 0, st, dy, x, mean, invstd,
-                       gamma, beta, (int)relu_x, M, C, g.tpr, g.rows_per_iter, work, mask, rdir);
+  if (!b && mask)
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, grid, block, 0, st, dy, a.x, a.mean, a.invstd, a.gamma, a.beta,
+                       (int)relu_x, M, C, g.tpr, g.rows_per_iter, a.work, mask, kDirBwdReduce);
+  else if (!b)
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, grid, block, 0, st, dy, a.x, a.mean, a.invstd, a.gamma, a.beta,
+                       (int)relu_x, M, C, g.tpr, g.rows_per_iter, a.work, mask, kDirBwdReduce);
   else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(nb, g.grid_y), dim3(BN_THREADS), 0, st, dy, x, mean, invstd,
-                       gamma, beta, (int)relu_x, M, C, g.tpr, g.rows_per_iter, work, mask, rdir);
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, FIN_CH)), dim3(256), 0, st, work, nb, C, dgamma, dbeta,
-                     1.f / (float)M, mean, invstd, gamma, beta, params);
+    hipLaunchKernelGGL((bn_bwd_reduce_kernel<true, true>), grid, block, 0, st, dy, a.x, a.mean, a.invstd, a.gamma,
+                       a.beta, 0, M, C, g.tpr, g.rows_per_iter, a.work, mask, kDirBwdReduce, b->x, b->mean, b->invstd,
+                       b->work);
+  for (const BnBwdSide* s : {&a, b})
+    if (s)
+      hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, FIN_CH)), dim3(256), 0, st, s->work, nb, C, s->dgamma,
+                         s->dbeta, inv_m, s->mean, s->invstd, s->gamma, s->beta, s->params);
 }
 
-// The second half: dx (and dres) from dy, x, the mask or relu_x, and launch_bn_bwd_params' table.
-void launch_bn_bwd_apply_pass(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* params,
-                              bool relu_x, uint16_t* dx, uint16_t* dres, long M, int C, hipStream_t st) {
-  launch_bn_bwd_apply(dy, x, mask, params, relu_x, dx, dres, M, C, st);
-}
-
-void launch_bn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const float* invstd, const float* gamma,
-                   const float* beta, bool relu_x, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta,
-                   float* work, float* params, long M, int C, hipStream_t st, const uint8_t* mask) {
-  launch_bn_bwd_params(dy, x, mask, nullptr, 0, mean, invstd, gamma, beta, relu_x, dgamma, dbeta, work, params, M, C,
-                       st);
-  launch_bn_bwd_apply(dy, x, mask, params, relu_x, dx, dres, M, C, st);
-}
-
-// launch_bn_bwd with the reduce done by dy's producer (the sums of bn_bwd_final_sums_kernel): the final and apply
-// passes only. mask: the packed ReLU bits (residual BatchNorm).
-void launch_bn_bwd_from_sums(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* sums, int nrep,
-                             const float* mean, const float* invstd, const float* gamma, const float* beta,
-                             uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta, float* params, long M, int C,
-                             hipStream_t st) {
-  launch_bn_bwd_params(dy, x, mask, sums, nrep, mean, invstd, gamma, beta, false, dgamma, dbeta, nullptr, params, M,
-                       C, st);
-  launch_bn_bwd_apply(dy, x, mask, params, false, dx, dres, M, C, st);
-}
-
-void launch_bn_bwd_relu_from_sums(const uint16_t* dy, const uint16_t* x, const float* sums, int nrep,
-                                  const float* mean, const float* invstd, const float* gamma, const float* beta,
-                                  uint16_t* dx, float* dgamma, float* dbeta, float* params, long M, int C,
-                                  hipStream_t st) {
-  hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums, nrep, C, dgamma,
-                     dbeta, 1.f / (float)M, mean, invstd, gamma, beta, params);
-  launch_bn_bwd_apply(dy, x, nullptr, params, true, dx, nullptr, M, C, st);
-}
-
-// The first half of both BatchNorm backwards of launch_bn_fwd_from_sums_dual: dgamma / dbeta of both and the two
-// params tables [sc | B | D | shift] that the dual apply pass -- or, per half, launch_bn_bwd_apply_pass or a consumer
-// that applies the table on load (bwd1x1_fused.hip) -- reads. sums / sums2: the reduction done by dy's producer (sums:
-// sum g, sum g (x - mean); sums2 slot 1: sum g (x2 - mean2)); both null: one reduce sweep over dy, x and x2 here
-// (work / work2: bn_workspace_floats each).
-void launch_bn_bwd_dual_params(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* sums, int nrep,
-                               const float* mean, const float* invstd, const float* gamma, const float* beta,
-                               float* dgamma, float* dbeta, float* work, float* params, const uint16_t* x2,
-                               const float* sums2, const float* mean2, const float* invstd2, const float* gamma2,
-                               const float* beta2, float* dgamma2, float* dbeta2, float* work2, float* params2, long M,
-                               int C, hipStream_t st) {
-  if (sums) {
-    hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums, nrep, C, dgamma,
-                       dbeta, 1.f / (float)M, mean, invstd, gamma, beta, params);
-    hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums2, nrep, C, dgamma2,
-                       dbeta2, 1.f / (float)M, mean2, invstd2, gamma2, beta2, params2);
-    return;
-  }
-  BnGeom g = bn_geom(C, M);
-  const int nb = bn_reduce_blocks(M, g);
-  const int rdir = stream_dir(1);
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<true, true>), dim3(nb, g.grid_y), dim3(BN_THREADS), 0, st, dy, x, mean,
-                     invstd, gamma, beta, 0, M, C, g.tpr, g.rows_per_iter, work, mask, rdir, x2, mean2, invstd2, work2);
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, FIN_CH)), dim3(256), 0, st, work, nb, C, dgamma, dbeta,
-                     1.f / (float)M, mean, invstd, gamma, beta, params);
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, FIN_CH)), dim3(256), 0, st, work2, nb, C, dgamma2, dbeta2,
-                     1.f / (float)M, mean2, invstd2, gamma2, beta2, params2);
-}
-
-// The second half: both gradients in one pass over dy, the mask, x and x2.
-static void launch_bn_bwd_apply_dual(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* params,
-                                     uint16_t* dx, const uint16_t* x2, const float* params2, uint16_t* dx2, long M,
-                                     int C, hipStream_t st) {
+// The second half: dx (and dres) from dy, x, the mask or relu_x, and launch_bn_bwd_params' table. Two sides: both
+// gradients in one pass over dy, the mask, x and x2.
+void launch_bn_bwd_apply(const uint16_t* dy, const uint8_t* mask, bool relu_x, const BnBwdSide& a, const BnBwdSide* b,
+                         uint16_t* dres, long M, int C, hipStream_t st) {
   const long nvec = M * C / 8;
   if (nvec >= (1L << 31)) throw std::runtime_error("BatchNorm tensor too large (>= 2^31 vectors)");
-  hipLaunchKernelGGL(bn_bwd_apply_dual_kernel, dim3(cdiv(nvec, BN_THREADS)), dim3(BN_THREADS), 0, st, dy, mask, x,
-                     params, dx, x2, params2, dx2, (int)nvec, C, make_fastdiv(C / 8),
-                     stream_order_mode() ? (stream_dir(0) ? 1 : 2) : 0);
-}
-
-void launch_bn_bwd_dual_from_sums(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* sums,
-                                  int nrep, const float* mean, const float* invstd, const float* gamma,
-                                  const float* beta, uint16_t* dx, float* dgamma, float* dbeta, float* params,
-                                  const uint16_t* x2, const float* sums2, const float* mean2, const float* invstd2,
-                                  const float* gamma2, const float* beta2, uint16_t* dx2, float* dgamma2,
-                                  float* dbeta2, float* params2, long M, int C, hipStream_t st) {
-  launch_bn_bwd_dual_params(dy, mask, x, sums, nrep, mean, invstd, gamma, beta, dgamma, dbeta, nullptr, params, x2,
-                            sums2, mean2, invstd2, gamma2, beta2, dgamma2, dbeta2, nullptr, params2, M, C, st);
-  launch_bn_bwd_apply_dual(dy, mask, x, params, dx, x2, params2, dx2, M, C, st);
-}
-
-// Backward of launch_bn_fwd_from_sums_dual: both BatchNorms' (dgamma, dbeta, dx) from one masked dy in one reduce
-// sweep and one apply pass (work / work2: bn_workspace_floats each; params / params2: fp32 [4][C] each).
-void launch_bn_bwd_dual(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* mean,
-                        const float* invstd, const float* gamma, const float* beta, uint16_t* dx, float* dgamma,
-                        float* dbeta, float* work, float* params, const uint16_t* x2, const float* mean2,
-                        const float* invstd2, const float* gamma2, const float* beta2, uint16_t* dx2, float* dgamma2,
-                        float* dbeta2, float* work2, float* params2, long M, int C, hipStream_t st) {
-  launch_bn_bwd_dual_params(dy, mask, x, nullptr, 0, mean, invstd, gamma, beta, dgamma, dbeta, work, params, x2,
-                            nullptr, mean2, invstd2, gamma2, beta2, dgamma2, dbeta2, work2, params2, M, C, st);
-  launch_bn_bwd_apply_dual(dy, mask, x, params, dx, x2, params2, dx2, M, C, st);
+  const dim3 grid(cdiv(nvec, BN_THREADS)), block(BN_THREADS);
+  if (!b) {
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, block, 0, st, dy, a.x, mask, a.params, (int)relu_x, a.dx, dres,
+                       (int)nvec, C, make_fastdiv(C / 8), kOrderBwdApply);
+    return;
+  }
+  if (!mask || relu_x || dres) throw std::runtime_error("bn_bwd: two BatchNorms share a packed mask and have no dres");
+  hipLaunchKernelGGL(bn_bwd_apply_dual_kernel, grid, block, 0, st, dy, mask, a.x, a.params, a.dx, b->x, b->params,
+                     b->dx, (int)nvec, C, make_fastdiv(C / 8), kOrderBwdApply);
 }
 
 // ---- stem BatchNorm + ReLU + 3x3 / s2 / p1 max pool (see bn_relu_maxpool_fwd_kernel)
@@ -1079,42 +1002,31 @@ void launch_bn_relu_maxpool_fwd(const uint16_t* x, const float* gamma, const flo
 
 int pool_bn_workspace_floats(int C) { return 4096 * C * 2; }
 
-void launch_pool_bn_bwd(const uint16_t* dpool, const uint8_t* idx, const uint16_t* x, const float* mean,
-                        const float* invstd, const float* gamma, const float* beta, uint16_t* dx, float* dgamma,
-                        float* dbeta, float* work, float* params, int N, int H, int W, int C, hipStream_t st) {
+// s.sums: taken by the data gradients into the pooled output (the winner's x and ReLU bit per pooled element,
+// bn_relu_maxpool_fwd_kernel's xarg / ybits) -- the final and apply passes only; null: the reduce sweep here
+void launch_pool_bn_bwd(const uint16_t* dpool, const uint8_t* idx, int nrep, const BnBwdSide& s, int N, int H, int W,
+                        int C, hipStream_t st) {
   if (C % 8 || BN_THREADS % (C / 8)) throw std::runtime_error("pool_bn_bwd: C / 8 must divide 256");
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, Hc = (H + 1) / 2, Wc = (W + 1) / 2;
   const long ncells = (long)N * Hc * Wc;
   if (ncells * (C / 8) >= (1L << 31)) throw std::runtime_error("pool_bn_bwd: tensor too large");
-  const int cpb = BN_THREADS / (C / 8);
-  long nb = (ncells + cpb - 1) / cpb;
-  nb = std::min(nb, 16L * planner_cus());  // ~16 blocks per CU: enough loads in flight (a 1024-block grid ran at half the roof)
-  hipLaunchKernelGGL(pool_bn_bwd_reduce_kernel, dim3((unsigned)nb), dim3(BN_THREADS), 0, st, dpool, idx, x, mean,
-                     invstd, gamma, beta, H, W, C, Ho, Wo, Hc, Wc, (int)ncells, work, make_fastdiv(Wc),
-                     make_fastdiv(Hc));
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, FIN_CH)), dim3(256), 0, st, work, (int)nb, C, dgamma, dbeta,
-                     1.f / (float)((long)N * H * W), mean, invstd, gamma, beta, params);
+  const float inv_m = 1.f / (float)((long)N * H * W);
+  if (s.sums) {
+    hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, s.sums, s.sums, nrep, C,
+                       s.dgamma, s.dbeta, inv_m, s.mean, s.invstd, s.gamma, s.beta, s.params);
+  } else {
+    const int cpb = BN_THREADS / (C / 8);
+    // ~16 blocks per CU: enough loads in flight (a 1024-block grid ran at half the roof)
+    const long nb = std::min((ncells + cpb - 1) / cpb, 16L * planner_cus());
+    hipLaunchKernelGGL(pool_bn_bwd_reduce_kernel, dim3((unsigned)nb), dim3(BN_THREADS), 0, st, dpool, idx, s.x, s.mean,
+                       s.invstd, s.gamma, s.beta, H, W, C, Ho, Wo, Hc, Wc, (int)ncells, s.work, make_fastdiv(Wc),
+                       make_fastdiv(Hc));
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3(cdiv(C, FIN_CH)), dim3(256), 0, st, s.work, (int)nb, C, s.dgamma,
+                       s.dbeta, inv_m, s.mean, s.invstd, s.gamma, s.beta, s.params);
+  }
   const long total = ncells * (C / 8);
-  hipLaunchKernelGGL(pool_bn_bwd_apply_kernel, dim3(cdiv(total, BN_THREADS)), dim3(BN_THREADS), 0, st, dpool, idx, x,
-                     params, dx, H, W, C, Ho, Wo, (int)total, make_fastdiv(C / 8), make_fastdiv(Wc),
-                     make_fastdiv(Hc));
-}
-
-// launch_pool_bn_bwd with the sums taken by the data gradients into the pooled output (the winner's x and ReLU bit
-// per pooled element, bn_relu_maxpool_fwd_kernel's xarg / ybits): the final and apply passes only
-void launch_pool_bn_bwd_from_sums(const uint16_t* dpool, const uint8_t* idx, const uint16_t* x, const float* mean,
-                                  const float* invstd, const float* gamma, const float* beta, uint16_t* dx,
-                                  float* dgamma, float* dbeta, const float* sums, int nrep, float* params, int N,
-                                  int H, int W, int C, hipStream_t st) {
-  if (C % 8 || BN_THREADS % (C / 8)) throw std::runtime_error("pool_bn_bwd: C / 8 must divide 256");
-  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, Hc = (H + 1) / 2, Wc = (W + 1) / 2;
-  const long ncells = (long)N * Hc * Wc;
-  if (ncells * (C / 8) >= (1L << 31)) throw std::runtime_error("pool_bn_bwd: tensor too large");
-  hipLaunchKernelGGL(bn_bwd_final_sums_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, sums, sums, nrep, C, dgamma,
-                     dbeta, 1.f / (float)((long)N * H * W), mean, invstd, gamma, beta, params);
-  const long total = ncells * (C / 8);
-  hipLaunchKernelGGL(pool_bn_bwd_apply_kernel, dim3(cdiv(total, BN_THREADS)), dim3(BN_THREADS), 0, st, dpool, idx, x,
-                     params, dx, H, W, C, Ho, Wo, (int)total, make_fastdiv(C / 8), make_fastdiv(Wc),
+  hipLaunchKernelGGL(pool_bn_bwd_apply_kernel, dim3(cdiv(total, BN_THREADS)), dim3(BN_THREADS), 0, st, dpool, idx, s.x,
+                     s.params, s.dx, H, W, C, Ho, Wo, (int)total, make_fastdiv(C / 8), make_fastdiv(Wc),
                      make_fastdiv(Hc));
 }
 

@@ -64,49 +64,29 @@ void launch_bn_fwd_from_sums_dual(const uint16_t* x, const float* gamma, const f
                                   const float* sums_r, int nrep_r, float* save_mean_r, float* save_invstd_r,
                                   float* run_mean_r, float* run_var_r, float* params_r, uint16_t* y, uint8_t* mask,
                                   long M, int C, float eps, float momentum, hipStream_t st);
-void launch_bn_bwd_from_sums(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* sums, int nrep,
-                             const float* mean, const float* invstd, const float* gamma, const float* beta,
-                             uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta, float* params, long M, int C,
-                             hipStream_t st);
-void launch_bn_bwd_relu_from_sums(const uint16_t* dy, const uint16_t* x, const float* sums, int nrep,
-                                  const float* mean, const float* invstd, const float* gamma, const float* beta,
-                                  uint16_t* dx, float* dgamma, float* dbeta, float* params, long M, int C,
-                                  hipStream_t st);
-void launch_bn_bwd_dual_from_sums(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* sums,
-                                  int nrep, const float* mean, const float* invstd, const float* gamma,
-                                  const float* beta, uint16_t* dx, float* dgamma, float* dbeta, float* params,
-                                  const uint16_t* x2, const float* sums2, const float* mean2, const float* invstd2,
-                                  const float* gamma2, const float* beta2, uint16_t* dx2, float* dgamma2,
-                                  float* dbeta2, float* params2, long M, int C, hipStream_t st);
-void launch_bn_bwd_dual(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* mean,
-                        const float* invstd, const float* gamma, const float* beta, uint16_t* dx, float* dgamma,
-                        float* dbeta, float* work, float* params, const uint16_t* x2, const float* mean2,
-                        const float* invstd2, const float* gamma2, const float* beta2, uint16_t* dx2, float* dgamma2,
-                        float* dbeta2, float* work2, float* params2, long M, int C, hipStream_t st);
-// launch_bn_bwd_dual / launch_bn_bwd_dual_from_sums without their apply pass: dgamma / dbeta of both BatchNorms and the
-// two params tables [sc | B | D | shift] (sums and sums2 null: the dual reduce sweep here, work / work2 =
-// bn_workspace_floats each). Each half's table is then applied by launch_bn_bwd_apply_pass(dy, x or x2, mask, ...) or
-// by a consumer on load.
-void launch_bn_bwd_dual_params(const uint16_t* dy, const uint8_t* mask, const uint16_t* x, const float* sums, int nrep,
-                               const float* mean, const float* invstd, const float* gamma, const float* beta,
-                               float* dgamma, float* dbeta, float* work, float* params, const uint16_t* x2,
-                               const float* sums2, const float* mean2, const float* invstd2, const float* gamma2,
-                               const float* beta2, float* dgamma2, float* dbeta2, float* work2, float* params2, long M,
-                               int C, hipStream_t st);
+// One BatchNorm of a backward. Two decisions describe every form: who did the reduction (this call: `work`; dy's
+// producer: `sums`) and who runs the apply pass (this call: `dx`; x's producer as it loads dy: `dx` null).
+struct BnBwdSide {
+  const uint16_t* x = nullptr;
+  const float *mean = nullptr, *invstd = nullptr, *gamma = nullptr, *beta = nullptr;
+  float *dgamma = nullptr, *dbeta = nullptr;
+  const float* sums = nullptr;  // the producer's reduction [nrep][2][C] (sum g, sum g (x - mean)), or null
+  float* work = nullptr;        // the reduce sweep's partials (bn_workspace_floats); null when `sums` is given
+  float* params = nullptr;      // fp32 [4][C] (sc | B | D | shift): written by the first half, read by the second
+  uint16_t* dx = nullptr;       // where the apply pass writes; null: deferred to a consumer that applies on load
+};
+// The first half: dgamma, dbeta and the params table of `a` -- and of `b`, a second BatchNorm fed by the same masked
+// dy (a ResNet downsample block; both sides with sums or both without; with sums `b` shares `a`'s sum g, slot 0).
+// The ReLU of the forward: the packed `mask`, recomputed from x (`relu_x`, one side only), or none.
+void launch_bn_bwd_params(const uint16_t* dy, const uint8_t* mask, bool relu_x, int nrep, const BnBwdSide& a,
+                          const BnBwdSide* b, long M, int C, hipStream_t st);
+// The second half: a.dx (and dres = the masked dy) from a.params; with `b` both dx in one pass over dy and the mask.
+void launch_bn_bwd_apply(const uint16_t* dy, const uint8_t* mask, bool relu_x, const BnBwdSide& a, const BnBwdSide* b,
+                         uint16_t* dres, long M, int C, hipStream_t st);
 void launch_bn_finalize_sums(const float* gamma, const float* beta, const float* sums, int nrep, float* save_mean,
                              float* save_invstd, float* run_mean, float* run_var, float* params, long M, int C,
                              float eps, float momentum, hipStream_t st);
 constexpr int kConvStatReplicas = 32;  // must match STAT_REPL in gemm.hip
-void launch_bn_bwd(const uint16_t* dy, const uint16_t* x, const float* mean, const float* invstd, const float* gamma,
-                   const float* beta, bool relu_x, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta,
-                   float* work, float* params, long M, int C, hipStream_t st, const uint8_t* mask = nullptr);
-// launch_bn_bwd / launch_bn_bwd_from_sums in their two halves: dgamma, dbeta and the params table [sc | B | D | shift]
-// (sums null: the reduce sweep here, work = bn_workspace_floats), then the apply pass that reads it
-void launch_bn_bwd_params(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* sums, int nrep,
-                          const float* mean, const float* invstd, const float* gamma, const float* beta, bool relu_x,
-                          float* dgamma, float* dbeta, float* work, float* params, long M, int C, hipStream_t st);
-void launch_bn_bwd_apply_pass(const uint16_t* dy, const uint16_t* x, const uint8_t* mask, const float* params,
-                              bool relu_x, uint16_t* dx, uint16_t* dres, long M, int C, hipStream_t st);
 // packed ReLU bits of a bf16 tensor (bit j of byte e = y[8e + j] > 0), nvec = numel / 8
 void launch_relu_mask(const uint16_t* y, uint8_t* mask, long nvec, hipStream_t st);
 
@@ -434,19 +414,10 @@ void launch_bn_relu_maxpool_fwd(const uint16_t* x, const float* gamma, const flo
                                 float* save_mean, float* save_invstd, float* run_mean, float* run_var, float* params,
                                 uint16_t* y, uint8_t* idx, int N, int H, int W, int C, float eps, float momentum,
                                 hipStream_t st, uint16_t* xarg = nullptr, uint8_t* ybits = nullptr);
-void launch_pool_bn_bwd_from_sums(const uint16_t* dpool, const uint8_t* idx, const uint16_t* x, const float* mean,
-                                  const float* invstd, const float* gamma, const float* beta, uint16_t* dx,
-                                  float* dgamma, float* dbeta, const float* sums, int nrep, float* params, int N,
-                                  int H, int W, int C, hipStream_t st);
 int pool_bn_workspace_floats(int C);
-void launch_pool_bn_bwd(const uint16_t* dpool, const uint8_t* idx, const uint16_t* x, const float* mean,
-                        const float* invstd, const float* gamma, const float* beta, uint16_t* dx, float* dgamma,
-                        float* dbeta, float* work, float* params, int N, int H, int W, int C, hipStream_t st);
-
-// Streaming-order state (batchnorm.hip): direction (0 ascending, 1 descending, as 8 concurrent bands) of the next
-// streaming launch; `fixed` is the direction used in the fixed-BatchNorm mode.
-int stream_order_mode();
-int stream_dir(int fixed);
+// s.sums (with nrep) given: the final and apply passes only, else s.work = pool_bn_workspace_floats(C)
+void launch_pool_bn_bwd(const uint16_t* dpool, const uint8_t* idx, int nrep, const BnBwdSide& s, int N, int H, int W,
+                        int C, hipStream_t st);
 
 void launch_flash_fwd(const AttnFwdArgs& a, int D, hipStream_t st);
 void launch_flash_bwd(const AttnBwdArgs& a, int D, const uint16_t* o, long sob, long sos, long soh, hipStream_t st);

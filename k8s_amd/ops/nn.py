@@ -456,21 +456,17 @@ class _BnAct(torch.autograd.Function):
             # residual gradient for a linked consumer: (dy, mask) instead of a written dres tensor
             handoff = isinstance(ctx.res_link, GradLink) and ctx.has_res and mask is not None
             want_dres = ctx.has_res and not (handoff or mask_out)
+            # the reduction, where it came with dy from its producer's epilogue (BnStatLink)
             pre = ctx.stat_link.take(dy) if ctx.stat_link is not None else None
+            sums = pre[0] if pre is not None else None
             if ctx.bn3_link is not None and not want_dres and bn3_onload_on():
                 # the first half only: x's producer applies the table as it loads dy (Bn3Link)
-                params = _C().bn_bwd_params(dy, x, mask, pre[0] if pre is not None else None, mean, invstd,
-                                            pg.master, pb.master, dg, db)
+                params = _C().bn_bwd_params(dy, x, mask, sums, mean, invstd, pg.master, pb.master, dg, db)
                 ctx.bn3_link.fill(dy, x, mask, params)
                 dx, dres = dy, None
-            elif pre is not None and mask is None:  # relu_x: the reduction came with dy (BnStatLink)
-                dx, dres = _C().bn_bwd_relu_from_sums(dy, x, pre[0], mean, invstd, pg.master, pb.master, dg, db)[0], None
-            elif pre is not None:  # the reduction came with dy from its producer's epilogue (BnStatLink)
-                dx, dres = _C().bn_bwd_from_sums(dy, x, mask, pre[0], mean, invstd, pg.master, pb.master, dg, db,
-                                                 want_dres)
             else:
                 dx, dres = _C().bn_bwd(dy, x, y, mean, invstd, pg.master, pb.master, ctx.relu_x, dg, db, want_dres,
-                                       mask)
+                                       mask, sums)
             if ctx.bn3_link is not None and dx is not dy:
                 _conv_impl().STATS["bn3_apply"] += 1
             if handoff:
@@ -564,10 +560,8 @@ class _BnReluConv(torch.autograd.Function):
         dz = impl.conv_bwd(gy, x, pw.weight, ctx.stride, ctx.padding, True, pw, xform=params, bn_link=link, bn3=bn3)
         dg, db, finish = _bn_param_grads(pg, pb, x.device)
         pre = link.take(dz) if link is not None else None
-        if pre is not None:
-            dx = _C().bn_bwd_relu_from_sums(dz, x, pre[0], mean, invstd, pg.master, pb.master, dg, db)[0]
-        else:
-            dx, _ = _C().bn_bwd(dz, x, None, mean, invstd, pg.master, pb.master, True, dg, db, False)
+        dx, _ = _C().bn_bwd(dz, x, None, mean, invstd, pg.master, pb.master, True, dg, db, False, None,
+                            pre[0] if pre is not None else None)
         finish()
         return (dx if ctx.x_requires_grad else None,) + (None,) * 12
 
@@ -1131,10 +1125,8 @@ class _BnReluMaxPool(torch.autograd.Function):
         dg, db, finish = _bn_param_grads(pg, pb, x.device)
         dy = dy.contiguous()
         pre = ctx.link.take(dy) if ctx.link is not None else None
-        if pre is not None:
-            dx = _C().pool_bn_bwd_from_sums(dy, idx, x, mean, invstd, pg.master, pb.master, dg, db, pre[0])
-        else:
-            dx = _C().pool_bn_bwd(dy, idx, x, mean, invstd, pg.master, pb.master, dg, db)
+        dx = _C().pool_bn_bwd(dy, idx, x, mean, invstd, pg.master, pb.master, dg, db,
+                              pre[0] if pre is not None else None)
         finish()
         return (dx,) + (None,) * 8
 
@@ -1192,25 +1184,19 @@ class _BnActDual(torch.autograd.Function):
         dg, db, finish = _bn_param_grads(pg, pb, x.device)
         dgr, dbr, finish_r = _bn_param_grads(pgr, pbr, x.device)
         pre = ctx.stat_link.take(dy) if ctx.stat_link is not None else None
-        if pre is not None and pre[1] is None:
-            pre = None
+        # both reductions came with dy (BnStatLink), or one reduce sweep here for both (dy and the mask read once)
+        sums, sums_r = pre if pre is not None and pre[1] is not None else (None, None)
+        args = (dy, mask, x, mean, invstd, pg.master, pb.master, dg, db, xr, mean_r, invstd_r, pgr.master, pbr.master,
+                dgr, dbr, sums, sums_r)
         if ctx.bn3_links is not None and _conv_impl().dual_onload_on():
             # the first half only: each input's producer applies its table as it loads dy (Bn3Link)
-            params, params_r = C_.bn_bwd_dual_params(dy, mask, x, mean, invstd, pg.master, pb.master, dg, db,
-                                                     pre[0] if pre is not None else None, xr, mean_r, invstd_r,
-                                                     pgr.master, pbr.master, dgr, dbr,
-                                                     pre[1] if pre is not None else None)
+            params, params_r = C_.bn_bwd_dual_params(*args)
             ctx.bn3_links[0].fill(dy, x, mask, params, dual=True)
             ctx.bn3_links[1].fill(dy, xr, mask, params_r, dual=True)
             _conv_impl().STATS["dual_onload"] += 1
             dx = dxr = dy
-        elif pre is not None:  # both reductions came with dy (BnStatLink)
-            dx, dxr = C_.bn_bwd_dual_from_sums(dy, mask, x, mean, invstd, pg.master, pb.master, dg, db, pre[0], xr,
-                                               mean_r, invstd_r, pgr.master, pbr.master, dgr, dbr, pre[1])
-        else:
-            # one reduce sweep and one apply pass for both (dy and the mask read once per pass)
-            dx, dxr = C_.bn_bwd_dual(dy, mask, x, mean, invstd, pg.master, pb.master, dg, db, xr, mean_r, invstd_r,
-                                     pgr.master, pbr.master, dgr, dbr)
+        else:  # and one apply pass for both
+            dx, dxr = C_.bn_bwd_dual(*args)
         finish()
         finish_r()
         return (dx, None, dxr) + (None,) * 15

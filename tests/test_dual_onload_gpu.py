@@ -1,6 +1,6 @@
 """The stage-1 entry block's two BatchNorm backwards applied on load: the fused 1x1 backward's final form
 (bwd1x1_fused.hip with addend / winner_x / winner_bits / winner_mean) against fp64 and, on load, against itself fed the
-apply pass's gradient; bn_bwd_dual_params against bn_bwd_dual_from_sums; and the block behind the stem's BatchNorm +
+apply pass's gradient; bn_bwd_dual_params against bn_bwd_dual; and the block behind the stem's BatchNorm +
 ReLU + max pool with K8S_AMD_DUAL_ONLOAD on and off."""
 import pytest
 import torch
@@ -185,8 +185,8 @@ def test_final_rejects_bad_operands(cuda):
 
 
 def test_dual_params_then_apply_twice_is_dual_from_sums(cuda):
-    """bn_bwd_dual_params + bn_bwd_apply per half = bn_bwd_dual_from_sums, bit for bit: dx, dxr and both BatchNorms'
-    dgamma / dbeta (M = 677, K = 256); without sums, = bn_bwd_dual."""
+    """bn_bwd_dual_params + bn_bwd_apply per half = bn_bwd_dual, bit for bit: dx, dxr and both BatchNorms' dgamma /
+    dbeta (M = 677, K = 256); from the producer's sums and without them."""
     C_ = _C()
     c = _case(cuda, 677, 64, 256)["inputs"]
     M, K = c["dy"].shape
@@ -204,18 +204,15 @@ def test_dual_params_then_apply_twice_is_dual_from_sums(cuda):
     sums2 = torch.randn(R, 2, K, device=cuda, generator=g)
     for pre in ((sums, sums2), (None, None)):
         a, ar, b, br = vecs(), vecs(), vecs(), vecs()
-        if pre[0] is not None:
-            dx, dxr = C_.bn_bwd_dual_from_sums(c["dy"], c["mask"], x, *a, pre[0], xr, *ar, pre[1])
-        else:
-            dx, dxr = C_.bn_bwd_dual(c["dy"], c["mask"], x, *a, xr, *ar)
-        params, params_r = C_.bn_bwd_dual_params(c["dy"], c["mask"], x, *b, pre[0], xr, *br, pre[1])
+        dx, dxr = C_.bn_bwd_dual(c["dy"], c["mask"], x, *a, xr, *ar, *pre)
+        params, params_r = C_.bn_bwd_dual_params(c["dy"], c["mask"], x, *b, xr, *br, *pre)
         assert torch.equal(C_.bn_bwd_apply(c["dy"], x, c["mask"], params), dx)
         assert torch.equal(C_.bn_bwd_apply(c["dy"], xr, c["mask"], params_r), dxr)
         for i in (4, 5):
             assert torch.equal(a[i], b[i]) and torch.equal(ar[i], br[i])
             assert a[i].abs().max().item() > 0 and ar[i].abs().max().item() > 0
     with pytest.raises(RuntimeError):  # the two sums come together
-        C_.bn_bwd_dual_params(c["dy"], c["mask"], x, *vecs(), sums, xr, *vecs(), None)
+        C_.bn_bwd_dual_params(c["dy"], c["mask"], x, *vecs(), xr, *vecs(), sums, None)
 
 
 # ---------------------------------------------------------------- block level

@@ -602,8 +602,8 @@ def test_dgrad_short_bnstats_epilogue(cuda, M, K, N, dual, rows, monkeypatch):
 
 
 def test_bn_bwd_from_sums_matches_reduce(cuda):
-    """bn_bwd_from_sums (final + apply from a producer's sums) against bn_bwd (its own reduction sweep) on the same
-    masked dy: dx, dgamma, dbeta."""
+    """bn_bwd with sums (final + apply from a producer's sums) against bn_bwd without (its own reduction sweep) on the
+    same masked dy: dx, dgamma, dbeta."""
     C_ = _C()
     torch.manual_seed(12)
     M, C = 4096, 256
@@ -619,9 +619,37 @@ def test_bn_bwd_from_sums_matches_reduce(cuda):
     sums[0, 1] = (g * (x.float() - mean)).sum(0)
     dg1, db1, dg2, db2 = (torch.empty(C, device=cuda) for _ in range(4))
     dx1, _ = C_.bn_bwd(dy, x, None, mean, invstd, gamma, beta, False, dg1, db1, False, mask)
-    dx2, _ = C_.bn_bwd_from_sums(dy, x, mask, sums, mean, invstd, gamma, beta, dg2, db2, False)
+    dx2, _ = C_.bn_bwd(dy, x, None, mean, invstd, gamma, beta, False, dg2, db2, False, mask, sums)
     assert _rel(db2, db1) < 1e-5 and _rel(dg2, dg1) < 1e-4
     assert _rel(dx2, dx1) < 5e-3
+
+
+def test_bn_bwd_relu_from_sums_matches_mask_from_sums(cuda):
+    """bn_bwd from the same fixed sums with the ReLU recomputed from x (relu_x) and with it read from the packed bits of
+    x > 0: dx, dgamma and dbeta bit for bit, every element. mean = beta = 0 and invstd, gamma powers of two make the
+    forward's affine exact, so its sign is the sign of x in any arithmetic, and |x| >= 2^-4 leaves no borderline
+    decision (no x == 0)."""
+    C_ = _C()
+    M, C = 677, 64
+    g = torch.Generator(device=cuda).manual_seed(14)
+    mag = torch.rand(M, C, device=cuda, generator=g) * 4 + 2.0 ** -4
+    x = (mag * torch.where(torch.rand(M, C, device=cuda, generator=g) < 0.5, -1.0, 1.0)).bfloat16()
+    assert int((x == 0).sum()) == 0 and float(x.float().abs().min()) >= 2.0 ** -4
+    dy = torch.randn(M, C, device=cuda, generator=g).bfloat16()
+    pow2 = torch.tensor([0.5, 1.0, 2.0], device=cuda)
+    invstd = pow2[torch.randint(0, 3, (C,), device=cuda, generator=g)]
+    gamma = pow2[torch.randint(0, 3, (C,), device=cuda, generator=g)]
+    mean, beta = torch.zeros(C, device=cuda), torch.zeros(C, device=cuda)
+    bits = (x > 0).view(M, C // 8, 8).to(torch.int32)
+    m = (bits << torch.arange(8, device=cuda, dtype=torch.int32)).sum(-1).to(torch.uint8).view(-1).contiguous()
+    assert torch.equal(_unpack_bits(m, (M, C)), x > 0)
+    S = torch.randn(C_.conv_stat_replicas, 2, C, device=cuda, generator=g)
+    dg1, db1, dg2, db2 = (torch.zeros(C, device=cuda) for _ in range(4))
+    dx1, _ = C_.bn_bwd(dy, x, None, mean, invstd, gamma, beta, True, dg1, db1, False, None, S)
+    dx2, _ = C_.bn_bwd(dy, x, None, mean, invstd, gamma, beta, False, dg2, db2, False, m, S)
+    assert torch.equal(dx1, dx2)
+    assert torch.equal(dg1, dg2) and torch.equal(db1, db2)
+    assert dx1.float().abs().max().item() > 0 and dg1.abs().max().item() > 0 and db1.abs().max().item() > 0
 
 
 @pytest.mark.parametrize("N,H,C,K", [(3, 56, 64, 64), (2, 28, 128, 128), (3, 14, 256, 256)])

@@ -362,7 +362,7 @@ def test_bn_relu_maxpool_fused_vs_fp32(cuda, N, H, W, C):
     bsums[0, 0] = gsel.sum(0)
     bsums[1, 1] = (gsel * (xarg.float().reshape(-1, C) - mean2)).sum(0)
     dg2, db2 = torch.empty(C, device=cuda), torch.empty(C, device=cuda)
-    dx2 = _C().pool_bn_bwd_from_sums(dy, idx2, x, mean2, invstd2, g, b, dg2, db2, bsums)
+    dx2 = _C().pool_bn_bwd(dy, idx2, x, mean2, invstd2, g, b, dg2, db2, bsums)
     # sums over the pooled gradient itself: a pixel that wins several windows adds their dy unrounded (the reference
     # and the reduce pass sum the bf16-rounded dz of that pixel), so ~1 bf16 ulp of such pixels apart
     _close(db2, dbr, 5e-3)
