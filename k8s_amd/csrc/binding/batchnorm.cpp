@@ -228,20 +228,24 @@ std::vector<Tensor> bn_bwd(Tensor dy, Tensor x, OptTensor y, Tensor mean, Tensor
 // loads (bwd1x1_fused with x3 / mask / params). bn_bwd_params: dgamma, dbeta and the params table fp32 [sc | B | D |
 // shift] -- from the producer's sums, or from its own reduce sweep without them. bn_bwd_apply: dx from that table, the
 // bits bn_bwd writes.
-Tensor bn_bwd_params(Tensor dy, Tensor x, Tensor mask, OptTensor sums, Tensor mean, Tensor invstd, Tensor gamma,
+// mask None: a non-residual BatchNorm + ReLU, the ReLU decision recomputed from x (relu_x) in both halves -- for a
+// consumer of dx that forms it on load from dy, x and the table (conv1_fused).
+Tensor bn_bwd_params(Tensor dy, Tensor x, OptTensor mask, OptTensor sums, Tensor mean, Tensor invstd, Tensor gamma,
                      Tensor beta, Tensor dgamma, Tensor dbeta) {
   const int C = bn_channels(x, "x", true);
   const long M = x.numel() / C;
   check_same_shape(dy, x, "dy");
-  const uint8_t* mk = check_bit_mask(mask, x.numel(), "mask");
+  const bool has_mask = mask && mask->defined();
+  const uint8_t* mk = has_mask ? check_bit_mask(*mask, x.numel(), "mask") : nullptr;
   BwdSide a = bwd_side(x, mean, invstd, gamma, beta, dgamma, dbeta, opt_ptr(sums), "sums", M, C);
-  launch_bn_bwd_params(cbf(dy), mk, false, a.nrep, a.s, nullptr, M, C, cur_stream());
+  launch_bn_bwd_params(cbf(dy), mk, !has_mask, a.nrep, a.s, nullptr, M, C, cur_stream());
   return a.params;
 }
-Tensor bn_bwd_apply(Tensor dy, Tensor x, Tensor mask, Tensor params) {
+Tensor bn_bwd_apply(Tensor dy, Tensor x, OptTensor mask, Tensor params) {
   const int C = bn_channels(x, "x", true);
   check_same_shape(dy, x, "dy");
-  const uint8_t* mk = check_bit_mask(mask, x.numel(), "mask");
+  const bool has_mask = mask && mask->defined();
+  const uint8_t* mk = has_mask ? check_bit_mask(*mask, x.numel(), "mask") : nullptr;
   check_channel_f32(params, 4L * C, "params");
   TORCH_CHECK(params.device() == x.device(), "params: on x's device");
   auto dx = torch::empty_like(x);
@@ -249,7 +253,7 @@ Tensor bn_bwd_apply(Tensor dy, Tensor x, Tensor mask, Tensor params) {
   a.x = cbf(x);
   a.params = f32(params);
   a.dx = bf(dx);
-  launch_bn_bwd_apply(cbf(dy), mk, false, a, nullptr, nullptr, x.numel() / C, C, cur_stream());
+  launch_bn_bwd_apply(cbf(dy), mk, !has_mask, a, nullptr, nullptr, x.numel() / C, C, cur_stream());
   return dx;
 }
 
@@ -310,9 +314,9 @@ void bind_batchnorm(pybind11::module_& m) {
   m.def("bn_finalize", &bn_finalize, "sums"_a, "gamma"_a, "beta"_a, "run_mean"_a, "run_var"_a, "count"_a, "momentum"_a,
         "eps"_a);
   m.def("bn_bwd_params", &bn_bwd_params, "dy"_a, "x"_a, "mask"_a, "sums"_a, "mean"_a, "invstd"_a, "gamma"_a, "beta"_a,
-        "dgamma"_a, "dbeta"_a, "first half of a masked BatchNorm backward: dgamma, dbeta, params [sc | B | D | shift]");
+        "dgamma"_a, "dbeta"_a, "first half of a BatchNorm backward (packed mask, or None: relu_x): dgamma, dbeta, params [sc | B | D | shift]");
   m.def("bn_bwd_apply", &bn_bwd_apply, "dy"_a, "x"_a, "mask"_a, "params"_a,
-        "second half of a masked BatchNorm backward: dx from bn_bwd_params' table");
+        "second half of a BatchNorm backward (packed mask, or None: relu_x): dx from bn_bwd_params' table");
   auto def_dual = [&m](const char* name, auto fn, const char* doc) {
     m.def(name, fn, "dy"_a, "mask"_a, "x"_a, "mean"_a, "invstd"_a, "gamma"_a, "beta"_a, "dgamma"_a, "dbeta"_a, "x2"_a,
           "mean2"_a, "invstd2"_a, "gamma2"_a, "beta2"_a, "dgamma2"_a, "dbeta2"_a, "sums"_a = py::none(),

@@ -233,6 +233,42 @@ Tensor bwd1x1_fused(Tensor gy, Tensor x, Tensor w, OptTensor xform, OptTensor ga
   return dz;
 }
 
+// The fused backward of the 1x1 / stride-1 convolution that opens a ResNet identity bottleneck, with the apply pass of
+// the BatchNorm + ReLU behind it formed on load (conv1_fused.hip). dz1 / x1 [M, W]: that BatchNorm's incoming gradient
+// and input, params its fp32 [sc | B | D | shift] table (bn_bwd_params with mask None); w [W, N]; xin [M, N] the
+// convolution's input. Returns dx [M, N] = bf16(bf16(dx1 . w) + (add_mask ? add_src : 0)) with dx1 =
+// bf16(fma(sc, relu_on(x1) ? dz1 : 0, fma(B, x1, D))) never stored; writes (accumulate: adds) dw [W, N] fp32 =
+// dx1^T . xin; adds the BatchNorm-backward sums of dx (g = mask ? dx : 0: sum g, sum g (x - mean)) into sums, zeroed
+// fp32 [conv_stat_replicas, 2, N]. (W, N) = (64, 256) or (128, 512).
+Tensor conv1_fused(Tensor dz1, Tensor x1, Tensor params, Tensor w, Tensor xin, Tensor add_src, Tensor add_mask,
+                   Tensor x, Tensor mask, Tensor mean, Tensor sums, Tensor dw, bool accumulate) {
+  check_bf16_dense(dz1, 2, "dz1"); check_bf16_dense(x1, 2, "x1"); check_bf16_dense(w, 2, "w");
+  check_bf16_dense(xin, 2, "xin"); check_bf16_dense(add_src, 2, "add_src"); check_bf16_dense(x, 2, "x");
+  for (const Tensor* t : {&dz1, &x1, &w, &xin, &add_src, &x, &add_mask, &mask, &params, &mean, &sums, &dw})
+    check_cuda(*t, "conv1_fused operand");
+  const long M = dz1.size(0), W = dz1.size(1), N = w.size(1);
+  TORCH_CHECK(k8s_amd::conv1_fused_ok(M, (int)W, (int)N), "conv1_fused: (W, N) = (64, 256) or (128, 512), 1 <= M < 2^31");
+  TORCH_CHECK(x1.sizes() == dz1.sizes() && w.size(0) == W && xin.size(0) == M && xin.size(1) == N &&
+                  add_src.sizes() == xin.sizes() && x.sizes() == xin.sizes(),
+              "shapes: dz1 / x1 [M, W], w [W, N], xin / add_src / x [M, N]");
+  k8s_amd::Conv1Fused c;
+  c.abits = check_bit_mask(add_mask, M * N, "add_mask"); check_aligned(add_mask, "add_mask");
+  c.bits = check_bit_mask(mask, M * N, "mask"); check_aligned(mask, "mask");
+  check_channel_f32(params, 4 * W, "params"); check_aligned(params, "params");
+  check_channel_f32(mean, N, "mean");
+  check_stat_sums(sums, N, "sums", true);
+  check_cuda(dw, "dw"); check_dtype(dw, at::kFloat, "dw"); check_aligned(dw, "dw");
+  TORCH_CHECK(dw.numel() == W * N, "dw must have W * N fp32 elements");
+  for (const Tensor* t : {&x1, &w, &xin, &add_src, &x, &add_mask, &mask, &params, &mean, &sums, &dw})
+    TORCH_CHECK(t->device() == dz1.device(), "conv1_fused: every operand on dz1's device");
+  Tensor dx = torch::empty({M, N}, dz1.options());
+  Tensor part = torch::empty({k8s_amd::conv1_fused_workspace(M, (int)W, (int)N)}, dw.options());
+  c.dz1 = cbf(dz1); c.x1 = cbf(x1); c.params = f32(params); c.w = cbf(w); c.xin = cbf(xin); c.dy = cbf(add_src);
+  c.x3 = cbf(x); c.mean = f32(mean); c.dx = bf(dx); c.sums = f32(sums); c.dw = f32(dw); c.dw_partials = f32(part);
+  launch_conv1_fused(c, M, (int)W, (int)N, accumulate, cur_stream());
+  return dx;
+}
+
 // The 3x3 / pad-1 weight gradient dw [K, 3, 3, C] fp32 (+)= dy^T . im2col(x) on the 4-wave GEMM with gathered B rows
 // (gemm256.hip), always: a shape outside conv3x3_w4_wgrad_ok raises (conv_wgrad asks conv3x3_w4_wgrad_use first).
 void conv3x3_w4_wgrad(Tensor x, Tensor dy, Tensor dw, int64_t stride, bool accumulate) {
@@ -370,6 +406,12 @@ void bind_conv(pybind11::module_& m) {
   m.def("bwd1x1_final_ok", [](int64_t M, int64_t C, int64_t K) {
     return C <= 1024 && K <= 4096 && k8s_amd::bwd1x1_final_ok(M, (int)C, (int)K);
   }, "M"_a, "C"_a, "K"_a, "whether bwd1x1_fused's final form (addend, winner_*) takes this shape");
+  m.def("conv1_fused", &conv1_fused, "dz1"_a, "x1"_a, "params"_a, "w"_a, "xin"_a, "add_src"_a, "add_mask"_a, "x"_a,
+        "mask"_a, "mean"_a, "sums"_a, "dw"_a, "accumulate"_a,
+        "identity-block conv1 backward with bn1's apply pass on load: dx, dw and the sums in one pass (conv1_fused.hip)");
+  m.def("conv1_fused_ok", [](int64_t M, int64_t W, int64_t N) {
+    return W <= 1024 && N <= 4096 && k8s_amd::conv1_fused_ok(M, (int)W, (int)N);
+  }, "M"_a, "W"_a, "N"_a, "whether conv1_fused takes this shape");
   m.def("wgrad_stream_eligible",&k8s_amd::wgrad_stream_eligible, "tall-K weight-gradient kernel takes this shape");
   m.def("conv_dgrad_wtrans", &conv_dgrad_wtrans);
   m.def("conv_dgrad_wsub", &conv_dgrad_wsub);

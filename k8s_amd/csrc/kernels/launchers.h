@@ -300,6 +300,28 @@ void launch_bwd1x1_fused(const uint16_t* gy, const uint16_t* x, const uint16_t* 
                          const float* gamma, const float* beta, const float* mean, const float* invstd, uint16_t* dz,
                          float* dw, float* sums, long M, int C, int K, bool accumulate, hipStream_t st,
                          const Bwd1x1Bn3* bn3 = nullptr, const Bwd1x1Final* fin = nullptr);
+// conv1_fused.hip: the whole backward of the 1x1 / stride-1 convolution that opens a ResNet identity bottleneck (N -> W
+// channels, (W, N) = (64, 256) or (128, 512), M < 2^31) with the apply pass of the BatchNorm + ReLU behind it formed on
+// load, in one pass: dx1 = bf16(fma(sc, relu_on(x1) ? dz1 : 0, fma(B, x1, D))) (params fp32 [sc | B | D | shift], 4W,
+// launch_bn_bwd_params with relu_x) is never stored; dx [M][N] = bf16(bf16(dx1 . w) + (abit ? dy : 0)), w [W][N];
+// sums [kConvStatReplicas][2][N] (zeroed) += sum g, sum g (x3 - mean), g = bit ? dx : 0 (GemmShortBnStats, one
+// BatchNorm); dw [W][N] fp32 (+)= dx1^T . xin through per-walker slabs summed in order (no atomics).
+struct Conv1Fused {
+  const uint16_t *dz1 = nullptr, *x1 = nullptr;  // [M][W]
+  const float* params = nullptr;
+  const uint16_t *w = nullptr, *xin = nullptr;   // [W][N], [M][N]
+  const uint16_t* dy = nullptr;                  // the masked addend [M][N] and its packed bits [M][N / 8]
+  const uint8_t* abits = nullptr;
+  const uint16_t* x3 = nullptr;                  // the BatchNorm of the sums: input, packed ReLU bits, mean
+  const uint8_t* bits = nullptr;
+  const float* mean = nullptr;
+  uint16_t* dx = nullptr;
+  float *sums = nullptr, *dw = nullptr;
+  float* dw_partials = nullptr;  // conv1_fused_workspace floats
+};
+bool conv1_fused_ok(long M, int W, int N);
+long conv1_fused_workspace(long M, int W, int N);
+void launch_conv1_fused(const Conv1Fused& c, long M, int W, int N, bool accumulate, hipStream_t st);
 void launch_conv_dgrad_wtrans(const uint16_t* w, uint16_t* w2, int K, int R, int S, int C, hipStream_t st);
 // per-output-parity sub-weights of a stride-s dgrad (up to 16 parities x 16 taps), packed at off[p]
 struct DgradTaps {

@@ -95,10 +95,13 @@ class Bottleneck(nn.Module):
             fuse = K.BN_DUAL and isinstance(dn, tuple) and dn[1] is not None and self.training and dn[0].is_cuda
             if not fuse:
                 idn = self.down_bn(dn, relu=False, dy_link=mlink)
-        t = self.conv1(x, grad_link=link or dlink)
+        # identity block: bn1's backward apply pass is taken on load by conv1's fused backward where that kernel runs
+        # (ops.nn.Bn3Link, relu form: stages 1 and 2 behind another identity block), so dx1 is never written
+        b1 = K.Bn3Link() if (identity and self.training) else None
+        t = self.conv1(x, grad_link=link or dlink, bn3_link=b1)
         # bn1 / bn2 + ReLU: normalised on load by the consuming convolution where ops.nn.BN_ONLOAD and its kernels
         # take it (ops.nn.bn_relu_conv: no apply pass, no z tensor), else applied by the BN kernel
-        t = K.bn_relu_conv(t, self.bn1, self.conv2)
+        t = K.bn_relu_conv(t, self.bn1, self.conv2, bn_in_link=b1)
         # identity block: bn3's backward apply pass is taken on load by conv3's fused backward where that kernel
         # runs (ops.nn.Bn3Link: stages 1 and 2), so dx3 is never written
         b3 = K.Bn3Link() if self.training else None

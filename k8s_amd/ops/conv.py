@@ -48,10 +48,15 @@ STATS = {"hip_fwd": 0, "aten_fwd": 0, "hip_wgrad": 0, "aten_wgrad": 0, "hip_dgra
          # final form (the downsample convolution's; with or without the downsample BatchNorm's backward on load)
          "dual_onload": 0, "dual_apply": 0, "fused_final": 0,
          # 3x3 forwards on the 4-wave GEMM with gathered A rows (_w4_3x3; counted in hip_fwd as well)
-         "w4_3x3_fwd": 0}
+         "w4_3x3_fwd": 0,
+         # an identity block's bn1 that holds a nn.Bn3Link with conv1 (its relu form): bn1 backwards that deferred
+         # their apply pass, apply passes run for bn1 after all (by its own backward, or by conv1's when it could not
+         # take the deferred form), and launches of conv1_fused.hip (conv1's whole backward, bn1's applied on load)
+         "conv1_onload": 0, "conv1_apply": 0, "conv1_fused": 0}
 # data-gradient route name -> times executed. The names name the data gradient's contract (what it accumulates onto,
 # which sums it takes), not the kernel: the fused 1x1 backward's final form is counted under the name _plan_dgrad gives
-# its data gradient ("tile_final_sums"), the kernel that ran in STATS["fused_final"].
+# its data gradient ("tile_final_sums"), the kernel that ran in STATS["fused_final"]; conv1_fused.hip's launches
+# likewise under "short_mask_sums" and in STATS["conv1_fused"].
 ROUTES = collections.Counter()
 
 
@@ -61,6 +66,12 @@ def dual_onload_on() -> bool:
     K8S_AMD_BWD1X1_FUSED=0 switch it off as well."""
     return all(os.environ.get(k, "1") != "0"
                for k in ("K8S_AMD_DUAL_ONLOAD", "K8S_AMD_BN3_ONLOAD", "K8S_AMD_BWD1X1_FUSED"))
+
+def conv1_fused_on() -> bool:
+    """K8S_AMD_CONV1_FUSED=0 (read per call: A/B, tests): an identity block's bn1 runs its own apply pass and conv1's
+    backward stays on its two kernels (gemm_short's masked-addend data gradient, the streaming weight gradient)."""
+    return os.environ.get("K8S_AMD_CONV1_FUSED", "1") != "0"
+
 
 # (Round 5 built weight gradients on a second HIP stream -- each conv's dW kernel forked off the compute stream to
 # overlap the data gradient and BatchNorm passes after it. The streams co-ran, but the HBM-bound kernels stretched:
@@ -411,20 +422,42 @@ def _dgrad_strided_hip(C_, gy, w, stride, padding, H, W, addend=None, bn_link=No
     return dx
 
 
-def _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok=True):
-    """Which family forms a convolution backward's data gradient: "fused_1x1" (both gradients and the input
-    BatchNorm + ReLU's backward sums in one pass over gy and x, bwd1x1_fused.hip), "fused_final" (the same kernel's
-    final form), "stride1" (``_plan_dgrad``), "strided" (``_plan_dgrad_strided``) or "aten". Launches and allocates
-    nothing. K8S_AMD_BWD1X1_FUSED=0 (read per call: A/B, tests) keeps a normalize-on-load 1x1 convolution's two
-    gradients on their two kernels. The fused family is one route, "fused_1x1", in both of its forms; the launches that
-    also apply the output BatchNorm's backward on load (``conv_bwd``'s ``bn3``) are counted in
+def conv1_fused_shape_ok(C_, M, K, C) -> bool:
+    """Whether conv1_fused.hip takes a (C -> K)-channel 1x1 convolution over M rows (the planners' test stubs carry no
+    such predicate: no)."""
+    ok = getattr(C_, "conv1_fused_ok", None)
+    return ok is not None and bool(ok(M, K, C))
+
+
+def _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok=True, bn1=None):
+    """Which family forms a convolution backward's data gradient: "conv1_fused" (below), "fused_1x1" (both gradients
+    and the input BatchNorm + ReLU's backward sums in one pass over gy and x, bwd1x1_fused.hip), "fused_final" (the same
+    kernel's final form), "stride1" (``_plan_dgrad``), "strided" (``_plan_dgrad_strided``) or "aten". Launches and
+    allocates nothing. K8S_AMD_BWD1X1_FUSED=0 (read per call: A/B, tests) keeps a normalize-on-load 1x1 convolution's
+    two gradients on their two kernels. The fused family is one route, "fused_1x1", in both of its forms; the launches
+    that also apply the output BatchNorm's backward on load (``conv_bwd``'s ``bn3``) are counted in
     ``STATS["bn3_onload"]``.
+    "conv1_fused": ``bn1`` is the filled relu-form ``nn.Bn3Link`` of the BatchNorm + ReLU that reads a (C, K) =
+    (256, 64) or (512, 128) 1x1 convolution's output -- ``gy`` is that BatchNorm's incoming gradient, its apply pass
+    deferred -- and the data gradient takes a masked addend and a mask-kind link's sums (an identity bottleneck's conv1
+    in ResNet's stages 1-2, after another identity block): both gradients, the sums and the BatchNorm's apply in one
+    pass (conv1_fused.hip), the contract of ``_plan_dgrad``'s "short_mask_sums" for the data gradient.
+    ``conv1_fused_on()`` switches it.
     "fused_final": a (C, K) = (64, 256) 1x1 convolution reading a stored x (no xform) whose data gradient is the
     second into x -- it accumulates onto the contiguous tensor ``addend`` -- and takes the sums of a pool-kind link
     covering x (ResNet's stage-1 downsample convolution): both gradients and the sums in one pass, the contract of
     ``_plan_dgrad``'s "tile_final_sums" for the data gradient. ``dw_ok``: the weight gradient is still to be formed,
     into an fp32 slot. ``dual_onload_on()`` switches it."""
     K, R, S, C = w.shape
+    if (bn1 is not None and bn1.mask is None and bn1.covers(gy) and xform is None and dw_ok and addend is not None
+            and not torch.is_tensor(addend) and R == 1 and S == 1 and stride == 1 and padding == 0 and conv1_fused_on()
+            and _link_kind(bn_link, x.shape) == "mask" and _hip(gy, x, w, addend.dy) and gy.is_contiguous()
+            and x.is_contiguous() and addend.dy.is_contiguous() and addend.dy.shape == x.shape
+            and bn1.x3.shape == gy.shape and conv1_fused_shape_ok(C_, gy.numel() // K, K, C)
+            # ... and only where the parent's route takes the sums in its epilogue ("short_mask_sums": the switches
+            # that turn those sums off turn this route off with them)
+            and C_.gemm_short_bnstats_ok(gy.numel() // K, C, K, False)):
+        return "conv1_fused"
     if (xform is None and dw_ok and torch.is_tensor(addend) and addend.is_contiguous() and addend.shape == x.shape
             and R == 1 and S == 1 and stride == 1 and padding == 0 and dual_onload_on()
             and _link_kind(bn_link, x.shape) == "pool" and _hip(gy, x, w, addend) and gy.is_contiguous()
@@ -465,10 +498,20 @@ def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None
     pass, so ``gy`` may be that BatchNorm's incoming dy and not yet the gradient of the output. The fused 1x1 family,
     in either form, applies it on load when the link covers ``gy`` (``STATS["bn3_onload"]`` / ``["fused_final"]``);
     in every other case the apply pass runs here first, on the ``gy`` received (``STATS["bn3_apply"]``, or
-    ``["dual_apply"]`` for a half of a downsample block's two BatchNorms)."""
+    ``["dual_apply"]`` for a half of a downsample block's two BatchNorms). A relu-form link (no mask: the BatchNorm +
+    ReLU behind an identity block's conv1, which this convolution's OUTPUT feeds) is taken only by the "conv1_fused"
+    family (``STATS["conv1_fused"]``); else its apply pass runs here first (``["conv1_apply"]``)."""
     K, R, S, C = w.shape
     C_ = _load() if gy.is_cuda else None
     dw_ok = p is not None and x_sub is None and p.grad.dtype == torch.float32
+    bn1 = None
+    if bn3 is not None and bn3.mask is None:
+        bn1, bn3 = bn3, None
+        if not (need_dx and _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok, bn1)
+                == "conv1_fused"):
+            STATS["conv1_apply"] += 1
+            gy = C_.bn_bwd_apply(gy.contiguous(), bn1.x3, None, bn1.params)
+            bn1 = None
     if bn3 is not None and not (need_dx and bn3.covers(gy)
                                 and _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok)
                                 in ("fused_1x1", "fused_final")):
@@ -487,7 +530,19 @@ def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None
     if addend is not None and not torch.is_tensor(addend) and not (
             hip and stride == 1 and K % 8 == 0 and C % 8 == 0):
         addend = addend.materialize()  # only the stride-1 dgrad on our kernels takes the (dy, mask) pair
-    family = _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok) if need_dx else None
+    family = _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok, bn1) if need_dx else None
+    if family == "conv1_fused":
+        ROUTES[_plan_dgrad(C_, gy, w, padding, addend, bn_link)] += 1  # the data gradient's contract: short_mask_sums
+        STATS["conv1_fused"] += 1
+        STATS["hip_wgrad"] += 1
+        STATS["hip_dgrad"] += 1
+        sums = _bn_sums(C_, bn_link, C, gy.device)
+        dx = C_.conv1_fused(gy.view(-1, K), bn1.x3.view(-1, K), bn1.params, w.view(K, C), x.view(-1, C),
+                            addend.dy.view(-1, C), addend.mask, bn_link.x.view(-1, C), bn_link.mask, bn_link.mean,
+                            sums, p.grad.view(K, C), p.written).view(x.shape)
+        _slot_written(p)
+        bn_link.deposit(sums, None, dx)
+        return dx
     if family == "fused_final":
         ROUTES[_plan_dgrad(C_, gy, w, padding, addend, bn_link)] += 1  # the data gradient's contract: tile_final_sums
         STATS["fused_final"] += 1

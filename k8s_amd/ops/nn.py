@@ -228,7 +228,13 @@ class Bn3Link:
     A stage-1 entry block holds two: one joins bn3 to conv3 as above, the other the downsample BatchNorm to the
     downsample convolution (``conv2d_nhwc(..., bn3_link=l)``, whose backward is then the fused kernel's final form),
     both BatchNorms running as one (``bn_act_dual(..., bn3_link=, bn3_link_r=)``). That backward defers both halves or
-    neither (``dual``: which counter an apply pass run for the link after all is counted in)."""
+    neither (``dual``: which counter an apply pass run for the link after all is counted in).
+
+    The relu form joins an identity block's bn1 (BatchNorm + ReLU, no residual, no stored mask: ``mask`` stays None
+    and the ReLU decision is recomputed from x) to conv1, which produced its input x1
+    (``conv2d_nhwc(x, conv1, bn3_link=l)`` then ``batch_norm_act(x1, ..., bn3_link=l)``): conv1's backward on
+    conv1_fused.hip forms dx1 from bn1's incoming gradient, x1 and the table as it loads them
+    (``ops.conv._plan_bwd`` "conv1_fused"), or runs the apply pass on what it received."""
     __slots__ = ("y_key", "x3", "mask", "params", "dy_key", "dual")
 
     def __init__(self):
@@ -287,6 +293,17 @@ class _Conv2dNHWC(torch.autograd.Function):
                 and bn_link is not None and bn_link.kind == "pool" and bn_link.x.shape == x.shape
                 and impl._hip(x, w) and impl.dual_onload_on() and p.grad.dtype == torch.float32
                 and _C().bwd1x1_final_ok(x.numel() // C, C, K_)):
+            bn3_link.offer(y)
+            ctx.bn3_link = bn3_link
+        # an identity block's conv1 in the shapes of conv1_fused.hip, behind another identity block (a mask-kind link
+        # on x, the residual gradient arriving through a GradLink of its own): its backward can take the apply pass of
+        # the BatchNorm + ReLU that reads y (Bn3Link, relu form). What only the backward knows -- the addend's form,
+        # the switch -- is checked there (ops.conv._plan_bwd "conv1_fused").
+        if (bn3_link is not None and ctx.bn3_link is None and BN_BSTATS and R == 1 and S == 1 and stride == 1
+                and padding == 0 and xs is None and link is not None and not link.shared and x.requires_grad
+                and x.is_contiguous() and bn_link is not None and bn_link.kind == "mask"
+                and bn_link.x.shape == x.shape and impl._hip(x, w) and p.grad.dtype == torch.float32
+                and impl.conv1_fused_shape_ok(_C(), x.numel() // C, K_, C)):
             bn3_link.offer(y)
             ctx.bn3_link = bn3_link
         if sums is not None:
@@ -438,8 +455,9 @@ class _BnAct(torch.autograd.Function):
                 stat_link.fill_mask(x, mask, mean, pg.store)
             ctx.stat_link = stat_link
         # the convolution that produced x takes this BatchNorm's apply pass into its backward (Bn3Link)
-        ctx.bn3_link = bn3_link if (bn3_link is not None and mask is not None and training
-                                    and bn3_link.offered(x)) else None
+        # ... or, a BatchNorm + ReLU without residual (the ReLU recomputed from x), conv1 of an identity block (relu form)
+        ctx.bn3_link = bn3_link if (bn3_link is not None and training and bn3_link.offered(x)
+                                    and (mask is not None or (ctx.relu_x and res is None and _gpu(x)))) else None
         return y
 
     @staticmethod
@@ -459,16 +477,19 @@ class _BnAct(torch.autograd.Function):
             # the reduction, where it came with dy from its producer's epilogue (BnStatLink)
             pre = ctx.stat_link.take(dy) if ctx.stat_link is not None else None
             sums = pre[0] if pre is not None else None
-            if ctx.bn3_link is not None and not want_dres and bn3_onload_on():
-                # the first half only: x's producer applies the table as it loads dy (Bn3Link)
+            defer = ctx.bn3_link is not None and not want_dres and (
+                _conv_impl().conv1_fused_on() if ctx.relu_x else bn3_onload_on())
+            if defer:
+                # the first half only: x's producer applies the table as it loads dy (Bn3Link; relu form: mask None)
                 params = _C().bn_bwd_params(dy, x, mask, sums, mean, invstd, pg.master, pb.master, dg, db)
                 ctx.bn3_link.fill(dy, x, mask, params)
+                _conv_impl().STATS["conv1_onload"] += ctx.relu_x
                 dx, dres = dy, None
             else:
                 dx, dres = _C().bn_bwd(dy, x, y, mean, invstd, pg.master, pb.master, ctx.relu_x, dg, db, want_dres,
                                        mask, sums)
             if ctx.bn3_link is not None and dx is not dy:
-                _conv_impl().STATS["bn3_apply"] += 1
+                _conv_impl().STATS["conv1_apply" if ctx.relu_x else "bn3_apply"] += 1
             if handoff:
                 dres = MaskedGrad(dy, mask)
             elif mask_out:  # the producing plain BN masks dy itself (MaskLink)
@@ -589,11 +610,12 @@ def onload_ok(x, conv) -> bool:
             bool(_C().conv3x3_staged_ok(x.shape[1], x.shape[2], C, K_, R, S, conv.stride, conv.pad)))
 
 
-def bn_relu_conv(t, bn, conv, bn3_link=None):
+def bn_relu_conv(t, bn, conv, bn3_link=None, bn_in_link=None):
     """``conv(bn(t))`` for ``t = (x, sums)`` from ``conv2d_nhwc(..., with_stats=True)``, a training-mode ReLU
     BatchNorm ``bn`` (models/resnet.BN) and a convolution ``conv`` (models/resnet.Conv): normalised on load
     (``_BnReluConv``) where the kernels take it (``onload_ok``), else the separate BN apply + conv. Returns (y, y's
-    sums). ``bn3_link``: a Bn3Link shared with the residual BatchNorm that is y's only reader."""
+    sums). ``bn3_link``: a Bn3Link shared with the residual BatchNorm that is y's only reader. ``bn_in_link``: a
+    relu-form Bn3Link shared with the convolution that produced ``x``, for ``bn`` where it runs as its own pass."""
     x, sums = t if isinstance(t, tuple) else (t, None)
     w = conv.w
     if (sums is not None and bn.training and _gpu(x) and x.dtype == torch.bfloat16 and x.shape[-1] % 64 == 0
@@ -601,7 +623,7 @@ def bn_relu_conv(t, bn, conv, bn3_link=None):
             and onload_ok(x, conv)):
         return _BnReluConv.apply(x, sums, w.store.anchor, bn.gamma, bn.beta, bn.running_mean, bn.running_var,
                                  bn.momentum, bn.eps, w, conv.stride, conv.pad, bn3_link)
-    return conv(bn(t))
+    return conv(bn(t, bn3_link=bn_in_link))
 
 
 # BatchNorm apply passes write the stride-2 subsample for a following downsample block (SubLink);

@@ -16,7 +16,7 @@ import json
 import re
 
 CATS = [
-    ("fused 1x1 backward (dgrad + wgrad + BN sums)", r"bwd1x1_fused"),
+    ("fused 1x1 backward (dgrad + wgrad + BN sums)", r"bwd1x1_fused|conv1_fused|slab_reduce"),
     ("BatchNorm", r"k8s_amd::bn_|relu_mask|pool_bn_bwd"),
     ("weight gradient", r"wgrad_stream|ConvWgB|MNMajorK, k8s_amd::MNMajorK|MNMaj, k8s_amd::g256r::MNMaj|gemm_w4_kernel<true, true>|splitk_reduce|"
                         r"wgrad3x3|wg3_reduce|stem_wgrad|stem_dw"),
