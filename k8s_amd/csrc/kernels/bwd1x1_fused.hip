@@ -99,7 +99,7 @@
 
 #include "common.h"
 #include "launchers.h"
-#include "mfma.h"
+#include "lds_image.h"
 
 namespace k8s_amd {
 namespace b1f {
@@ -110,24 +110,6 @@ constexpr int CT = 64;  // channels per workgroup
 __device__ __attribute__((aligned(64))) uint16_t g_zero16[64];
 
 typedef __attribute__((ext_vector_type(4))) int int4_t;
-
-__device__ __forceinline__ int swz128(int r) { return 2 * (((r >> 1) & 1) | (((r >> 3) & 1) << 1)); }
-__device__ __forceinline__ int swz_g(int r) { return (2 * ((r & 3) | (((r >> 3) & 1) << 2))) | ((r >> 2) & 1); }
-
-struct TrRaw {
-  short4_t lo, hi;
-};
-// Transposed fragment of an [rows (m)][RB bytes] image: lane l holds column rb + (l & 15), rows kk*32 + 8*(l >> 4) + j
-template <int RB, bool G>
-__device__ __forceinline__ void tr_load(TrRaw& r, const char* img, int rb, int kk, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int u = (rb >> 3) + (p >> 1);
-  const int r0 = kk * 32 + 8 * g + q, r1 = r0 + 4;
-  const int u0 = u ^ (G ? swz_g(r0) : swz128(r0)), u1 = u ^ (G ? swz_g(r1) : swz128(r1));
-  tr16_asm(r.lo, img + r0 * RB + (u0 << 4) + (p & 1) * 8);
-  tr16_asm(r.hi, img + r1 * RB + (u1 << 4) + (p & 1) * 8);
-}
-#define K8S_LDS_TIE4(w, a, b, c, d) asm volatile(w : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
 
 struct Args {
   const uint16_t *gy, *x, *w;  // ONLOAD: gy is dy, and the tile becomes dx3 from the next three
@@ -145,12 +127,6 @@ struct Args {
   const uint8_t* bits;
   float* dwpart;  // FINAL: fp32 [workgroup][K][C] partials of dW, summed in workgroup order after the kernel
 };
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 // 4 B per lane into LDS at (wave-uniform base + lane * 4): the FINAL form's bits tile, 8-B rows
 __device__ __forceinline__ void glds4(const void* src, void* lds_base) {
@@ -497,9 +473,9 @@ __global__ void __launch_bounds__(THREADS, 1) bwd1x1_fused_kernel(Args a) {
     for (int kk = 0; kk < RS / 32; ++kk) {
       TrRaw ar[KTW], br[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) tr_load<128, false>(br[j], X, j * 16, kk, lane);
+      for (int j = 0; j < 4; ++j) tr_load<128, swz128>(br[j], X, j * 16, kk, lane);
 #pragma unroll
-      for (int i = 0; i < KTW; ++i) tr_load<RB, true>(ar[i], G, wid * KW + i * 16, kk, lane);
+      for (int i = 0; i < KTW; ++i) tr_load<RB, swz_g>(ar[i], G, wid * KW + i * 16, kk, lane);
       K8S_LDS_TIE8("s_waitcnt lgkmcnt(0)", br[0].lo, br[0].hi, br[1].lo, br[1].hi, br[2].lo, br[2].hi, br[3].lo,
                    br[3].hi);
 #pragma unroll

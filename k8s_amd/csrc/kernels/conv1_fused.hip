@@ -39,7 +39,7 @@
 
 #include "common.h"
 #include "launchers.h"
-#include "mfma.h"
+#include "lds_image.h"
 
 namespace k8s_amd {
 namespace c1f {
@@ -51,25 +51,7 @@ constexpr int REPL = kConvStatReplicas;
 
 typedef __attribute__((ext_vector_type(4))) int int4_t;
 
-// (the swizzles and the transposed fragment read of bwd1x1_fused.hip, whose images these are)
-__device__ __forceinline__ int swz128(int r) { return 2 * (((r >> 1) & 1) | (((r >> 3) & 1) << 1)); }
-__device__ __forceinline__ int swz_g(int r) { return (2 * ((r & 3) | (((r >> 3) & 1) << 2))) | ((r >> 2) & 1); }
-
-struct TrRaw {
-  short4_t lo, hi;
-};
-// Transposed fragment of a [32 rows (m)][RB bytes] image: lane l holds column rb + (l & 15), rows 8 (l >> 4) + j
-template <int RB, bool G>
-__device__ __forceinline__ void tr_load(TrRaw& r, const char* img, int rb, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int u = (rb >> 3) + (p >> 1);
-  const int r0 = 8 * g + q, r1 = r0 + 4;
-  const int u0 = u ^ (G ? swz_g(r0) : swz128(r0)), u1 = u ^ (G ? swz_g(r1) : swz128(r1));
-  tr16_asm(r.lo, img + r0 * RB + (u0 << 4) + (p & 1) * 8);
-  tr16_asm(r.hi, img + r1 * RB + (u1 << 4) + (p & 1) * 8);
-}
-#define K8S_C1F_TIE4(w, a, b, c, d) asm volatile(w : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
-
+// (the images are bwd1x1_fused.hip's: lds_image.h holds their swizzles and the transposed fragment read)
 struct Args {
   const uint16_t *dz1, *x1;  // [M][W]: bn1's incoming gradient and input
   const float* params;       // bn1's [sc | B | D | shift], fp32 [4][W]
@@ -85,12 +67,6 @@ struct Args {
   float* dwpart;             // fp32 [walker][W][N]
   int M, ntiles, npairs;
 };
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
 
 //   <64>: 2 x 58 KB ring + 16 KB product tile;  <128>: 2 x 66 KB ring + 16 KB
 template <int W>
@@ -289,14 +265,15 @@ __global__ void __launch_bounds__(THREADS, 1) conv1_fused_kernel(Args a) {
     {
       TrRaw ar[2], br[NJ];
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) tr_load<128, false>(br[j], S + OFF_Z + (j >> 2) * (RS * 128), (j & 3) * 16, lane);
+      for (int j = 0; j < NJ; ++j)
+        tr_load<128, swz128>(br[j], S + OFF_Z + (j >> 2) * (RS * 128), (j & 3) * 16, 0, lane);
 #pragma unroll
-      for (int i = 0; i < 2; ++i) tr_load<512, true>(ar[i], S + OFF_XIN, wid * 32 + i * 16, lane);
+      for (int i = 0; i < 2; ++i) tr_load<512, swz_g>(ar[i], S + OFF_XIN, wid * 32 + i * 16, 0, lane);
 #pragma unroll
       for (int j = 0; j < NJ; j += 4)
         K8S_LDS_TIE8("s_waitcnt lgkmcnt(0)", br[j].lo, br[j].hi, br[j + 1].lo, br[j + 1].hi, br[j + 2].lo, br[j + 2].hi,
                      br[j + 3].lo, br[j + 3].hi);
-      K8S_C1F_TIE4("s_waitcnt lgkmcnt(0)", ar[0].lo, ar[0].hi, ar[1].lo, ar[1].hi);
+      K8S_LDS_TIE4("s_waitcnt lgkmcnt(0)", ar[0].lo, ar[0].hi, ar[1].lo, ar[1].hi);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll

@@ -26,7 +26,7 @@
 
 #include "common.h"
 #include "launchers.h"
-#include "mfma.h"
+#include "lds_image.h"
 
 namespace k8s_amd {
 namespace wgs {
@@ -35,32 +35,9 @@ constexpr int KS = 64;  // rows of the reduction per stage
 
 __device__ __attribute__((aligned(64))) uint16_t g_zero16[64];
 
-__device__ __forceinline__ int swz128(int r) { return 2 * (((r >> 1) & 1) | (((r >> 3) & 1) << 1)); }
-__device__ __forceinline__ int swz256(int r) { return 2 * ((r & 3) | (((r >> 3) & 1) << 2)); }
-
-// Transposed fragment of an [64 rows (m)][W cols] image (W = 64: 128-B rows, W = 128: 256-B rows):
-// lane l holds col rb + (l & 15), rows kk*32 + 8*(l >> 4) + j. Issued as inline asm (tr16_asm: the builtin
-// would make hipcc drain the LDS-DMA ring before every read); ready after the stage's lds tie.
-struct TrRaw {
-  short4_t lo, hi;
-};
+// The [64 rows (m)][W cols] images (lds_image.h) are swizzled by their width: W = 64: 128-B rows, W = 128: 256-B rows
 template <int W>
-__device__ __forceinline__ void tr_load(TrRaw& r, const char* img, int rb, int kk, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  const int u = (rb >> 3) + (p >> 1);
-  const int r0 = kk * 32 + 8 * g + q, r1 = r0 + 4;
-  constexpr int RB = W * 2;
-  int u0, u1;
-  if constexpr (W == 64) {
-    u0 = u ^ swz128(r0);
-    u1 = u ^ swz128(r1);
-  } else {
-    u0 = u ^ swz256(r0);
-    u1 = u ^ swz256(r1);
-  }
-  tr16_asm(r.lo, img + r0 * RB + (u0 << 4) + (p & 1) * 8);
-  tr16_asm(r.hi, img + r1 * RB + (u1 << 4) + (p & 1) * 8);
-}
+constexpr auto swz_of = W == 64 ? swz128 : swz256;
 
 // dy rows: m -> dy + m * K (plain [M][K] matrix), columns k0 .. k0 + W
 struct DySrc {
@@ -180,9 +157,10 @@ __global__ void __launch_bounds__(WK * WC * 64, WK * WC == 8 ? 1 : 2) wgrad_stre
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
-      for (int i = 0; i < RT; ++i) tr_load<KT>(ar[kk * RT + i], st, wk * (KT / WK) + i * 16, kk, lane);
+      for (int i = 0; i < RT; ++i) tr_load<KT * 2, swz_of<KT>>(ar[kk * RT + i], st, wk * (KT / WK) + i * 16, kk, lane);
 #pragma unroll
-      for (int j = 0; j < CTT; ++j) tr_load<CT>(br[kk * CTT + j], st + IMG_A, wc * (CT / WC) + j * 16, kk, lane);
+      for (int j = 0; j < CTT; ++j)
+        tr_load<CT * 2, swz_of<CT>>(br[kk * CTT + j], st + IMG_A, wc * (CT / WC) + j * 16, kk, lane);
     }
     static_assert((2 * RT) % 4 == 0 && (2 * CTT) % 4 == 0, "tie groups of 4");
 #pragma unroll

@@ -31,13 +31,13 @@ class BN(nn.Module):
         self.register_buffer("running_var", torch.ones(c))
         self.momentum, self.eps = 0.1, 1e-5
 
-    def forward(self, x, residual=None, relu=True, res_link=None, dy_link=None, sub2=False, bn3_link=None):
+    def forward(self, x, residual=None, relu=True, res_link=None, dy_link=None, sub2=False, apply_link=None):
         sums = None
         if isinstance(x, tuple):  # (conv output, fused statistics)
             x, sums = x
         return K.batch_norm_act(x, self.gamma, self.beta, self.running_mean, self.running_var, residual, relu,
                                 self.training, self.momentum, self.eps, sums=sums, res_link=res_link,
-                                dy_link=dy_link, sub2=sub2, bn3_link=bn3_link)
+                                dy_link=dy_link, sub2=sub2, apply_link=apply_link)
 
 
 class Conv(nn.Module):
@@ -46,10 +46,10 @@ class Conv(nn.Module):
         self.w = store.new(name + ".weight", (cout, k, k, cin), init_kaiming_normal(cin * k * k))
         self.stride, self.pad = stride, k // 2
 
-    def forward(self, x, grad_link=None, bn3_link=None):
+    def forward(self, x, grad_link=None, apply_link=None):
         # BN statistics are accumulated in the conv epilogue (returned alongside y)
         return K.conv2d_nhwc(x, self.w, self.stride, self.pad, with_stats=True, grad_link=grad_link,
-                             bn3_link=bn3_link)
+                             apply_link=apply_link)
 
 
 class Bottleneck(nn.Module):
@@ -85,34 +85,34 @@ class Bottleneck(nn.Module):
         # then accumulates onto conv1's dx (shared GradLink) instead of zero-filling the 3 parities it never writes
         # ... and where its two BatchNorms run as one (bn_act_dual) and both convolutions can take their half of that
         # backward's apply pass on load (the stage-1 entry block: conv3 and the stride-1 downsample convolution on
-        # the fused 1x1 backward), two Bn3Links join them, so neither dx3 nor the downsample's gradient is written
-        mlink = dn = b3r = None
+        # the fused 1x1 backward), two ApplyLinks join them, so neither dx3 nor the downsample's gradient is written
+        mlink = dn = ar = None
         if self.down is not None:
             mlink = K.MaskLink()
-            b3r = K.Bn3Link() if self.training else None
-            dn = self.down(x, grad_link=dlink, bn3_link=b3r)
+            ar = K.ApplyLink() if self.training else None
+            dn = self.down(x, grad_link=dlink, apply_link=ar)
             # bn3 + downsample BN in one apply pass where the fused kernel applies (ops.nn.bn_act_dual)
             fuse = K.BN_DUAL and isinstance(dn, tuple) and dn[1] is not None and self.training and dn[0].is_cuda
             if not fuse:
                 idn = self.down_bn(dn, relu=False, dy_link=mlink)
         # identity block: bn1's backward apply pass is taken on load by conv1's fused backward where that kernel runs
-        # (ops.nn.Bn3Link, relu form: stages 1 and 2 behind another identity block), so dx1 is never written
-        b1 = K.Bn3Link() if (identity and self.training) else None
-        t = self.conv1(x, grad_link=link or dlink, bn3_link=b1)
+        # (ops.nn.ApplyLink, relu kind: stages 1 and 2 behind another identity block), so dx1 is never written
+        a1 = K.ApplyLink() if (identity and self.training) else None
+        t = self.conv1(x, grad_link=link or dlink, apply_link=a1)
         # bn1 / bn2 + ReLU: normalised on load by the consuming convolution where ops.nn.BN_ONLOAD and its kernels
         # take it (ops.nn.bn_relu_conv: no apply pass, no z tensor), else applied by the BN kernel
-        t = K.bn_relu_conv(t, self.bn1, self.conv2, bn_in_link=b1)
+        t = K.bn_relu_conv(t, self.bn1, self.conv2, in_link=a1)
         # identity block: bn3's backward apply pass is taken on load by conv3's fused backward where that kernel
-        # runs (ops.nn.Bn3Link: stages 1 and 2), so dx3 is never written
-        b3 = K.Bn3Link() if self.training else None
-        t = K.bn_relu_conv(t, self.bn2, self.conv3, bn3_link=b3)
+        # runs (ops.nn.ApplyLink: stages 1 and 2), so dx3 is never written
+        a3 = K.ApplyLink() if self.training else None
+        t = K.bn_relu_conv(t, self.bn2, self.conv3, out_link=a3)
         if dn is not None and fuse:
-            y = K.bn_act_dual(t, self.bn3, dn, self.down_bn, bn3_link=b3, bn3_link_r=b3r)
+            y = K.bn_act_dual(t, self.bn3, dn, self.down_bn, apply_link=a3, apply_link_r=ar)
             if y is not None:
                 return y
             idn = self.down_bn(dn, relu=False, dy_link=mlink)
         return self.bn3(t, residual=idn, relu=True, res_link=link or mlink, sub2=sub2,
-                        bn3_link=b3 if self.down is None else None)
+                        apply_link=a3 if self.down is None else None)
 
 
 class ResNet(nn.Module):

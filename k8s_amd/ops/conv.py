@@ -25,6 +25,7 @@ view; on the GPU they are counted in ``STATS`` and warned about once.
 from __future__ import annotations
 
 import collections
+import functools
 import os
 import warnings
 
@@ -39,19 +40,19 @@ from k8s_amd.ops._ext import load as _load
 
 STATS = {"hip_fwd": 0, "aten_fwd": 0, "hip_wgrad": 0, "aten_wgrad": 0, "hip_dgrad": 0, "aten_dgrad": 0,
          "bn_bstats": 0, "hip_infer": 0, "aten_infer": 0,
-         # a residual BatchNorm that holds a nn.Bn3Link: fused 1x1 backwards that applied its backward on load, and
-         # apply passes (bn_bwd_apply) run for it instead, by its own backward or by the linked convolution's when it
-         # could not take the deferred form
+         # a residual BatchNorm that holds a mask-kind nn.ApplyLink: fused 1x1 backwards that applied its backward on
+         # load, and apply passes (bn_bwd_apply) run for it instead, by its own backward or by the linked
+         # convolution's when it could not take the deferred form
          "bn3_onload": 0, "bn3_apply": 0,
-         # a downsample block's two BatchNorms (nn.bn_act_dual) holding two nn.Bn3Links: backwards that deferred both
-         # apply halves, apply passes run for a deferred half after all, and launches of the fused 1x1 backward's
+         # a downsample block's two BatchNorms (nn.bn_act_dual) holding two dual-kind links: backwards that deferred
+         # both apply halves, apply passes run for a deferred half after all, and launches of the fused 1x1 backward's
          # final form (the downsample convolution's; with or without the downsample BatchNorm's backward on load)
          "dual_onload": 0, "dual_apply": 0, "fused_final": 0,
          # 3x3 forwards on the 4-wave GEMM with gathered A rows (_w4_3x3; counted in hip_fwd as well)
          "w4_3x3_fwd": 0,
-         # an identity block's bn1 that holds a nn.Bn3Link with conv1 (its relu form): bn1 backwards that deferred
-         # their apply pass, apply passes run for bn1 after all (by its own backward, or by conv1's when it could not
-         # take the deferred form), and launches of conv1_fused.hip (conv1's whole backward, bn1's applied on load)
+         # an identity block's bn1 that holds a relu-kind link with conv1: bn1 backwards that deferred their apply
+         # pass, apply passes run for bn1 after all (by its own backward, or by conv1's when it could not take the
+         # deferred form), and launches of conv1_fused.hip (conv1's whole backward, bn1's applied on load)
          "conv1_onload": 0, "conv1_apply": 0, "conv1_fused": 0}
 # data-gradient route name -> times executed. The names name the data gradient's contract (what it accumulates onto,
 # which sums it takes), not the kernel: the fused 1x1 backward's final form is counted under the name _plan_dgrad gives
@@ -60,17 +61,26 @@ STATS = {"hip_fwd": 0, "aten_fwd": 0, "hip_wgrad": 0, "aten_wgrad": 0, "hip_dgra
 ROUTES = collections.Counter()
 
 
-def dual_onload_on() -> bool:
-    """K8S_AMD_DUAL_ONLOAD=0 (read per call: A/B, tests): a downsample block's two BatchNorms run their dual apply
-    pass and its downsample convolution's backward stays on its two kernels. K8S_AMD_BN3_ONLOAD=0 and
-    K8S_AMD_BWD1X1_FUSED=0 switch it off as well."""
-    return all(os.environ.get(k, "1") != "0"
-               for k in ("K8S_AMD_DUAL_ONLOAD", "K8S_AMD_BN3_ONLOAD", "K8S_AMD_BWD1X1_FUSED"))
+# The fused backwards' switches (NAME=0 switches off; read per call: A/B, tests), each with the switch it needs on as
+# well -- the hierarchy, stated here only:
+#   K8S_AMD_BWD1X1_FUSED  off: a normalize-on-load 1x1 convolution's two gradients stay on their two kernels
+#   K8S_AMD_BN3_ONLOAD    off: a residual BatchNorm always runs its own apply pass
+#   K8S_AMD_DUAL_ONLOAD   off: a downsample block's two BatchNorms run their dual apply pass, its downsample
+#                         convolution's backward stays on its two kernels
+#   K8S_AMD_CONV1_FUSED   off: an identity block's bn1 runs its own apply pass, conv1's backward stays on its two
+#                         kernels (gemm_short's masked-addend data gradient, the streaming weight gradient)
+_SWITCH_NEEDS = {"K8S_AMD_BWD1X1_FUSED": None, "K8S_AMD_BN3_ONLOAD": "K8S_AMD_BWD1X1_FUSED",
+                 "K8S_AMD_DUAL_ONLOAD": "K8S_AMD_BN3_ONLOAD", "K8S_AMD_CONV1_FUSED": None}
 
-def conv1_fused_on() -> bool:
-    """K8S_AMD_CONV1_FUSED=0 (read per call: A/B, tests): an identity block's bn1 runs its own apply pass and conv1's
-    backward stays on its two kernels (gemm_short's masked-addend data gradient, the streaming weight gradient)."""
-    return os.environ.get("K8S_AMD_CONV1_FUSED", "1") != "0"
+
+def _switch_on(name) -> bool:
+    return name is None or (os.environ.get(name, "1") != "0" and _switch_on(_SWITCH_NEEDS[name]))
+
+
+bwd1x1_fused_on = functools.partial(_switch_on, "K8S_AMD_BWD1X1_FUSED")
+bn3_onload_on = functools.partial(_switch_on, "K8S_AMD_BN3_ONLOAD")
+dual_onload_on = functools.partial(_switch_on, "K8S_AMD_DUAL_ONLOAD")
+conv1_fused_on = functools.partial(_switch_on, "K8S_AMD_CONV1_FUSED")
 
 
 # (Round 5 built weight gradients on a second HIP stream -- each conv's dW kernel forked off the compute stream to
@@ -429,45 +439,71 @@ def conv1_fused_shape_ok(C_, M, K, C) -> bool:
     return ok is not None and bool(ok(M, K, C))
 
 
-def _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok=True, bn1=None):
-    """Which family forms a convolution backward's data gradient: "conv1_fused" (below), "fused_1x1" (both gradients
-    and the input BatchNorm + ReLU's backward sums in one pass over gy and x, bwd1x1_fused.hip), "fused_final" (the same
-    kernel's final form), "stride1" (``_plan_dgrad``), "strided" (``_plan_dgrad_strided``) or "aten". Launches and
-    allocates nothing. K8S_AMD_BWD1X1_FUSED=0 (read per call: A/B, tests) keeps a normalize-on-load 1x1 convolution's
-    two gradients on their two kernels. The fused family is one route, "fused_1x1", in both of its forms; the launches
-    that also apply the output BatchNorm's backward on load (``conv_bwd``'s ``bn3``) are counted in
-    ``STATS["bn3_onload"]``.
-    "conv1_fused": ``bn1`` is the filled relu-form ``nn.Bn3Link`` of the BatchNorm + ReLU that reads a (C, K) =
-    (256, 64) or (512, 128) 1x1 convolution's output -- ``gy`` is that BatchNorm's incoming gradient, its apply pass
-    deferred -- and the data gradient takes a masked addend and a mask-kind link's sums (an identity bottleneck's conv1
-    in ResNet's stages 1-2, after another identity block): both gradients, the sums and the BatchNorm's apply in one
-    pass (conv1_fused.hip), the contract of ``_plan_dgrad``'s "short_mask_sums" for the data gradient.
-    ``conv1_fused_on()`` switches it.
-    "fused_final": a (C, K) = (64, 256) 1x1 convolution reading a stored x (no xform) whose data gradient is the
-    second into x -- it accumulates onto the contiguous tensor ``addend`` -- and takes the sums of a pool-kind link
-    covering x (ResNet's stage-1 downsample convolution): both gradients and the sums in one pass, the contract of
-    ``_plan_dgrad``'s "tile_final_sums" for the data gradient. ``dw_ok``: the weight gradient is still to be formed,
-    into an fp32 slot. ``dual_onload_on()`` switches it."""
+def fused_candidate(C_, x, w, stride, padding, x_kind, slot_ok, onload):
+    """The forward-known half of the fused backward families' contracts, written once for the forward's offer
+    (``offer_family``) and for ``_plan_bwd``: the one family this convolution's backward can be, else None. A
+    contiguous x into a 1x1 / stride-1 / pad-0 filter, ``x_kind`` the ``_link_kind`` of the BnStatLink on x, and
+      "fused_1x1"    x normalised on load (``onload``), a relu-kind link, ``bwd1x1_fused_ok``
+      "fused_final"  a stored x, a pool-kind link, ``bwd1x1_final_ok``    } bf16 GPU operands, dw into the parameter's
+      "conv1_fused"  a stored x, a mask-kind link, ``conv1_fused_ok``     } fp32 slot, x not subsampled (``slot_ok``)"""
     K, R, S, C = w.shape
-    if (bn1 is not None and bn1.mask is None and bn1.covers(gy) and xform is None and dw_ok and addend is not None
-            and not torch.is_tensor(addend) and R == 1 and S == 1 and stride == 1 and padding == 0 and conv1_fused_on()
-            and _link_kind(bn_link, x.shape) == "mask" and _hip(gy, x, w, addend.dy) and gy.is_contiguous()
-            and x.is_contiguous() and addend.dy.is_contiguous() and addend.dy.shape == x.shape
-            and bn1.x3.shape == gy.shape and conv1_fused_shape_ok(C_, gy.numel() // K, K, C)
-            # ... and only where the parent's route takes the sums in its epilogue ("short_mask_sums": the switches
-            # that turn those sums off turn this route off with them)
-            and C_.gemm_short_bnstats_ok(gy.numel() // K, C, K, False)):
-        return "conv1_fused"
-    if (xform is None and dw_ok and torch.is_tensor(addend) and addend.is_contiguous() and addend.shape == x.shape
-            and R == 1 and S == 1 and stride == 1 and padding == 0 and dual_onload_on()
-            and _link_kind(bn_link, x.shape) == "pool" and _hip(gy, x, w, addend) and gy.is_contiguous()
-            and x.is_contiguous() and C_.bwd1x1_final_ok(gy.numel() // K, C, K)):
+    if not (R == 1 and S == 1 and stride == 1 and padding == 0 and x.is_contiguous()):
+        return None
+    M = x.numel() // C
+    if onload:
+        return "fused_1x1" if x_kind == "relu" and C_.bwd1x1_fused_ok(M, C, K) else None
+    if not (slot_ok and _hip(x, w)):
+        return None
+    if x_kind == "pool" and C_.bwd1x1_final_ok(M, C, K):
         return "fused_final"
-    if (xform is not None and addend is None and R == 1 and S == 1 and stride == 1 and padding == 0
-            and os.environ.get("K8S_AMD_BWD1X1_FUSED", "1") != "0" and _link_kind(bn_link, x.shape) == "relu"
-            and bn_link.x.data_ptr() == x.data_ptr() and gy.is_contiguous() and x.is_contiguous()
-            and C_.bwd1x1_fused_ok(gy.numel() // K, C, K)):
-        return "fused_1x1"
+    if x_kind == "mask" and conv1_fused_shape_ok(C_, M, K, C):
+        return "conv1_fused"
+    return None
+
+
+def offer_family(C_, x, w, stride, padding, x_kind, slot_ok, onload=False, grad_link=None):
+    """The forward's question: the fused family this convolution's backward will be as far as it can know, so that
+    it may offer to take the apply pass of the BatchNorm reading its output (``nn.ApplyLink``), else None:
+    ``fused_candidate`` plus what only the forward sees -- which reader of x this is (``grad_link``: "fused_final" is
+    one of two on a shared link, "conv1_fused" gets a residual gradient on a link of its own), that x wants a
+    gradient, and for the final form ``dual_onload_on()`` as of now."""
+    family = fused_candidate(C_, x, w, stride, padding, x_kind, slot_ok, onload)
+    if family == "fused_final":
+        return family if grad_link is not None and grad_link.shared and x.requires_grad and dual_onload_on() else None
+    if family == "conv1_fused":
+        return family if grad_link is not None and not grad_link.shared and x.requires_grad else None
+    return family
+
+
+def _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok=True, apply_link=None):
+    """Which family forms a convolution backward's data gradient: a fused one, "stride1" (``_plan_dgrad``), "strided"
+    (``_plan_dgrad_strided``) or "aten". Launches and allocates nothing. A fused family is ``fused_candidate``'s
+    (``dw_ok``: the weight gradient is still to be formed, into an fp32 slot) where the backward's own facts hold too:
+      "fused_1x1"    both gradients and the input BatchNorm + ReLU's backward sums in one pass over gy and x
+                     (bwd1x1_fused.hip): no addend, the relu-kind link filled for this very x; ``bwd1x1_fused_on()``
+      "fused_final"  that kernel's final form, the second data gradient into x (ResNet's stage-1 downsample
+                     convolution): it accumulates onto the contiguous tensor ``addend`` and takes the pool-kind link's
+                     sums, the contract of ``_plan_dgrad``'s "tile_final_sums"; ``dual_onload_on()``
+      "conv1_fused"  both gradients, a mask-kind link's sums and the apply pass of the BatchNorm + ReLU reading the
+                     output (conv1_fused.hip; an identity bottleneck's conv1 in stages 1-2 behind another identity
+                     block): ``apply_link`` is that BatchNorm's relu-kind ``nn.ApplyLink`` covering ``gy``, the addend
+                     masked, and the data gradient's own route takes the sums ("short_mask_sums": the switches that
+                     turn those sums off turn this family off with them); ``conv1_fused_on()``
+    The first two also apply a mask- or dual-kind link on load, which is ``conv_bwd``'s to decide."""
+    K, R, S, C = w.shape
+    family = fused_candidate(C_, x, w, stride, padding, _link_kind(bn_link, x.shape), dw_ok, xform is not None)
+    masked = addend is not None and not torch.is_tensor(addend)
+    if (family == "conv1_fused" and apply_link is not None and apply_link.kind == "relu" and apply_link.covers(gy)
+            and masked and conv1_fused_on() and _hip(gy, addend.dy) and gy.is_contiguous()
+            and addend.dy.is_contiguous() and addend.dy.shape == x.shape and apply_link.x.shape == gy.shape
+            and C_.gemm_short_bnstats_ok(x.numel() // C, C, K, False)):
+        return family
+    if (family == "fused_final" and torch.is_tensor(addend) and addend.is_contiguous() and addend.shape == x.shape
+            and dual_onload_on() and _hip(gy, addend) and gy.is_contiguous()):
+        return family
+    if (family == "fused_1x1" and addend is None and bwd1x1_fused_on() and bn_link.x.data_ptr() == x.data_ptr()
+            and gy.is_contiguous()):
+        return family
     if _hip(gy, x, w) and stride == 1 and K % 8 == 0 and C % 8 == 0:
         return "stride1"
     if _hip(gy, x, w) and strided_dgrad_ok(gy, w, stride, padding):
@@ -488,86 +524,80 @@ def _finish_dw(p, gy, x, w, stride, padding):
         p.store.deposit(p, dw)
 
 
-def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None, x_sub=None, bn_link=None, bn3=None):
+def _fused_bwd(C_, family, gy, x, w, padding, addend, xform, ln, p, apply_link):
+    """A fused family's one launch: dw into ``p``'s slot, the data gradient with the sums of the BnStatLink ``ln``
+    deposited, and ``apply_link``'s BatchNorm backward applied as gy is loaded. Returns the data gradient."""
+    K, _, _, C = w.shape
+    STATS["hip_wgrad"] += 1
+    STATS["hip_dgrad"] += 1
+    sums = _bn_sums(C_, ln, C, gy.device)
+    gy2, x2, w2, dw = gy.view(-1, K), x.view(-1, C), w.view(K, C), p.grad.view(K, C)
+    onload = {} if apply_link is None else {"x3": apply_link.x.view(-1, K), "mask": apply_link.mask,
+                                            "params": apply_link.params}
+    if family == "conv1_fused":
+        ROUTES[_plan_dgrad(C_, gy, w, padding, addend, ln)] += 1  # the data gradient's contract: short_mask_sums
+        STATS["conv1_fused"] += 1
+        dx = C_.conv1_fused(gy2, onload["x3"], onload["params"], w2, x2, addend.dy.view(-1, C), addend.mask,
+                            ln.x.view(-1, C), ln.mask, ln.mean, sums, dw, p.written).view(x.shape)
+    elif family == "fused_final":
+        ROUTES[_plan_dgrad(C_, gy, w, padding, addend, ln)] += 1  # the data gradient's contract: tile_final_sums
+        STATS["fused_final"] += 1
+        C_.bwd1x1_fused(gy2, x2, w2, None, None, None, None, None, dw, sums, p.written, addend=addend.view(-1, C),
+                        winner_x=ln.x.view(-1, C), winner_bits=ln.mask.view(-1), winner_mean=ln.mean, **onload)
+        dx = addend
+    else:
+        ROUTES[family] += 1
+        STATS["bn3_onload"] += apply_link is not None
+        dx = C_.bwd1x1_fused(gy2, x2, w2, xform, ln.gamma, ln.beta, ln.mean, ln.invstd, dw, sums, p.written,
+                             **onload).view(x.shape)
+    _slot_written(p)
+    ln.deposit(sums, None, dx)
+    return dx
+
+
+def conv_bwd(gy, x, w, stride, padding, need_dx, p=None, addend=None, xform=None, x_sub=None, bn_link=None,
+             apply_link=None):
     """Returns dx (+ ``addend``, e.g. the residual branch's gradient of the same tensor, fused into the
     dgrad epilogue where our kernel runs) or None; deposits dw into ``p``'s flat gradient slot. ``xform``: the
     convolution's input is relu(bn(x)) normalised on load (see ``_wgrad_hip``); dx is then the gradient w.r.t.
     that normalised input. ``x_sub``: a 1x1 / pad-0 convolution's input already subsampled by its stride
     (``nn._Conv2dNHWC`` with ``subsample_ok``): the weight gradient runs as the stride-1 product on it; ``x`` then only gives dx's shape.
-    ``bn3``: a filled ``nn.Bn3Link`` -- the residual BatchNorm that read this convolution's output deferred its apply
-    pass, so ``gy`` may be that BatchNorm's incoming dy and not yet the gradient of the output. The fused 1x1 family,
-    in either form, applies it on load when the link covers ``gy`` (``STATS["bn3_onload"]`` / ``["fused_final"]``);
-    in every other case the apply pass runs here first, on the ``gy`` received (``STATS["bn3_apply"]``, or
-    ``["dual_apply"]`` for a half of a downsample block's two BatchNorms). A relu-form link (no mask: the BatchNorm +
-    ReLU behind an identity block's conv1, which this convolution's OUTPUT feeds) is taken only by the "conv1_fused"
-    family (``STATS["conv1_fused"]``); else its apply pass runs here first (``["conv1_apply"]``)."""
+    ``apply_link``: a filled ``nn.ApplyLink`` -- the BatchNorm that read this convolution's output deferred its apply
+    pass, so ``gy`` is that BatchNorm's incoming dy and not yet the gradient of the output. The link is kept, and
+    applied as the kernel loads gy, when the planned family is one its kind can go to (``nn.APPLY_KINDS``) and it
+    covers ``gy``; in every other case the apply pass runs here first, on the ``gy`` received, counted under the
+    kind's ``apply_stat``."""
+    from k8s_amd.ops.nn import APPLY_KINDS
+
     K, R, S, C = w.shape
     C_ = _load() if gy.is_cuda else None
     dw_ok = p is not None and x_sub is None and p.grad.dtype == torch.float32
-    bn1 = None
-    if bn3 is not None and bn3.mask is None:
-        bn1, bn3 = bn3, None
-        if not (need_dx and _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok, bn1)
-                == "conv1_fused"):
-            STATS["conv1_apply"] += 1
-            gy = C_.bn_bwd_apply(gy.contiguous(), bn1.x3, None, bn1.params)
-            bn1 = None
-    if bn3 is not None and not (need_dx and bn3.covers(gy)
-                                and _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok)
-                                in ("fused_1x1", "fused_final")):
-        STATS["dual_apply" if bn3.dual else "bn3_apply"] += 1
-        gy = C_.bn_bwd_apply(gy.contiguous(), bn3.x3, bn3.mask, bn3.params)
-        bn3 = None
+    hip = _hip(gy, x, w)
+    if addend is not None and not torch.is_tensor(addend) and not (
+            hip and stride == 1 and K % 8 == 0 and C % 8 == 0):
+        addend = addend.materialize()  # only the stride-1 dgrad on our kernels takes the (dy, mask) pair
+
+    def plan():
+        return _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok, apply_link) if need_dx else None
+
+    family = plan()
+    if apply_link is not None:
+        kind = APPLY_KINDS[apply_link.kind]
+        if not (family in kind.families and apply_link.covers(gy)):
+            STATS[kind.apply_stat] += 1
+            gy = C_.bn_bwd_apply(gy.contiguous(), apply_link.x, apply_link.mask, apply_link.params)
+            apply_link = None
+            family = plan()
     if x_sub is not None:
         _wgrad_hip(C_, gy, x_sub, p.grad.view(p.shape), 1, 0, p.written)
         STATS["hip_wgrad"] += 1
         _slot_written(p)
         p = None  # done
-    hip = _hip(gy, x, w)
     if xform is not None and not (hip and C % 64 == 0 and K % 8 == 0 and p is not None
                                   and p.grad.dtype == torch.float32):
         raise RuntimeError("normalize-on-load weight gradient outside the kernels' contract")
-    if addend is not None and not torch.is_tensor(addend) and not (
-            hip and stride == 1 and K % 8 == 0 and C % 8 == 0):
-        addend = addend.materialize()  # only the stride-1 dgrad on our kernels takes the (dy, mask) pair
-    family = _plan_bwd(C_, gy, x, w, stride, padding, addend, xform, bn_link, dw_ok, bn1) if need_dx else None
-    if family == "conv1_fused":
-        ROUTES[_plan_dgrad(C_, gy, w, padding, addend, bn_link)] += 1  # the data gradient's contract: short_mask_sums
-        STATS["conv1_fused"] += 1
-        STATS["hip_wgrad"] += 1
-        STATS["hip_dgrad"] += 1
-        sums = _bn_sums(C_, bn_link, C, gy.device)
-        dx = C_.conv1_fused(gy.view(-1, K), bn1.x3.view(-1, K), bn1.params, w.view(K, C), x.view(-1, C),
-                            addend.dy.view(-1, C), addend.mask, bn_link.x.view(-1, C), bn_link.mask, bn_link.mean,
-                            sums, p.grad.view(K, C), p.written).view(x.shape)
-        _slot_written(p)
-        bn_link.deposit(sums, None, dx)
-        return dx
-    if family == "fused_final":
-        ROUTES[_plan_dgrad(C_, gy, w, padding, addend, bn_link)] += 1  # the data gradient's contract: tile_final_sums
-        STATS["fused_final"] += 1
-        STATS["hip_wgrad"] += 1
-        STATS["hip_dgrad"] += 1
-        sums = _bn_sums(C_, bn_link, C, gy.device)
-        onload = {} if bn3 is None else {"x3": bn3.x3.view(-1, K), "mask": bn3.mask, "params": bn3.params}
-        C_.bwd1x1_fused(gy.view(-1, K), x.view(-1, C), w.view(K, C), None, None, None, None, None, p.grad.view(K, C),
-                        sums, p.written, addend=addend.view(-1, C), winner_x=bn_link.x.view(-1, C),
-                        winner_bits=bn_link.mask.view(-1), winner_mean=bn_link.mean, **onload)
-        _slot_written(p)
-        bn_link.deposit(sums, None, addend)
-        return addend
-    if family == "fused_1x1":
-        ROUTES[family] += 1
-        STATS["bn3_onload"] += bn3 is not None
-        STATS["hip_wgrad"] += 1
-        STATS["hip_dgrad"] += 1
-        sums = _bn_sums(C_, bn_link, C, gy.device)
-        onload = {} if bn3 is None else {"x3": bn3.x3.view(-1, K), "mask": bn3.mask, "params": bn3.params}
-        dz = C_.bwd1x1_fused(gy.view(-1, K), x.view(-1, C), w.view(K, C), xform, bn_link.gamma, bn_link.beta,
-                             bn_link.mean, bn_link.invstd, p.grad.view(K, C), sums, p.written, **onload).view(x.shape)
-        _slot_written(p)
-        bn_link.deposit(sums, None, dz)
-        return dz
+    if family in ("fused_1x1", "fused_final", "conv1_fused"):
+        return _fused_bwd(C_, family, gy, x, w, padding, addend, xform, bn_link, p, apply_link)
     # ---- weight gradient
     if hip and C % 8 == 0 and K % 8 == 0 and p is not None and p.grad.dtype == torch.float32:
         STATS["hip_wgrad"] += 1

@@ -11,6 +11,7 @@ conv weights are KRSC ``[K, R, S, C]``; linear weights ``[out, in]``.
 """
 from __future__ import annotations
 
+import collections
 import os
 from typing import Optional
 
@@ -19,6 +20,7 @@ import torch.nn.functional as F
 
 from k8s_amd.ops import reference as ref
 from k8s_amd.ops._ext import load as _load_ext
+from k8s_amd.ops.conv import bn3_onload_on, conv1_fused_on, dual_onload_on  # the deferrals' switches (APPLY_KINDS)
 
 
 def _gpu(t: torch.Tensor) -> bool:
@@ -107,6 +109,13 @@ class MaskedGrad:
         return _C().mask_apply(self.dy, self.mask)
 
 
+def _tensor_key(t):
+    """The identity of a tensor as a link recorded it (BnStatLink: the data gradient a deposit's sums were taken over;
+    ApplyLink: the dy a deferred apply pass belongs to): an in-place add keeps the pointer and the shape, so the
+    version counter is part of it."""
+    return t.data_ptr(), tuple(t.shape), t._version
+
+
 class BnStatLink:
     """Joins a BatchNorm to the convolution(s) that read its output y: a data gradient into y -- the whole gradient of
     y -- also accumulates the BatchNorm-backward sums (sum g, sum g (x - mean), g = dy where the ReLU passed) in its
@@ -154,16 +163,10 @@ class BnStatLink:
     def fill_pool(self, x, mask, mean, store=None):
         self._fill("pool", store, x, mean, mask)
 
-    @staticmethod
-    def _key(t):
-        """The identity of the tensor a deposit's sums were taken over: an in-place add keeps the pointer and the
-        shape, so the version counter is part of it."""
-        return t.data_ptr(), tuple(t.shape), t._version
-
     def deposit(self, sums, sums2, over):
         """The convolution's backward hands over the sums (``sums2``: the second BatchNorm's, or None) taken over the
         data gradient ``over``."""
-        self.sums, self.sums2, self.dy_key = sums, sums2, self._key(over)
+        self.sums, self.sums2, self.dy_key = sums, sums2, _tensor_key(over)
         _conv_impl().STATS["bn_bstats"] += 1
 
     def deposit_pending(self, sums):
@@ -173,7 +176,7 @@ class BnStatLink:
 
     def complete(self, over):
         """The second data gradient corrected the pending sums: they now hold for the final tensor ``over``."""
-        self.dy_key, self.pending = self._key(over), False
+        self.dy_key, self.pending = _tensor_key(over), False
 
     def drop_pending(self):
         """No data gradient can complete the pending sums: the BatchNorm takes its own reduction."""
@@ -181,7 +184,7 @@ class BnStatLink:
 
     def covers(self, t) -> bool:
         """Whether a completed deposit's sums were taken over ``t`` as it is now."""
-        return self.sums is not None and self.dy_key == self._key(t)
+        return self.sums is not None and self.dy_key == _tensor_key(t)
 
     def take(self, dy):
         """(sums, sums2) if they were taken over ``dy``, else None; clears the link either way (the BatchNorm's
@@ -209,64 +212,75 @@ class MaskLink:
         self.mask = None
 
 
-def bn3_onload_on() -> bool:
-    """K8S_AMD_BN3_ONLOAD=0 (read per call: A/B, tests): a residual BatchNorm always runs its own apply pass."""
-    return os.environ.get("K8S_AMD_BN3_ONLOAD", "1") != "0" and os.environ.get("K8S_AMD_BWD1X1_FUSED", "1") != "0"
+class ApplyLink:
+    """Hands a BatchNorm's deferred backward apply pass to the convolution that produced the BatchNorm's input x
+    (``conv2d_nhwc(..., apply_link=l)`` or ``bn_relu_conv(..., out_link=l)``, then ``batch_norm_act(x, ...,
+    apply_link=l)``), x having no other reader. dx = sc * g + B * x + D (g: dy where the ReLU passed) has one reader,
+    that convolution's backward, which on a fused kernel can form it tile by tile as it loads dy. So where the
+    convolution said in its forward that it can (``offer``; ``ops.conv.offer_family``), the BatchNorm's backward runs
+    only its first half -- dgamma, dbeta and the [sc | B | D] table -- leaves (x, mask, params) and the identity of dy
+    here (one ``fill_*`` per kind) and returns dy itself as x's gradient: no apply pass, no dx tensor. The
+    convolution's backward takes the link (``take``) and hands it to ``ops.conv.conv_bwd``, which applies the table on
+    load if the gradient it received is that dy, unchanged (``covers``), and the family it planned is one of the
+    kind's (``APPLY_KINDS``); otherwise it runs the apply pass on what it received.
 
-
-class Bn3Link:
-    """Joins a residual BatchNorm (a bottleneck's bn3) to the normalize-on-load 1x1 convolution that produced its
-    input x3 (``bn_relu_conv(t, bn2, conv3, bn3_link=l)`` then ``batch_norm_act(x3, ..., bn3_link=l)``), x3 having no
-    other reader. dx3 = sc * (mask ? dy : 0) + B * x3 + D has one reader, that convolution's backward, which on the
-    fused kernel (bwd1x1_fused.hip) can form it tile by tile as it loads dy. So where the convolution said in its
-    forward that it can (``offer``), the BatchNorm's backward runs only its first half -- dgamma, dbeta and the
-    [sc | B | D] table -- leaves (x3, mask, params) and the identity of dy here (``fill``) and returns dy itself as
-    x3's gradient: no apply pass, no dx3 tensor. The convolution's backward takes the link (``take``) and hands it to
-    ``ops.conv.conv_bwd``, which applies the table on load if the gradient it received is that dy, unchanged
-    (``covers``), and otherwise runs the apply pass on what it received.
-
-    A stage-1 entry block holds two: one joins bn3 to conv3 as above, the other the downsample BatchNorm to the
-    downsample convolution (``conv2d_nhwc(..., bn3_link=l)``, whose backward is then the fused kernel's final form),
-    both BatchNorms running as one (``bn_act_dual(..., bn3_link=, bn3_link_r=)``). That backward defers both halves or
-    neither (``dual``: which counter an apply pass run for the link after all is counted in).
-
-    The relu form joins an identity block's bn1 (BatchNorm + ReLU, no residual, no stored mask: ``mask`` stays None
-    and the ReLU decision is recomputed from x) to conv1, which produced its input x1
-    (``conv2d_nhwc(x, conv1, bn3_link=l)`` then ``batch_norm_act(x1, ..., bn3_link=l)``): conv1's backward on
-    conv1_fused.hip forms dx1 from bn1's incoming gradient, x1 and the table as it loads them
-    (``ops.conv._plan_bwd`` "conv1_fused"), or runs the apply pass on what it received."""
-    __slots__ = ("y_key", "x3", "mask", "params", "dy_key", "dual")
+    Kinds:
+      mask  a residual BatchNorm with a packed ReLU mask: a bottleneck's bn3 to its normalize-on-load conv3
+            (bwd1x1_fused.hip)
+      dual  one half of a downsample block's two BatchNorms running as one (``bn_act_dual(..., apply_link=,
+            apply_link_r=)``): a stage-1 entry block holds two, bn3 to conv3 and the downsample BatchNorm to the
+            downsample convolution (the fused kernel's final form). That backward defers both halves or neither.
+      relu  a BatchNorm + ReLU without residual or stored mask (``mask`` is None, the ReLU decision is recomputed
+            from x): an identity block's bn1 to conv1 (conv1_fused.hip)"""
+    __slots__ = ("y_key", "kind", "x", "mask", "params", "dy_key")
 
     def __init__(self):
-        self.y_key = self.x3 = self.mask = self.params = self.dy_key = None
-        self.dual = False
+        self.y_key = self.kind = self.x = self.mask = self.params = self.dy_key = None
 
     def offer(self, y):
-        """The convolution's forward: its backward will be the fused family's for an output of this shape."""
+        """The convolution's forward: its backward will be a fused family's for an output of this shape."""
         self.y_key = (y.data_ptr(), tuple(y.shape))
 
     def offered(self, x) -> bool:
         return self.y_key == (x.data_ptr(), tuple(x.shape))
 
-    def fill(self, dy, x3, mask, params, dual=False):
-        self.x3, self.mask, self.params, self.dy_key, self.dual = x3, mask, params, BnStatLink._key(dy), dual
+    def _fill(self, kind, dy, x, mask, params):
+        self.kind, self.x, self.mask, self.params, self.dy_key = kind, x, mask, params, _tensor_key(dy)
+
+    def fill_mask(self, dy, x, mask, params):
+        self._fill("mask", dy, x, mask, params)
+
+    def fill_dual(self, dy, x, mask, params):
+        self._fill("dual", dy, x, mask, params)
+
+    def fill_relu(self, dy, x, params):
+        self._fill("relu", dy, x, None, params)
 
     def covers(self, t) -> bool:
-        return self.dy_key == BnStatLink._key(t)
+        return self.dy_key == _tensor_key(t)
 
     def take(self):
         """The filled link's content as a link of its own (None if the BatchNorm did not defer); clears this one."""
-        if self.params is None:
+        if self.kind is None:
             return None
-        out = Bn3Link()
-        out.x3, out.mask, out.params, out.dy_key, out.dual = self.x3, self.mask, self.params, self.dy_key, self.dual
-        self.x3 = self.mask = self.params = self.dy_key = None
+        out = ApplyLink()
+        out.kind, out.x, out.mask, out.params, out.dy_key = self.kind, self.x, self.mask, self.params, self.dy_key
+        self.kind = self.x = self.mask = self.params = self.dy_key = None
         return out
+
+
+# Per ApplyLink kind: the families of ops.conv._plan_bwd that apply the link as they load dy, the ops.conv.STATS key
+# an apply pass run for the link after all is counted under, and the switch (read per call) under which the
+# BatchNorm's backward defers.
+ApplyKind = collections.namedtuple("ApplyKind", "families apply_stat defer_on")
+APPLY_KINDS = {"mask": ApplyKind(("fused_1x1", "fused_final"), "bn3_apply", bn3_onload_on),
+               "dual": ApplyKind(("fused_1x1", "fused_final"), "dual_apply", dual_onload_on),
+               "relu": ApplyKind(("conv1_fused",), "conv1_apply", conv1_fused_on)}
 
 
 class _Conv2dNHWC(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, anchor, p, stride, padding, with_stats, link=None, bn_link=None, bn3_link=None):
+    def forward(ctx, x, anchor, p, stride, padding, with_stats, link=None, bn_link=None, apply_link=None):
         impl = _conv_impl()
         w = p.weight if x.dtype == p.weight.dtype else p.master.to(x.dtype)
         sums = None
@@ -284,28 +298,15 @@ class _Conv2dNHWC(torch.autograd.Function):
         ctx.save_for_backward(x, xs)
         ctx.p, ctx.stride, ctx.padding, ctx.link, ctx.bn_link = p, stride, padding, link, bn_link
         ctx.x_requires_grad = x.requires_grad
-        # the backward will be the fused kernel's final form (ops.conv._plan_bwd "fused_final", but for what only the
-        # backward knows: which of x's two readers runs second): it can take the output BatchNorm's apply pass
-        ctx.bn3_link = None
-        K_, R, S, C = w.shape
-        if (bn3_link is not None and BN_BSTATS and R == 1 and S == 1 and stride == 1 and padding == 0 and xs is None
-                and link is not None and link.shared and x.requires_grad and x.is_contiguous()
-                and bn_link is not None and bn_link.kind == "pool" and bn_link.x.shape == x.shape
-                and impl._hip(x, w) and impl.dual_onload_on() and p.grad.dtype == torch.float32
-                and _C().bwd1x1_final_ok(x.numel() // C, C, K_)):
-            bn3_link.offer(y)
-            ctx.bn3_link = bn3_link
-        # an identity block's conv1 in the shapes of conv1_fused.hip, behind another identity block (a mask-kind link
-        # on x, the residual gradient arriving through a GradLink of its own): its backward can take the apply pass of
-        # the BatchNorm + ReLU that reads y (Bn3Link, relu form). What only the backward knows -- the addend's form,
-        # the switch -- is checked there (ops.conv._plan_bwd "conv1_fused").
-        if (bn3_link is not None and ctx.bn3_link is None and BN_BSTATS and R == 1 and S == 1 and stride == 1
-                and padding == 0 and xs is None and link is not None and not link.shared and x.requires_grad
-                and x.is_contiguous() and bn_link is not None and bn_link.kind == "mask"
-                and bn_link.x.shape == x.shape and impl._hip(x, w) and p.grad.dtype == torch.float32
-                and impl.conv1_fused_shape_ok(_C(), x.numel() // C, K_, C)):
-            bn3_link.offer(y)
-            ctx.bn3_link = bn3_link
+        # the backward will be a fused family's as far as the forward knows (the stage-1 downsample convolution: the
+        # fused kernel's final form; an identity block's conv1 behind another identity block: conv1_fused.hip): it
+        # can take the apply pass of the BatchNorm that reads y (ApplyLink)
+        ctx.apply_link = None
+        if (apply_link is not None and BN_BSTATS and impl.offer_family(
+                _C() if _gpu(x) else None, x, w, stride, padding, impl._link_kind(bn_link, x.shape),
+                xs is None and p.grad.dtype == torch.float32, grad_link=link)):
+            apply_link.offer(y)
+            ctx.apply_link = apply_link
         if sums is not None:
             ctx.mark_non_differentiable(sums)
         # the statistics output never gets a gradient: without this autograd materialises a zeros_like(sums) for
@@ -320,30 +321,31 @@ class _Conv2dNHWC(torch.autograd.Function):
         impl = _conv_impl()
         w = p.weight if x.dtype == p.weight.dtype else p.master.to(x.dtype)
         gy = gy.contiguous()
-        bn3 = ctx.bn3_link.take() if ctx.bn3_link is not None else None
+        deferred = ctx.apply_link.take() if ctx.apply_link is not None else None
         addend = None
         if ctx.link is not None:
             addend, ctx.link.grad = ctx.link.grad, None
             if addend is None and ctx.link.shared and ctx.x_requires_grad:  # first of the two readers of x
                 ctx.link.grad = impl.conv_bwd(gy, x, w, ctx.stride, ctx.padding, True, p, x_sub=xs,
-                                              bn_link=ctx.bn_link, bn3=bn3)
+                                              bn_link=ctx.bn_link, apply_link=deferred)
                 return None, None, None, None, None, None, None, None, None
         dx = impl.conv_bwd(gy, x, w, ctx.stride, ctx.padding, ctx.x_requires_grad, p, addend=addend, x_sub=xs,
-                           bn_link=ctx.bn_link, bn3=bn3)
+                           bn_link=ctx.bn_link, apply_link=deferred)
         return dx, None, None, None, None, None, None, None, None
 
 
 def conv2d_nhwc(x: torch.Tensor, p, stride: int = 1, padding: int = 0, with_stats: bool = False,
-                grad_link: "GradLink" = None, bn3_link: "Bn3Link" = None):
+                grad_link: "GradLink" = None, apply_link: "ApplyLink" = None):
     """NHWC convolution with KRSC weight ``p`` (no bias).
 
     With ``with_stats`` returns ``(y, sums)``: ``sums`` = fp32 [2, K] per-channel sum / sum of squares of y
     accumulated in the conv epilogue (None when the layer runs on the fallback path) -- the following
     ``batch_norm_act(..., sums=sums)`` then needs no statistics pass. ``grad_link``: a gradient for x
     deposited there by a later-backward node (``batch_norm_act(res_link=...)``) is added to dx in the dgrad.
-    ``bn3_link``: a Bn3Link shared with the BatchNorm that is y's only reader (``bn_act_dual(..., bn3_link_r=)``)."""
+    ``apply_link``: an ApplyLink shared with the BatchNorm that is y's only reader (``batch_norm_act(...,
+    apply_link=)``, ``bn_act_dual(..., apply_link_r=)``)."""
     bn_link = getattr(x, "_k8s_bnstat", None)
-    y, sums = _Conv2dNHWC.apply(x, p.store.anchor, p, stride, padding, with_stats, grad_link, bn_link, bn3_link)
+    y, sums = _Conv2dNHWC.apply(x, p.store.anchor, p, stride, padding, with_stats, grad_link, bn_link, apply_link)
     return (y, sums) if with_stats else y
 
 
@@ -419,7 +421,7 @@ def stem_s2d_input(images, pad: int = 3):
 class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, anchor, pg, pb, run_mean, run_var, training, momentum, eps, relu, sums=None,
-                res_link=None, dy_link=None, stat_link=None, sub2=None, bn3_link=None):
+                res_link=None, dy_link=None, stat_link=None, sub2=None, apply_link=None):
         x = x.contiguous()
         if res is not None:
             res = res.contiguous()
@@ -454,10 +456,11 @@ class _BnAct(torch.autograd.Function):
             else:
                 stat_link.fill_mask(x, mask, mean, pg.store)
             ctx.stat_link = stat_link
-        # the convolution that produced x takes this BatchNorm's apply pass into its backward (Bn3Link)
-        # ... or, a BatchNorm + ReLU without residual (the ReLU recomputed from x), conv1 of an identity block (relu form)
-        ctx.bn3_link = bn3_link if (bn3_link is not None and training and bn3_link.offered(x)
-                                    and (mask is not None or (ctx.relu_x and res is None and _gpu(x)))) else None
+        # the convolution that produced x takes this BatchNorm's apply pass into its backward (ApplyLink): a residual
+        # BatchNorm with its mask, or a BatchNorm + ReLU without residual (the ReLU recomputed from x)
+        kind = "mask" if mask is not None else "relu" if (ctx.relu_x and res is None and _gpu(x)) else None
+        linked = apply_link is not None and training and kind is not None and apply_link.offered(x)
+        ctx.apply_link, ctx.apply_kind = (apply_link, kind) if linked else (None, None)
         return y
 
     @staticmethod
@@ -477,19 +480,21 @@ class _BnAct(torch.autograd.Function):
             # the reduction, where it came with dy from its producer's epilogue (BnStatLink)
             pre = ctx.stat_link.take(dy) if ctx.stat_link is not None else None
             sums = pre[0] if pre is not None else None
-            defer = ctx.bn3_link is not None and not want_dres and (
-                _conv_impl().conv1_fused_on() if ctx.relu_x else bn3_onload_on())
-            if defer:
-                # the first half only: x's producer applies the table as it loads dy (Bn3Link; relu form: mask None)
+            kind = APPLY_KINDS[ctx.apply_kind] if ctx.apply_link is not None else None
+            if kind is not None and not want_dres and kind.defer_on():
+                # the first half only: x's producer applies the table as it loads dy (ApplyLink)
                 params = _C().bn_bwd_params(dy, x, mask, sums, mean, invstd, pg.master, pb.master, dg, db)
-                ctx.bn3_link.fill(dy, x, mask, params)
-                _conv_impl().STATS["conv1_onload"] += ctx.relu_x
+                if ctx.apply_kind == "relu":
+                    ctx.apply_link.fill_relu(dy, x, params)
+                    _conv_impl().STATS["conv1_onload"] += 1
+                else:
+                    ctx.apply_link.fill_mask(dy, x, mask, params)
                 dx, dres = dy, None
             else:
                 dx, dres = _C().bn_bwd(dy, x, y, mean, invstd, pg.master, pb.master, ctx.relu_x, dg, db, want_dres,
                                        mask, sums)
-            if ctx.bn3_link is not None and dx is not dy:
-                _conv_impl().STATS["conv1_apply" if ctx.relu_x else "bn3_apply"] += 1
+            if kind is not None and dx is not dy:
+                _conv_impl().STATS[kind.apply_stat] += 1
             if handoff:
                 dres = MaskedGrad(dy, mask)
             elif mask_out:  # the producing plain BN masks dy itself (MaskLink)
@@ -541,7 +546,7 @@ class _BnReluConv(torch.autograd.Function):
     Returns (y, y's BN statistics sums) like ``conv2d_nhwc(..., with_stats=True)``."""
 
     @staticmethod
-    def forward(ctx, x, sums, anchor, pg, pb, run_mean, run_var, momentum, eps, pw, stride, padding, bn3_link=None):
+    def forward(ctx, x, sums, anchor, pg, pb, run_mean, run_var, momentum, eps, pw, stride, padding, out_link=None):
         C_ = _C()
         x = x.contiguous()
         M = x.numel() // x.shape[-1]
@@ -556,14 +561,13 @@ class _BnReluConv(torch.autograd.Function):
         ctx.x_requires_grad = x.requires_grad
         ctx.mark_non_differentiable(ysums)
         ctx.set_materialize_grads(False)
-        # the backward will be the fused family's (ops.conv._plan_bwd, but for the switches read per call): it can
-        # take the output BatchNorm's apply pass (Bn3Link)
-        ctx.bn3_link = None
-        K_, R, S, C = w.shape
-        if (bn3_link is not None and BN_BSTATS and R == 1 and S == 1 and stride == 1 and padding == 0
-                and C_.bwd1x1_fused_ok(M, C, K_)):
-            bn3_link.offer(y)
-            ctx.bn3_link = bn3_link
+        # the backward will be the fused family's (it fills a relu-kind BnStatLink on x under BN_BSTATS; the switches
+        # are read per call): it can take the output BatchNorm's apply pass (ApplyLink)
+        ctx.out_link = None
+        if (out_link is not None and BN_BSTATS
+                and _conv_impl().offer_family(C_, x, w, stride, padding, "relu", True, onload=True)):
+            out_link.offer(y)
+            ctx.out_link = out_link
         return y, ysums
 
     @staticmethod
@@ -577,8 +581,9 @@ class _BnReluConv(torch.autograd.Function):
         if BN_BSTATS:
             link = BnStatLink()
             link.fill_relu(x, mean, invstd, pg.master, pb.master, pg.store)
-        bn3 = ctx.bn3_link.take() if ctx.bn3_link is not None else None
-        dz = impl.conv_bwd(gy, x, pw.weight, ctx.stride, ctx.padding, True, pw, xform=params, bn_link=link, bn3=bn3)
+        deferred = ctx.out_link.take() if ctx.out_link is not None else None
+        dz = impl.conv_bwd(gy, x, pw.weight, ctx.stride, ctx.padding, True, pw, xform=params, bn_link=link,
+                           apply_link=deferred)
         dg, db, finish = _bn_param_grads(pg, pb, x.device)
         pre = link.take(dz) if link is not None else None
         dx, _ = _C().bn_bwd(dz, x, None, mean, invstd, pg.master, pb.master, True, dg, db, False, None,
@@ -610,20 +615,21 @@ def onload_ok(x, conv) -> bool:
             bool(_C().conv3x3_staged_ok(x.shape[1], x.shape[2], C, K_, R, S, conv.stride, conv.pad)))
 
 
-def bn_relu_conv(t, bn, conv, bn3_link=None, bn_in_link=None):
+def bn_relu_conv(t, bn, conv, out_link=None, in_link=None):
     """``conv(bn(t))`` for ``t = (x, sums)`` from ``conv2d_nhwc(..., with_stats=True)``, a training-mode ReLU
     BatchNorm ``bn`` (models/resnet.BN) and a convolution ``conv`` (models/resnet.Conv): normalised on load
     (``_BnReluConv``) where the kernels take it (``onload_ok``), else the separate BN apply + conv. Returns (y, y's
-    sums). ``bn3_link``: a Bn3Link shared with the residual BatchNorm that is y's only reader. ``bn_in_link``: a
-    relu-form Bn3Link shared with the convolution that produced ``x``, for ``bn`` where it runs as its own pass."""
+    sums). ``out_link``: an ApplyLink shared with the BatchNorm that is the output y's only reader. ``in_link``: an
+    ApplyLink shared with the convolution that produced ``x``, for the input BatchNorm ``bn`` where it runs as its
+    own pass."""
     x, sums = t if isinstance(t, tuple) else (t, None)
     w = conv.w
     if (sums is not None and bn.training and _gpu(x) and x.dtype == torch.bfloat16 and x.shape[-1] % 64 == 0
             and w.weight.dtype == torch.bfloat16 and w.shape[0] % 8 == 0 and w.grad.dtype == torch.float32
             and onload_ok(x, conv)):
         return _BnReluConv.apply(x, sums, w.store.anchor, bn.gamma, bn.beta, bn.running_mean, bn.running_var,
-                                 bn.momentum, bn.eps, w, conv.stride, conv.pad, bn3_link)
-    return conv(bn(t, bn3_link=bn_in_link))
+                                 bn.momentum, bn.eps, w, conv.stride, conv.pad, out_link)
+    return conv(bn(t, apply_link=in_link))
 
 
 # BatchNorm apply passes write the stride-2 subsample for a following downsample block (SubLink);
@@ -642,18 +648,18 @@ class SubLink:
 
 
 def batch_norm_act(x, pg, pb, run_mean, run_var, residual=None, relu=True, training=True, momentum=0.1,
-                   eps=1e-5, sums=None, res_link=None, dy_link=None, sub2=False, bn3_link=None):
+                   eps=1e-5, sums=None, res_link=None, dy_link=None, sub2=False, apply_link=None):
     """y = act(BN(x) + residual) over the last (channel) dim of an NHWC tensor.
 
     ``sums`` (fp32 [2, C] from ``conv2d_nhwc(..., with_stats=True)``) skips the statistics pass.
     ``res_link``: the residual's gradient is handed to that GradLink (and NOT returned to autograd); the
     node consuming the link must add it (``conv2d_nhwc(..., grad_link=link)`` on the same tensor).
     ``res_link`` may also be a MaskLink whose ``dy_link`` end is the plain BN that produced ``residual``.
-    ``bn3_link``: the Bn3Link given to the ``bn_relu_conv`` that produced ``x``, whose only reader this is."""
+    ``apply_link``: the ApplyLink given to the convolution that produced ``x``, whose only reader this is."""
     link = BnStatLink() if (BN_BSTATS and relu and training and _gpu(x)) else None
     sub = SubLink() if (sub2 and SUB2_FUSED and sums is not None and _gpu(x)) else None
     y = _BnAct.apply(x, residual, pg.store.anchor, pg, pb, run_mean, run_var, training, momentum, eps, relu,
-                     sums, res_link, dy_link, link, sub, bn3_link)
+                     sums, res_link, dy_link, link, sub, apply_link)
     if link is not None and link.kind is not None:
         y._k8s_bnstat = link
     if sub is not None and sub.y is not None:
@@ -1180,7 +1186,7 @@ class _BnActDual(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, sums, xr, sums_r, anchor, pg, pb, run_mean, run_var, pgr, pbr, run_mean_r, run_var_r,
-                momentum, eps, stat_link=None, bn3_link=None, bn3_link_r=None):
+                momentum, eps, stat_link=None, apply_link=None, apply_link_r=None):
         x, xr = x.contiguous(), xr.contiguous()
         y, mean, invstd, mask, mean_r, invstd_r = _C().bn_fwd_from_sums_dual(
             x, sums, pg.master, pb.master, run_mean, run_var, xr, sums_r, pgr.master, pbr.master, run_mean_r,
@@ -1190,11 +1196,12 @@ class _BnActDual(torch.autograd.Function):
         ctx.stat_link = stat_link
         if stat_link is not None:
             stat_link.fill_dual(x, mask, mean, xr, mean_r, pg.store)
-        # both producing convolutions take their half of the apply pass into their backwards (two Bn3Links): both
+        # both producing convolutions take their half of the apply pass into their backwards (two ApplyLinks): both
         # or neither
-        ctx.bn3_links = None
-        if (bn3_link is not None and bn3_link_r is not None and bn3_link.offered(x) and bn3_link_r.offered(xr)):
-            ctx.bn3_links = (bn3_link, bn3_link_r)
+        ctx.apply_links = None
+        if (apply_link is not None and apply_link_r is not None and apply_link.offered(x)
+                and apply_link_r.offered(xr)):
+            ctx.apply_links = (apply_link, apply_link_r)
         return y
 
     @staticmethod
@@ -1210,11 +1217,11 @@ class _BnActDual(torch.autograd.Function):
         sums, sums_r = pre if pre is not None and pre[1] is not None else (None, None)
         args = (dy, mask, x, mean, invstd, pg.master, pb.master, dg, db, xr, mean_r, invstd_r, pgr.master, pbr.master,
                 dgr, dbr, sums, sums_r)
-        if ctx.bn3_links is not None and _conv_impl().dual_onload_on():
-            # the first half only: each input's producer applies its table as it loads dy (Bn3Link)
+        if ctx.apply_links is not None and APPLY_KINDS["dual"].defer_on():
+            # the first half only: each input's producer applies its table as it loads dy (ApplyLink)
             params, params_r = C_.bn_bwd_dual_params(*args)
-            ctx.bn3_links[0].fill(dy, x, mask, params, dual=True)
-            ctx.bn3_links[1].fill(dy, xr, mask, params_r, dual=True)
+            ctx.apply_links[0].fill_dual(dy, x, mask, params)
+            ctx.apply_links[1].fill_dual(dy, xr, mask, params_r)
             _conv_impl().STATS["dual_onload"] += 1
             dx = dxr = dy
         else:  # and one apply pass for both
@@ -1224,11 +1231,11 @@ class _BnActDual(torch.autograd.Function):
         return (dx, None, dxr) + (None,) * 15
 
 
-def bn_act_dual(t, bn, tr, bn_r, bn3_link=None, bn3_link_r=None):
+def bn_act_dual(t, bn, tr, bn_r, apply_link=None, apply_link_r=None):
     """``relu(bn(t) + bn_r(tr))`` for ``t`` / ``tr`` = (conv output, epilogue sums) pairs and training-mode
     BatchNorms (models/resnet.BN); None when the fused kernel does not apply (caller runs the separate BNs).
-    ``bn3_link`` / ``bn3_link_r``: the Bn3Links given to the convolutions that produced ``t`` and ``tr``, whose only
-    reader this is."""
+    ``apply_link`` / ``apply_link_r``: the ApplyLinks given to the convolutions that produced ``t`` and ``tr``, whose
+    only reader this is."""
     if not BN_DUAL or not (isinstance(t, tuple) and isinstance(tr, tuple)):
         return None
     (x, sums), (xr, sums_r) = t, tr
@@ -1238,7 +1245,7 @@ def bn_act_dual(t, bn, tr, bn_r, bn3_link=None, bn3_link_r=None):
     link = BnStatLink() if BN_BSTATS else None
     y = _BnActDual.apply(x, sums, xr, sums_r, bn.gamma.store.anchor, bn.gamma, bn.beta, bn.running_mean,
                          bn.running_var, bn_r.gamma, bn_r.beta, bn_r.running_mean, bn_r.running_var, bn.momentum,
-                         bn.eps, link, bn3_link, bn3_link_r)
+                         bn.eps, link, apply_link, apply_link_r)
     if link is not None:
         y._k8s_bnstat = link
     return y

@@ -231,11 +231,11 @@ def test_bottleneck_bn3_fallback(cuda, monkeypatch):
 
     def forward(blk, x):  # Bottleneck.forward of an identity block, the copy between conv3 and bn3
         link = K.GradLink()
-        b3 = K.Bn3Link()
+        b3 = K.ApplyLink()
         t = blk.conv1(x, grad_link=link)
         t = K.bn_relu_conv(t, blk.bn1, blk.conv2)
-        y3, sums = K.bn_relu_conv(t, blk.bn2, blk.conv3, bn3_link=b3)
-        return blk.bn3((_CopyGrad.apply(y3), sums), residual=x, relu=True, res_link=link, bn3_link=b3)
+        y3, sums = K.bn_relu_conv(t, blk.bn2, blk.conv3, out_link=b3)
+        return blk.bn3((_CopyGrad.apply(y3), sums), residual=x, relu=True, res_link=link, apply_link=b3)
 
     monkeypatch.setenv("K8S_AMD_BN3_ONLOAD", "1")
     fb = _step(cuda, forward)

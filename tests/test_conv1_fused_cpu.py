@@ -1,4 +1,4 @@
-"""The relu-form Bn3Link between an identity block's conv1 and bn1 (offer / fill / covers / take) and
+"""The relu-kind ApplyLink between an identity block's conv1 and bn1 (offer / fill / covers / take) and
 ops.conv._plan_bwd's "conv1_fused" branch with its fallbacks. The planner launches nothing: it is driven with small CPU
 tensors, a stub in place of the extension and ``_hip`` answering yes; the CPU model path takes none of it."""
 import types
@@ -38,8 +38,11 @@ def _mask_link(shape=(N, H, H, C), kind="mask"):
 
 def _bn1(gy, w=W, mask=None):
     """bn1's deferred backward as conv1's backward takes it: filled for ``gy``."""
-    l = K.Bn3Link()
-    l.fill(gy, _t(*gy.shape), mask, _t(4 * w, dtype=torch.float32))
+    l = K.ApplyLink()
+    if mask is None:
+        l.fill_relu(gy, _t(*gy.shape), _t(4 * w, dtype=torch.float32))
+    else:
+        l.fill_mask(gy, _t(*gy.shape), mask, _t(4 * w, dtype=torch.float32))
     return l.take()
 
 
@@ -70,7 +73,7 @@ def test_plan_bwd_conv1_family(monkeypatch):
     assert _plan(monkeypatch, w=256, c=1024) == "stride1"  # stages 3-4
     assert _plan(monkeypatch, dw_ok=False) == "stride1"
     assert _plan(monkeypatch, xform=_t(2 * C, dtype=torch.float32)) == "stride1"
-    # a masked link is conv3's kind: the fused 1x1 family's, never this route's
+    # a mask-kind link is conv3's: the fused 1x1 family's, never this route's
     gy = _t(N, H, H, W)
     assert _plan(monkeypatch, gy=gy, bn1=_bn1(gy, mask=_t(N * H * H * W // 8, dtype=torch.uint8))) == "stride1"
 
@@ -107,16 +110,16 @@ def test_parent_route_and_counters(monkeypatch):
 
 def test_relu_form_offer_fill_covers_take():
     y1 = torch.zeros(4, 8)
-    b1 = K.Bn3Link()
+    b1 = K.ApplyLink()
     assert not b1.offered(y1) and b1.take() is None
     b1.offer(y1)
     assert b1.offered(y1) and not b1.offered(y1[:2]) and b1.offered(y1.view_as(y1))
     assert b1.take() is None  # offered, but bn1 has not deferred (the switch off, or bn1 normalised on load)
     dz1, p = torch.ones(4, 8), torch.zeros(32)
-    b1.fill(dz1, y1, None, p)
+    b1.fill_relu(dz1, y1, p)
     t = b1.take()
     assert b1.take() is None  # cleared
-    assert t.mask is None and t.x3 is y1 and t.params is p and not t.dual
+    assert t.kind == "relu" and t.mask is None and t.x is y1 and t.params is p
     assert t.covers(dz1) and not t.covers(dz1.clone())
     dz1.add_(1.0)  # an in-place change
     assert not t.covers(dz1)

@@ -313,11 +313,11 @@ def test_block_conv1_fallback(cuda, monkeypatch):
             return g.clone()
 
     def forward(blk, x):  # Bottleneck.forward of an identity block, the copy between conv1 and bn1
-        link, b1, b3 = K.GradLink(), K.Bn3Link(), K.Bn3Link()
-        y1, sums = blk.conv1(x, grad_link=link, bn3_link=b1)
-        t = K.bn_relu_conv((_CopyGrad.apply(y1), sums), blk.bn1, blk.conv2, bn_in_link=b1)
-        t = K.bn_relu_conv(t, blk.bn2, blk.conv3, bn3_link=b3)
-        return blk.bn3(t, residual=x, relu=True, res_link=link, bn3_link=b3)
+        link, b1, b3 = K.GradLink(), K.ApplyLink(), K.ApplyLink()
+        y1, sums = blk.conv1(x, grad_link=link, apply_link=b1)
+        t = K.bn_relu_conv((_CopyGrad.apply(y1), sums), blk.bn1, blk.conv2, in_link=b1)
+        t = K.bn_relu_conv(t, blk.bn2, blk.conv3, out_link=b3)
+        return blk.bn3(t, residual=x, relu=True, res_link=link, apply_link=b3)
 
     monkeypatch.setenv("K8S_AMD_CONV1_FUSED", "1")
     fb = _step(cuda, monkeypatch, forward)

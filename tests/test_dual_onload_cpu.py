@@ -1,4 +1,4 @@
-"""The two Bn3Links of a stage-1 entry block (offer / fill / covers / take) and ops.conv._plan_bwd's "fused_final"
+"""The two ApplyLinks of a stage-1 entry block (offer / fill / covers / take) and ops.conv._plan_bwd's "fused_final"
 branch. The planner only reads shapes, so it is driven with meta tensors, a stub in place of the extension and
 ``_hip`` answering yes; the CPU model path takes none of it."""
 import types
@@ -79,26 +79,26 @@ def test_final_data_gradient_keeps_its_route_name(monkeypatch):
 
 def test_two_links_offer_fill_covers_take():
     y3, yr = torch.zeros(4, 8), torch.zeros(4, 8)
-    b3, b3r = K.Bn3Link(), K.Bn3Link()
-    assert not b3.offered(y3) and b3.take() is None and not b3.dual
+    b3, b3r = K.ApplyLink(), K.ApplyLink()
+    assert not b3.offered(y3) and b3.take() is None and b3.kind is None
     b3.offer(y3)
     b3r.offer(yr)
     assert b3.offered(y3) and b3r.offered(yr) and not b3.offered(yr) and not b3r.offered(y3)
     assert not b3.offered(y3[:2]) and b3.offered(y3.view_as(y3))
     assert b3.take() is None  # offered, but the BatchNorm has not deferred
     dy, mask, p, pr = torch.ones(4, 8), torch.zeros(4, dtype=torch.uint8), torch.zeros(32), torch.ones(32)
-    b3.fill(dy, y3, mask, p, dual=True)
-    b3r.fill(dy, yr, mask, pr, dual=True)
+    b3.fill_dual(dy, y3, mask, p)
+    b3r.fill_dual(dy, yr, mask, pr)
     t3, tr = b3.take(), b3r.take()
     assert b3.take() is None and b3r.take() is None  # cleared
-    assert t3.dual and tr.dual and t3.x3 is y3 and tr.x3 is yr and t3.params is p and tr.params is pr
+    assert t3.kind == tr.kind == "dual" and t3.x is y3 and tr.x is yr and t3.params is p and tr.params is pr
     assert t3.covers(dy) and tr.covers(dy)  # the one dy is both halves' gradient
     assert not t3.covers(dy.clone())
     dy.add_(1.0)  # an in-place change
     assert not t3.covers(dy) and not tr.covers(dy)
-    single = K.Bn3Link()
-    single.fill(dy, y3, mask, p)
-    assert not single.take().dual
+    single = K.ApplyLink()
+    single.fill_mask(dy, y3, mask, p)
+    assert single.take().kind == "mask"
 
 
 def test_cpu_entry_block_unchanged():

@@ -235,13 +235,13 @@ def _fallback_forward(blk, x):
     from k8s_amd.ops import nn as K
 
     dlink = K.GradLink(shared=True)
-    b3, b3r = K.Bn3Link(), K.Bn3Link()
-    dn = blk.down(x, grad_link=dlink, bn3_link=b3r)
+    b3, b3r = K.ApplyLink(), K.ApplyLink()
+    dn = blk.down(x, grad_link=dlink, apply_link=b3r)
     t = blk.conv1(x, grad_link=dlink)
     t = K.bn_relu_conv(t, blk.bn1, blk.conv2)
-    y3, s3 = K.bn_relu_conv(t, blk.bn2, blk.conv3, bn3_link=b3)
+    y3, s3 = K.bn_relu_conv(t, blk.bn2, blk.conv3, out_link=b3)
     return K.bn_act_dual((_CopyGrad.apply(y3), s3), blk.bn3, (_CopyGrad.apply(dn[0]), dn[1]), blk.down_bn,
-                         bn3_link=b3, bn3_link_r=b3r)
+                         apply_link=b3, apply_link_r=b3r)
 
 
 def _step(cuda, forward=_block_forward):

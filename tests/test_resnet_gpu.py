@@ -257,6 +257,9 @@ def test_bn_backward_sums_in_dgrad_epilogue_match_reduction(cuda):
     from k8s_amd.models.resnet_ref import reference_grads
     from k8s_amd.ops import conv as kc
 
+    ONLOAD_STATS = ("bn3_onload", "bn3_apply", "dual_onload", "dual_apply", "fused_final", "conv1_onload",
+                    "conv1_apply", "conv1_fused")
+
     def run(on):
         old = K.BN_BSTATS
         K.BN_BSTATS = on
@@ -277,29 +280,34 @@ def test_bn_backward_sums_in_dgrad_epilogue_match_reduction(cuda):
             x = m.prepare_input(images.bfloat16())
             x8 = m.prepare_input(images.bfloat16(), s2d=False)
             y = torch.arange(4, device=cuda) % 10
-            n0, r0 = kc.STATS["bn_bstats"], kc.ROUTES.copy()
+            n0, r0, s0 = kc.STATS["bn_bstats"], kc.ROUTES.copy(), dict(kc.STATS)
             store.begin_step()
             loss = K.cross_entropy(m(x), y)
             loss.backward()
             store.zero_unwritten()
             n, routes = kc.STATS["bn_bstats"] - n0, dict(kc.ROUTES - r0)
+            onload = {k: kc.STATS[k] - s0[k] for k in ONLOAD_STATS}
             _, ref = reference_grads(m, store, x8, y)
             err = {}
             for p in store.params:
                 r = ref[p.name].float()
                 err[p.name] = (p.grad.float() - r).norm().item() / (r.norm().item() + 1e-6)
-            return loss.item(), err, n, routes
+            return loss.item(), err, n, routes, onload
         finally:
             K.BN_BSTATS = old
 
-    l1, e1, n1, routes = run(True)
-    l0, e0, n0, _ = run(False)
+    l1, e1, n1, routes, onload = run(True)
+    l0, e0, n0, _, _ = run(False)
     # s1b0 (dual), s1b1, s2b1, the stage-1/2 bn2 sums in conv3's dgrad, the s1b2 / s2b2 outputs' two-dgrad sums
     assert n0 == 0 and n1 >= 8, (n0, n1)
     # the route every data gradient of the step takes (ops.conv.ROUTES), recorded at the commit before the dispatch was
     # split into planners by tallying its branches: a changed count is a layer moved to another kernel
     assert routes == {"fused_1x1": 6, "gemm_plain": 2, "implicit_flipped": 5, "parity": 4, "parity_complete_sums": 2,
                       "short_entry_pending": 2, "short_mask_sums": 4, "tile_final_sums": 1, "tile_relu_sums": 2}, routes
+    # ... and the BatchNorm apply passes deferred to the producing convolution (ops.nn.ApplyLink), recorded at the
+    # commit before the link kinds were made explicit: every offer is taken on load, none turns into a fallback apply
+    assert onload == {"bn3_onload": 5, "bn3_apply": 0, "dual_onload": 1, "dual_apply": 0, "fused_final": 1,
+                      "conv1_onload": 2, "conv1_apply": 0, "conv1_fused": 2}, onload
     assert l1 == l0, (l1, l0)  # the forward is untouched (and deterministic at this size)
     bad = [(k, round(e1[k], 4), round(e0[k], 4)) for k in e0 if e1[k] > 1.5 * e0[k] + 0.02]
     assert not bad, bad
