@@ -178,6 +178,6 @@ inline GemmShortBnStats gemm_short_bn_stats(const Tensor& x, const Tensor& mask,
 // ------------------------------------------------------------------ one per family file
 using Module = pybind11::module_;
 void bind_optim(Module&), bind_batchnorm(Module&), bind_norm(Module&), bind_gemm(Module&), bind_conv(Module&);
-void bind_attention(Module&), bind_elementwise(Module&), bind_data(Module&);
+void bind_attention(Module&), bind_elementwise(Module&), bind_data(Module&), bind_decode(Module&);
 
 }  // namespace k8s_amd::binding

@@ -6,7 +6,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   using namespace k8s_amd::binding;
   m.doc() = "k8s_amd gfx950 (MI355X) HIP kernels";
   for (auto bind : {bind_optim, bind_batchnorm, bind_norm, bind_gemm, bind_conv, bind_attention, bind_elementwise,
-                    bind_data})
+                    bind_data, bind_decode})
     bind(m);
   m.def("planner_cus", &k8s_amd::planner_cus,
         "CUs the launch planners size grids for (the device's multiprocessor count unless overridden)");

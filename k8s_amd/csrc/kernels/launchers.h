@@ -520,4 +520,28 @@ void launch_maxpool_fwd(const uint16_t* x, uint16_t* y, uint8_t* idx, int N, int
 void launch_maxpool_bwd(const uint16_t* dy, const uint8_t* idx, uint16_t* dx, int N, int H, int W, int C, int Ho,
                         int Wo, int k, int s, int p, hipStream_t st);
 
+// decode.hip: generation. linear_skinny: y[M, N] = x[M, K] . w[N, K]^T for 1 <= M <= 16, K % 64 == 0, N % 16 == 0
+// (linear_skinny_ok); skinny_plan: its K split, a function of (N, K) alone -- `part` holds nsplit fp32 [M, N] partials
+// when nsplit > 1 and is not read otherwise.
+struct SkinnyPlan {
+  int kc = 0;      // k per chunk, a multiple of 64
+  int nsplit = 1;  // chunks
+};
+bool linear_skinny_ok(long M, long N, long K);
+SkinnyPlan skinny_plan(long N, long K);
+void launch_linear_skinny(const uint16_t* x, const uint16_t* w, uint16_t* y, float* part, int M, int N, int K,
+                          hipStream_t st);
+// token s of row b of qkv [B * S, (Hq + 2 Hkv) * D] -> position clamp(start[b] + s, 0, Smax - 1) of the bf16 caches
+// [B, Hkv, Smax, D]; start: device int32 [B]
+void launch_kv_append(const uint16_t* qkv, uint16_t* ck, uint16_t* cv, const int* start, int B, int S, int Hq, int Hkv,
+                      int D, int Smax, hipStream_t st);
+// one new token per row: q [B, Hq, D] with row stride ldq (elements, a multiple of 8), caches [B, Hkv, Smax, D], lens device int32 [B] (clamped into [1, Smax]), out
+// [B, Hq * D]. Keys in chunks of kDecodeChunk; nchunks chunks are launched (every row's len <= nchunks * kDecodeChunk
+// is the caller's to ensure; a longer row attends to that many keys); workspaces fp32 ws_ml [B, Hkv, nchunks, G, 2]
+// and ws_o [B, Hkv, nchunks, G, D], G = Hq / Hkv <= 16.
+constexpr int kDecodeChunk = 256;
+void launch_decode_attention(const uint16_t* q, long ldq, const uint16_t* ck, const uint16_t* cv, const int* lens, float* ws_ml,
+                             float* ws_o, uint16_t* out, int B, int Hq, int Hkv, int D, int Smax, int nchunks,
+                             float scale, hipStream_t st);
+
 }  // namespace k8s_amd

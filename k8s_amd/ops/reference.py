@@ -152,25 +152,31 @@ def dropout_rowkey(state, site: int, rows):
     return philox4x32(counter, key)[0]
 
 
-def dropout_keep(state, site: int, rows, cols, p: float):
-    """Keep mask (bool, ``rows``' shape + [len(cols)]) of the dropout site ``site``: ``rows`` int64 row indices (a
-    tensor, or a count meaning 0 .. n - 1), ``cols`` likewise the columns; ``state`` a DropoutState, its int64
-    [seed, step] tensor, or a (seed, step) pair."""
+def counter_bits(state, site: int, rows, cols):
+    """The counter generator's 32-bit value (int64 tensor of values < 2^32, ``rows``' shape + [len(cols)]) at
+    ``(seed, step, site, row, col)``: ``rows`` int64 row indices (a tensor, or a count meaning 0 .. n - 1), ``cols``
+    likewise the columns; ``state`` a DropoutState, its int64 [seed, step] tensor, or a (seed, step) pair. What
+    ``dropout_keep`` compares with its threshold, and what ``ops.sampling`` draws its uniform number from."""
     t = getattr(state, "tensor", state)
     dev = t.device if isinstance(t, torch.Tensor) else None
     if not isinstance(rows, torch.Tensor):
         rows = torch.arange(int(rows), dtype=torch.int64, device=dev)
     if not isinstance(cols, torch.Tensor):
         cols = torch.arange(int(cols), dtype=torch.int64, device=rows.device)
-    thr, _ = drop_params(p)
     rk = dropout_rowkey(state, site, rows).unsqueeze(-1)
     x = rk ^ _mul32(cols.to(device=rows.device, dtype=torch.int64) & _M32, 0x9E3779B1)
     x = x ^ (x >> 16)
     x = _mul32(x, 0x7FEB352D)
     x = x ^ (x >> 15)
     x = _mul32(x, 0x846CA68B)
-    x = x ^ (x >> 16)
-    return x >= thr
+    return x ^ (x >> 16)
+
+
+def dropout_keep(state, site: int, rows, cols, p: float):
+    """Keep mask (bool, ``rows``' shape + [len(cols)]) of the dropout site ``site``: ``counter_bits`` of the same
+    arguments at or above the threshold of ``p``."""
+    thr, _ = drop_params(p)
+    return counter_bits(state, site, rows, cols) >= thr
 
 
 def attention_keep(state, site: int, B: int, H: int, Sq: int, Sk: int, p: float, device=None):
@@ -644,3 +650,50 @@ def causal_doc_batch(src, starts, abs_starts, doc_tok, S: int):
     hi = (end - ab).clamp(max=S)
     labels = torch.where(p + 1 < end, labels, torch.full_like(labels, -100))
     return ids, labels, lo.to(torch.int32), hi.to(torch.int32), (j - lo).to(torch.int32)
+
+
+# --------------------------------------------------------------------------- generation (ops/decode.py)
+def linear_skinny(x, w):
+    """y = x . w^T accumulated in fp32, one rounding to x's dtype."""
+    return torch.matmul(x.float(), w.float().t()).to(x.dtype)
+
+
+def check_cache_table(table, B: int, lo: int, hi: int, what: str) -> None:
+    """A host mirror (int [B]) with every entry in [lo, hi], as the bindings check it before a launch."""
+    t = torch.as_tensor(table).reshape(-1)
+    if t.numel() != B:
+        raise RuntimeError("%s must have B = %d entries, has %d" % (what, B, t.numel()))
+    bad = ((t < lo) | (t > hi)).nonzero()
+    if bad.numel():
+        b = int(bad[0])
+        raise RuntimeError("%s row %d: %d outside [%d, %d]" % (what, b, int(t[b]), lo, hi))
+
+
+def kv_append(qkv, cache_k, cache_v, start, S: int, Hq: int) -> None:
+    """Token s of row b of the packed, rotated projection output ``qkv`` [B * S, (Hq + 2 Hkv) * D] goes to position
+    ``start[b] + s`` of the caches [B, Hkv, Smax, D]: an index copy."""
+    B, Hkv, Smax, D = cache_k.shape
+    start = torch.as_tensor(start).to(qkv.device).long()
+    check_cache_table(start.cpu(), B, 0, Smax - S, "start")
+    g = qkv.reshape(B, S, Hq + 2 * Hkv, D)
+    pos = start[:, None] + torch.arange(S, device=qkv.device)[None]  # [B, S]
+    b = torch.arange(B, device=qkv.device)[:, None].expand(B, S)
+    for h in range(Hkv):
+        cache_k[b, h, pos] = g[:, :, Hq + h].to(cache_k.dtype)
+        cache_v[b, h, pos] = g[:, :, Hq + Hkv + h].to(cache_v.dtype)
+
+
+def decode_attention(q, cache_k, cache_v, lens, scale: float):
+    """One query token per row: q [B, Hq, D] against the keys 0 .. lens[b] - 1 of the caches [B, Hkv, Smax, D]; returns
+    [B, Hq * D]. Cache positions at or past lens[b] are never read (they may hold anything, NaN included): they are
+    replaced by zeros before the products, not merely masked in the scores."""
+    B, Hq, D = q.shape
+    Hkv, Smax = cache_k.shape[1], cache_k.shape[2]
+    lens = torch.as_tensor(lens).to(q.device).long().clamp(1, Smax)
+    live = torch.arange(Smax, device=q.device)[None, :] < lens[:, None]  # [B, Smax]
+    zero = torch.zeros((), device=q.device)
+    k = torch.where(live[:, None, :, None], cache_k.float(), zero)
+    v = torch.where(live[:, None, :, None], cache_v.float(), zero)
+    s = torch.einsum("bhgd,bhsd->bhgs", q.float().reshape(B, Hkv, Hq // Hkv, D), k) * scale
+    p = torch.softmax(s.masked_fill(~live[:, None, None, :], float("-inf")), -1)
+    return torch.einsum("bhgs,bhsd->bhgd", p, v).reshape(B, Hq * D).to(q.dtype)
