@@ -5,12 +5,13 @@
 namespace k8s_amd::binding {
 namespace {
 
-// x of a BatchNorm: dense bf16 with the channels last; returns C
-int bn_channels(const Tensor& x, const char* name, bool mult8) {
+// x of a BatchNorm: dense bf16 with the channels last, in whole 16-byte groups of 8 channels (what every kernel reads
+// and writes); returns C
+int bn_channels(const Tensor& x, const char* name) {
   check_bf16_dense(x, -1, name);
   TORCH_CHECK(x.dim() >= 1 && x.size(-1) > 0, name, ": channels last");
   const int C = (int)x.size(-1);
-  TORCH_CHECK(!mult8 || C % 8 == 0, "channels must be a multiple of 8");
+  TORCH_CHECK(C % 8 == 0, "channels must be a multiple of 8");
   return C;
 }
 // gamma / beta / running mean / running variance
@@ -40,7 +41,7 @@ Tensor relu_mask_for(const Tensor& x, bool want_mask) {
 std::vector<Tensor> bn_fwd_impl(const Tensor& x, const OptTensor& res, const Tensor& gamma, const Tensor& beta,
                                 const Tensor* sums, const Tensor& run_mean, const Tensor& run_var, bool training,
                                 double momentum, double eps, bool relu, bool want_mask, bool want_sub2) {
-  const int C = bn_channels(x, "x", true);
+  const int C = bn_channels(x, "x");
   const long M = x.numel() / C;
   check_affine(gamma, beta, run_mean, run_var, C);
   const int nrep = sums ? check_stat_sums(*sums, C, "sums", false) : 0;
@@ -83,7 +84,7 @@ std::vector<Tensor> bn_fwd_from_sums(Tensor x, OptTensor res, Tensor gamma, Tens
 std::vector<Tensor> bn_fwd_from_sums_dual(Tensor x, Tensor sums, Tensor gamma, Tensor beta, Tensor run_mean,
                                           Tensor run_var, Tensor xr, Tensor sums_r, Tensor gamma_r, Tensor beta_r,
                                           Tensor run_mean_r, Tensor run_var_r, double momentum, double eps) {
-  const int C = bn_channels(x, "x", true);
+  const int C = bn_channels(x, "x");
   const long M = x.numel() / C;
   check_same_shape(xr, x, "xr");
   check_affine(gamma, beta, run_mean, run_var, C);
@@ -106,6 +107,7 @@ std::vector<Tensor> bn_fwd_from_sums_dual(Tensor x, Tensor sums, Tensor gamma, T
 std::vector<Tensor> bn_finalize(Tensor sums, Tensor gamma, Tensor beta, Tensor run_mean, Tensor run_var,
                                 int64_t count, double momentum, double eps) {
   const int C = (int)gamma.numel();
+  TORCH_CHECK(C > 0 && C % 8 == 0, "channels must be a multiple of 8");  // what every consumer of params loads
   check_affine(gamma, beta, run_mean, run_var, C);
   const int nrep = check_stat_sums(sums, C, "sums", false);
   auto mean = torch::empty({C}, gamma.options()), invstd = torch::empty({C}, gamma.options());
@@ -147,8 +149,6 @@ std::vector<Tensor> bn_relu_maxpool(Tensor x, Tensor sums, Tensor gamma, Tensor 
 // the reduction was already done by dy's producer (a data gradient's epilogue), leaving the final and apply passes --
 // and no workspace is allocated. pool: the stem's BN + max pool (its own workspace size; sums of exactly
 // conv_stat_replicas). s.dx stays null (a deferred apply pass) until the caller sets it.
-// The callers' channel checks differ and stay as they were: bn_bwd takes any C (bn_channels without mult8),
-// bn_bwd_params and bn_bwd_apply want C % 8 == 0, the two-BatchNorm forms want it only without sums.
 struct BwdSide {
   k8s_amd::BnBwdSide s;
   int nrep = 0;
@@ -184,6 +184,7 @@ Tensor pool_bn_bwd(Tensor dpool, Tensor idx, Tensor x, Tensor mean, Tensor invst
   check_bf16_dense(dpool, 4, "dpool");
   check_cuda(idx, "idx"); check_dtype(idx, at::kByte, "idx");
   const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  TORCH_CHECK(C > 0 && C % 8 == 0 && 256 % (C / 8) == 0, "C / 8 must divide 256");
   TORCH_CHECK(dpool.sizes() == idx.sizes() && dpool.size(0) == N && dpool.size(1) == (H + 1) / 2 &&
                   dpool.size(2) == (W + 1) / 2 && dpool.size(3) == C, "dpool / idx shape mismatch");
   BwdSide a = bwd_side(x, mean, invstd, gamma, beta, dgamma, dbeta, opt_ptr(sums), "sums", 0, C, true);
@@ -198,7 +199,7 @@ Tensor pool_bn_bwd(Tensor dpool, Tensor idx, Tensor x, Tensor mean, Tensor invst
 // from y first (compatibility; the trainer passes the mask). sums (optional, with the mask or relu_x, not with y).
 std::vector<Tensor> bn_bwd(Tensor dy, Tensor x, OptTensor y, Tensor mean, Tensor invstd, Tensor gamma, Tensor beta,
                            bool relu_x, Tensor dgamma, Tensor dbeta, bool want_dres, OptTensor mask, OptTensor sums) {
-  const int C = bn_channels(x, "x", false);
+  const int C = bn_channels(x, "x");
   const long M = x.numel() / C;
   check_same_shape(dy, x, "dy");
   const bool has_mask = mask && mask->defined();
@@ -232,7 +233,7 @@ std::vector<Tensor> bn_bwd(Tensor dy, Tensor x, OptTensor y, Tensor mean, Tensor
 // consumer of dx that forms it on load from dy, x and the table (conv1_fused).
 Tensor bn_bwd_params(Tensor dy, Tensor x, OptTensor mask, OptTensor sums, Tensor mean, Tensor invstd, Tensor gamma,
                      Tensor beta, Tensor dgamma, Tensor dbeta) {
-  const int C = bn_channels(x, "x", true);
+  const int C = bn_channels(x, "x");
   const long M = x.numel() / C;
   check_same_shape(dy, x, "dy");
   const bool has_mask = mask && mask->defined();
@@ -242,7 +243,7 @@ Tensor bn_bwd_params(Tensor dy, Tensor x, OptTensor mask, OptTensor sums, Tensor
   return a.params;
 }
 Tensor bn_bwd_apply(Tensor dy, Tensor x, OptTensor mask, Tensor params) {
-  const int C = bn_channels(x, "x", true);
+  const int C = bn_channels(x, "x");
   check_same_shape(dy, x, "dy");
   const bool has_mask = mask && mask->defined();
   const uint8_t* mk = has_mask ? check_bit_mask(*mask, x.numel(), "mask") : nullptr;
@@ -270,7 +271,7 @@ std::vector<Tensor> bn_bwd_dual_impl(bool want_dx, const Tensor& dy, const Tenso
                                      const OptTensor& sums2) {
   const Tensor *pre = opt_ptr(sums), *pre2 = opt_ptr(sums2);
   TORCH_CHECK(!pre == !pre2, "sums and sums2 come together");
-  const int C = bn_channels(x, "x", !pre);
+  const int C = bn_channels(x, "x");
   const long M = x.numel() / C;
   check_same_shape(dy, x, "dy");
   check_same_shape(x2, x, "x2");

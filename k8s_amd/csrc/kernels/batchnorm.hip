@@ -71,12 +71,23 @@ __global__ void __launch_bounds__(BN_THREADS) bn_stats_kernel(const uint16_t* __
 #pragma unroll
   for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
   float shift[8];
-  // shift by the first row of the block to avoid catastrophic cancellation
-  if (active && r0 < M) {
-    load8(x + r0 * C + cg * 8, shift);
-  } else {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) shift[j] = 0.f;
+  for (int j = 0; j < 8; ++j) shift[j] = 0.f;
+  // shift by the mean of the block's first four rows (its last row again where it has fewer) to avoid catastrophic
+  // cancellation. One row alone is several sigma from the channel's mean in some channel of every wide tensor, and
+  // every rounding of the merges below is as large as that distance. Sums of four bf16 values and a scaling by 1/4 are
+  // exact, so equal rows still give d = 0 and M2 = 0; every thread of a channel group forms the same shift.
+  if (active && r0 < M) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long rw = r0 + u < r1 ? r0 + u : r1 - 1;
+      float v[8];
+      load8(x + rw * C + cg * 8, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) shift[j] += v[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) shift[j] *= 0.25f;
   }
   int n = 0;
   if (active) {
@@ -115,31 +126,35 @@ __global__ void __launch_bounds__(BN_THREADS) bn_stats_kernel(const uint16_t* __
     sh[1][t][j] = n ? (q[j] - s[j] * mean) : 0.f;
   }
   sh[0][t][8] = (float)n;
-  __syncthreads();
-  // combine rows (threads with the same cg_local) -- row 0 threads do it
-  if (r == 0 && cg * 8 < C) {
-    float cnt = sh[0][t][8];
-    float mean[8], m2[8];
+  // combine rows (threads with the same cg_local) as a tree: row r takes in row r + half. Every Chan merge rounds the
+  // running mean (in the shifted coordinates, an ulp of |mean - shift|); rows_per_iter - 1 (up to 255) such roundings
+  // one after another, behind a one-row shift, left the mean up to 16 u mean|x| off. The tree's log2(rows_per_iter)
+  // levels and the four-row shift keep it inside 8 u with room (tests/test_bn_kernels_gpu.py).
+  int span = 1;
+  while (span < rows_per_iter) span <<= 1;
+  for (int half = span >> 1; half >= 1; half >>= 1) {
+    __syncthreads();
+    if (r < half && r + half < rows_per_iter && cg * 8 < C) {
+      const int o = (r + half) * tpr + cg_local;
+      const float cnt = sh[0][t][8], nb = sh[0][o][8];
+      if (nb != 0.f) {
+        const float tot = cnt + nb;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { mean[j] = sh[0][t][j]; m2[j] = sh[1][t][j]; }
-    for (int rr = 1; rr < rows_per_iter; ++rr) {
-      const int o = rr * tpr + cg_local;
-      const float nb = sh[0][o][8];
-      if (nb == 0.f) continue;
-      const float tot = cnt + nb;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float d = sh[0][o][j] - mean[j];
-        mean[j] += d * nb / tot;
-        m2[j] += sh[1][o][j] + d * d * cnt * nb / tot;
+        for (int j = 0; j < 8; ++j) {
+          const float d = sh[0][o][j] - sh[0][t][j];
+          sh[0][t][j] += d * nb / tot;
+          sh[1][t][j] += sh[1][o][j] + d * d * cnt * nb / tot;
+        }
+        sh[0][t][8] = tot;
       }
-      cnt = tot;
     }
+  }
+  if (r == 0 && cg * 8 < C) {  // its own slot: no barrier needed
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const long idx = ((long)blockIdx.x * C + cg * 8 + j) * 2;
-      part[idx] = mean[j] + shift[j];
-      part[idx + 1] = m2[j];
+      part[idx] = sh[0][t][j] + shift[j];
+      part[idx + 1] = sh[1][t][j];
     }
   }
 }
