@@ -36,7 +36,7 @@ Tensor conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad, int64_t dil, bo
   return y;
 }
 
-// Inference convolution with the following BatchNorm folded into the epilogue (gemm.hip IEPI):
+// Inference convolution with the following BatchNorm folded into the epilogue (gemm.hip TileEpi::LeanInfer):
 //   y = act(bf16(conv(x, w) * scale + shift) + res); scale / shift fp32 [K], res bf16 [N, Ho, Wo, K] or None.
 // Always the tile kernel; a shape outside its contract raises. `out`: write into this bf16 [N, Ho, Wo, K] tensor.
 Tensor conv_infer(Tensor x, Tensor w, int64_t stride, int64_t pad, Tensor scale, Tensor shift, OptTensor res,
@@ -78,7 +78,7 @@ void conv_fwd_subgrid(Tensor x, Tensor w, int64_t pad, int64_t Hs, int64_t Ws, T
   TORCH_CHECK(Hs >= 1 && Ws >= 1 && (Hs - 1) * stride + a < OH && (Ws - 1) * stride + b < OW,
               "sub-grid exceeds the output image");
   k8s_amd::SubGrid sg{OH, OW, (int)stride, (int)a, (int)b};
-  // bn_*: a BatchNorm's backward sums over `out` (gemm.hip BST sub-grid path). mask kind (bn_mask, accumulate): the
+  // bn_*: a BatchNorm's backward sums over `out` (gemm.hip TileEpi::LeanBnBwd, sub-grid rows). mask kind (bn_mask, accumulate): the
   // correction of a residual BatchNorm's sums for the elements this accumulating product changes (the first data
   // gradient into `out` took the sums over its values). relu kind (bn_gamma / bn_beta / bn_invstd, a plain store):
   // the sums of a BatchNorm + ReLU over this parity's stored pixels (the parities partition the output).

@@ -78,7 +78,7 @@ Tensor dgrad_short_bnstats(Tensor gy, Tensor w, OptTensor add_src, OptTensor add
 }
 
 // 1x1 data gradient dx[M, N] = gy[M, K] . w[K, N] on the tile kernel with the BatchNorm-backward sums of dx for the
-// relu(BN(x)) that produced the convolution's input (gemm.hip BST epilogue); for shapes the 4-wave kernel does not
+// relu(BN(x)) that produced the convolution's input (gemm.hip TileEpi::LeanBnBwd); for shapes the 4-wave kernel does not
 // take (gemm_dgrad_bnstats_ok). sums: zeroed fp32 [conv_stat_replicas, 2, N].
 Tensor gemm_dgrad_bnstats(Tensor gy, Tensor w, Tensor x, Tensor gamma, Tensor beta, Tensor mean, Tensor invstd,
                           Tensor sums) {
@@ -126,6 +126,19 @@ Tensor gemm_dgrad_bnstats_mask(Tensor gy, Tensor w, Tensor out, Tensor x, Tensor
   launch_gemm_dgrad_bnstats(cbf(gy), cbf(w), bf(out), (int)M, (int)N, (int)K, bb, cur_stream(), true,
                             add_src ? cbf(*add_src) : nullptr, am);
   return out;
+}
+
+// The tile kernel's form for a launch described by plain values (gemm.hip choose_tile_form): a pure host function,
+// like flash_plan. A launch the chooser refuses raises its message.
+std::string gemm_tile_form(const std::string& pair, int64_t wm, int64_t N, int64_t splits, int64_t xuse, int64_t ldc,
+                           bool out_f32, int64_t mode, bool bias, bool pre, int64_t act, bool stats, bool rst,
+                           bool addsrc, bool addmask, bool bb_sums, bool bb_mask, bool c_aligned, bool pre_aligned) {
+  k8s_amd::TileFormQuery q;
+  q.pair = pair.c_str(); q.wm = (int)wm; q.N = (int)N; q.splits = (int)splits; q.xuse = (int)xuse;
+  q.ldc = ldc < 0 ? N : ldc; q.out_f32 = out_f32; q.mode = (int)mode; q.act = (int)act;
+  q.bias = bias; q.pre = pre; q.stats = stats; q.rst = rst; q.addsrc = addsrc; q.addmask = addmask;
+  q.bb_sums = bb_sums; q.bb_mask = bb_mask; q.c_aligned = c_aligned; q.pre_aligned = pre_aligned;
+  return k8s_amd::gemm_tile_form(q);
 }
 
 bool gemm_dgrad_bnstats_ok(int64_t M, int64_t N, int64_t K) {
@@ -293,6 +306,11 @@ void bind_gemm(pybind11::module_& m) {
   m.def("gemm", &gemm, "a"_a, "a_kmajor"_a, "b"_a, "b_kmajor"_a, "out"_a, "out_f32"_a, "bias"_a, "act"_a, "pre"_a,
         "accumulate"_a, "alpha"_a, "splits"_a, "add_src"_a = py::none(), "add_mask"_a = py::none(),
         "xform_b"_a = py::none(), "xform_c"_a = 0);
+  m.def("gemm_tile_form", &gemm_tile_form, "pair"_a, "wm"_a = 2, "N"_a = 128, "splits"_a = 1, "xuse"_a = 0, "ldc"_a = -1,
+        "out_f32"_a = false, "mode"_a = 0, "bias"_a = false, "pre"_a = false, "act"_a = 0, "stats"_a = false,
+        "rst"_a = false, "addsrc"_a = false, "addmask"_a = false, "bb_sums"_a = false, "bb_mask"_a = false,
+        "c_aligned"_a = true, "pre_aligned"_a = true,
+        "which form of the tile kernel (gemm.hip TileEpi, +A / +B on-load) a launch takes; ldc < 0: N");
   m.def("gemm_short_ok", [](int64_t M, int64_t N, int64_t K) { return k8s_amd::gemm_short_ok((int)M, (int)N, (int)K, K, N); },
         "whether C[M,N] = A[M,K] . B^T (contiguous) takes the short-K streaming kernel (gemm_short.hip)");
   m.def("dgrad_short_bnstats", &dgrad_short_bnstats, "gy"_a, "w"_a, "add_src"_a, "add_mask"_a, "x"_a, "mask"_a,
@@ -302,7 +320,7 @@ void bind_gemm(pybind11::module_& m) {
     return M < (1L << 31) && k8s_amd::gemm_short_bnstats_ok((int)M, (int)N, (int)K, dual);
   });
   m.def("gemm_dgrad_bnstats", &gemm_dgrad_bnstats,
-        "1x1 data gradient with the BatchNorm-backward sums of a relu(BN(x)) input (gemm.hip BST epilogue)");
+        "1x1 data gradient with the BatchNorm-backward sums of a relu(BN(x)) input (gemm.hip TileEpi::LeanBnBwd)");
   m.def("gemm_dgrad_bnstats_ok", &gemm_dgrad_bnstats_ok,
         "whether a 1x1 data gradient takes gemm_dgrad_bnstats (on its regular kernel: the 4-wave or the tile kernel)");
   m.def("gemm_dgrad_bnstats_mask", &gemm_dgrad_bnstats_mask, "gy"_a, "w"_a, "out"_a, "x"_a, "mask"_a, "mean"_a,

@@ -1,15 +1,18 @@
-// K1 + K2: MFMA GEMM and NHWC implicit-GEMM convolution for gfx950.
+// K1 + K2: the MFMA tile GEMM and NHWC implicit-GEMM convolution for gfx950.
 //
 //   C[M,N] (+)= A[M,K] . B[K,N]   bf16 in, fp32 accumulate, bf16/fp32 out
 //
-// One kernel template, four operand "sources":
+// One kernel template (gemm_bf16_kernel) over five operand "sources", an epilogue kind and an on-load kind:
 //   KMajor   : operand stored row-major with K contiguous   (activations x[m][k], weights w[n][k])
-//   MNMajor  : operand stored with M (or N) contiguous      (dY^T in wgrad, w[k][n] in dgrad)
-//   ConvA    : implicit im2col of an NHWC input, K = (r, s, c), K contiguous per (r, s)
+//   MNMajorK : operand stored with M (or N) contiguous      (dY^T in wgrad, w[k][n] in dgrad); K tails read zeros
+//   ConvA    : implicit im2col of an NHWC input, K = (r, s, c), K contiguous per (r, s), C % 64 == 0
+//   ConvAG   : the same for any C % 8 == 0 (the stem), every 16-B unit decoding its own (r, s, c)
 //   ConvWgB  : implicit im2col used as the N-major B operand of the weight-gradient GEMM
+//   TileEpi / OnLoad : what leaves the accumulators, and BatchNorm + ReLU applied to A or B on its way into LDS (the
+//              table above the enums); the host side's choose_tile_form picks them, one launch() runs every entry point
 //
 // Design (MI355X_MICROARCH / cdna_hip_programming guide):
-//  * 128x128 block tile, BK = 64, 256 threads = 4 waves (2x2), each wave 64x64 = 4x4
+//  * 128x128 block tile (256x64: N <= 64, K-major operands), BK = 64, 256 threads = 4 waves, each wave 64x64 = 4x4
 //    v_mfma_f32_16x16x32_bf16 tiles (64 accumulator VGPRs).
 //  * global -> LDS with 16-byte global_load_lds (no VGPR round trip); the LDS image is
 //    lane-linear, so bank-conflict swizzles are applied to the per-lane SOURCE address and
@@ -19,14 +22,14 @@
 //      MN-major  [64 k][128 mn]    : 16-B unit u of k-row r stored at u ^ h(r),
 //                                    h(r) = 2 * ((r & 3) | ((r >> 3 & 1) << 2))
 //                                    -> conflict-free ds_read_b64_tr_b16 transposed reads
-//  * double-buffered LDS (2 x 32 KB), next tile's loads issued before the current tile's MFMAs.
+//  * double-buffered LDS (2 x 32 KB), next tile's loads issued before the current tile's MFMAs (one buffer: short K).
 //  * operands swapped in the MFMA (B tile as the "A" operand) so each lane ends with 4
-//    CONSECUTIVE output columns: 8-byte bf16 / 16-byte fp32 stores in the epilogue.
+//    CONSECUTIVE output columns: 8-byte bf16 / 16-byte fp32 stores in the General epilogue.
 //  * XCD-aware, bijective block remap + grouped tile order so blocks sharing an A or B panel
 //    run on the same XCD (private L2).
-//  * epilogue: bias, ReLU / GELU(tanh), pre-activation side output, fp32 accumulate, split-K
-//    fp32 atomics (for the tall-K weight gradients).
+//  * split-K (the tall-K weight gradients): each split stores a private fp32 slab (mode 3), splitk_reduce combines.
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 #include <type_traits>
 
@@ -103,26 +106,6 @@ struct KMajor {
   // channel of K index k0 (a 1x1 convolution's activation: K is the channel)
   __device__ __forceinline__ int chan0(int k0) const { return k0; }
   static constexpr bool kmajor = true;
-};
-
-struct MNMajor {
-  const uint16_t* p;
-  long ld;   // elements between k rows
-  int cols;  // valid M (or N) extent; must be a multiple of 8
-  __device__ __forceinline__ const void* src(int s, int c0, int k0) const {
-    const int krow = s >> 4, up = s & 15;
-    const int u = up ^ mn_swz(krow);
-    int col = c0 + u * 8;
-    col = col < cols ? col : cols - 8;
-    return p + (long)(k0 + krow) * ld + col;
-  }
-  // no hoisted cursor: every tile re-derives the address from the slot index
-  struct Cursor { int s, base; };
-  __device__ __forceinline__ Cursor cursor(int s, int base) const { return Cursor{s, base}; }
-  __device__ __forceinline__ const void* at(const Cursor& c, int k0) const { return src(c.s, c.base, k0); }
-  // per-K-step uniform part of the address (identity here; see ConvA)
-  __device__ __forceinline__ int tap(int k0) const { return k0; }
-  static constexpr bool kmajor = false;
 };
 
 // Implicit im2col of NHWC input x[N][H][W][C] for a KRSC weight: row m = (n, ho, wo), k = (r, s, c).
@@ -312,34 +295,57 @@ __device__ __forceinline__ mfma_bf16x8 frag(const char* tile, int b, int kk, int
 }
 
 // ----------------------------------------------------------------------------- epilogue
+// (which fields a kind reads: the table above TileEpi; the hosts set the first seven positionally)
 struct Epi {
-  void* c;           // output (bf16 or fp32)
+  void* c;                      // output (bf16 or fp32)
   long ldc;
-  const float* bias;  // [N] or null
-  uint16_t* pre;      // bf16 pre-activation copy or null
-  int out_f32;        // 1: fp32 output
-  int act;            // 0 none, 1 relu, 2 gelu(tanh)
-  int mode;           // 0 store, 1 accumulate (fp32 C += acc), 2 atomic add (fp32),
-                      // 3 split-K slab: split z stores plain fp32 at c + z * slab (reduced by splitk_reduce)
-  long slab;
-  float alpha;
-  float* stats;       // [STAT_REPL][2][N] fp32 per-column sum / sum of squares of the stored outputs
-                      // (BN fusion) or null; tile row tm adds into replica tm % STAT_REPL so the atomics
-                      // spread over STAT_REPL x 2N addresses instead of contending on 2N
+  const float* bias = nullptr;  // [N] or null
+  uint16_t* pre = nullptr;      // bf16 pre-activation copy or null
+  int out_f32 = 0;              // 1: fp32 output
+  int act = 0;                  // 0 none, 1 relu, 2 gelu(tanh)
+  int mode = 0;                 // 0 store, 1 accumulate (fp32 C += acc), 2 atomic add (fp32),
+                                // 3 split-K slab: split z stores plain fp32 at c + z * slab (reduced by splitk_reduce)
+  long slab = 0;
+  float alpha = 1.f;
+  float* stats = nullptr;  // [STAT_REPL][2][N] fp32 per-column sum / sum of squares of the stored outputs
+                           // (BN fusion) or null; tile row tm adds into replica tm % STAT_REPL so the atomics
+                           // spread over STAT_REPL x 2N addresses instead of contending on 2N
   // Sub-grid output (stride-s data gradient by output parity): GEMM row m = (n, i, j) over an rHo x rWo grid
   // is stored at output row (n, i*rst + ra, j*rst + rb) of an rH x rW image. rst == 0: identity.
-  int rst, rHo, rWo, rH, rW, ra, rb;
-  // accumulate (mode 1, lean epilogue) onto addsrc instead of C's old value, with the elements whose packed bit in
+  int rst = 0, rHo = 0, rWo = 0, rH = 0, rW = 0, ra = 0, rb = 0;
+  // accumulate (mode 1, Lean / LeanBnBwd) onto addsrc instead of C's old value, with the elements whose packed bit in
   // addmask is clear taken as zero: C = acc + (bit ? addsrc : 0). A ResNet identity block's input gradient is
   // conv1's dgrad plus the block output's gradient masked by its ReLU -- read here from dy and the forward's
-  // 1-bit mask instead of from a materialised residual gradient.
-  const uint16_t* addsrc;
-  const uint8_t* addmask;
-  // BST instantiation (lean fast path, identity rows, ldc == N): the BatchNorm-backward sums of the stored output
-  // for the relu(BN(x)) that produced this data gradient's input (launchers.h BnBwdSums), into bb.sums
+  // 1-bit mask instead of from a materialised residual gradient. (LeanInfer: addsrc is the residual.)
+  const uint16_t* addsrc = nullptr;
+  const uint8_t* addmask = nullptr;
+  // LeanBnBwd: the BatchNorm-backward sums of the stored output for the relu(BN(x)) that produced this data
+  // gradient's input (launchers.h BnBwdSums), into bb.sums
   BnBwdSums bb;
 };
 constexpr int STAT_REPL = 32;
+
+// The kernel's forms: what leaves the accumulators (TileEpi) and which operand is transformed on its way into LDS
+// (OnLoad). choose_tile_form (host side) says which form a launch takes; the kernel's static_asserts hold the pairs
+// that exist. Every kind reads c ldc alpha and mode; rst* = the sub-grid fields.
+//   kind        computes                                                       also reads          modes
+//   General     per-lane stores, bf16 or fp32, every option a run-time branch  bias pre out_f32    0 1 2 3
+//                                                                              act slab stats rst*
+//   F32Rows     fp32 C = alpha acc (+ C) through LDS as whole 256-B row        slab                0 1 3
+//               segments (weight gradients, their split-K slabs); 2 x 2 tile;
+//               ldc or N % 4 != 0: the General body
+//   Lean        bf16 C through LDS in 16-B row chunks (+ C, or + the masked    stats rst* addsrc   0 1
+//               addsrc); column statistics (convolutions, data gradients)      addmask
+//   LeanLinear  Lean's staging with bias, pre-activation copy, ReLU / GELU     bias pre act        0
+//               (the transformer linears); identity rows, no statistics
+//   LeanBnBwd   Lean with a BatchNorm's backward sums of the stored gradient   rst* addsrc addmask 0, 1 (mask
+//               for the statistics; identity rows (ldc == N) or sub-grid; 2x2  bb                  kind)
+//   LeanInfer   bf16 C = act(bf16(acc scale + shift) + residual), ldc == N     bias (shift) addsrc 0
+//               (a convolution with its folded BatchNorm); identity rows       act; XForm::p
+//   OnLoad::A (K-major A, Lean), OnLoad::B (MN-major B, F32Rows): the operand is a BatchNorm's raw input and the
+//   GEMM consumes relu(fma(x, scale, shift)); reads XForm p C fC
+enum class TileEpi { General, F32Rows, Lean, LeanLinear, LeanBnBwd, LeanInfer };
+enum class OnLoad { None, A, B };
 
 // GELU(tanh) as x * sigmoid(2u), u = k0 (x + k1 x^3): sigmoid(2u) = (1 + tanh u) / 2 = 1 / (1 + 2^(-2u log2 e)),
 // one v_exp_f32 + one v_rcp_f32 (both ~1 ulp) instead of tanhf's polynomial. The epilogue runs it serially per
@@ -348,6 +354,42 @@ __device__ __forceinline__ float gelu_tanh(float x) {
   const float k0 = 0.7978845608028654f, k1 = 0.044715f;
   const float u = k0 * (x + k1 * x * x * x);
   return x * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-2.8853900817779268f * u));
+}
+
+// the sub-grid output row of GEMM row m (Epi::rst != 0)
+__device__ __forceinline__ long subgrid_row(const Epi E, int m) {
+  const int hw = E.rHo * E.rWo;
+  const int nimg = m / hw, rem = m - nimg * hw;
+  const int ii = rem / E.rWo, jj = rem - ii * E.rWo;
+  return ((long)nimg * E.rH + ii * E.rst + E.ra) * E.rW + jj * E.rst + E.rb;
+}
+
+// Column sums of the Lean copy-outs' per-thread partials (thread t: NV vectors a [, b] over the 8 columns of chunk
+// t % CPR): partials [GEMM_THREADS][16] in LDS, then thread (which, col) sums the GEMM_THREADS / CPR partials of its
+// column: one atomic per (column, vector) per block, vector `which` into out[which * N + n]
+template <int BN, int NV>
+__device__ __forceinline__ void colsum_reduce(char* smem, const float (&a)[8], const float (&b)[8], float* out, int tid,
+                                              int n0, int N) {
+  constexpr int CPR = BN / 8;
+  __syncthreads();
+  float* part = reinterpret_cast<float*>(smem);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    part[tid * 16 + r] = a[r];
+    if constexpr (NV == 2) part[tid * 16 + 8 + r] = b[r];
+  }
+  __syncthreads();
+  if (tid < NV * BN) {
+    const int col = tid % BN, which = NV == 1 ? 0 : tid / BN;
+    const int n = n0 + col;
+    if (n < N) {
+      const int c = col >> 3, r = col & 7;
+      float v = 0.f;
+#pragma unroll 4
+      for (int t = c; t < GEMM_THREADS; t += CPR) v += part[t * 16 + which * 8 + r];
+      atomicAdd(out + (long)which * N + n, v);
+    }
+  }
 }
 
 // ----------------------------------------------------------------------------- the kernel
@@ -359,34 +401,38 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 // WM x WN waves (WM * WN = 4), each owning a 64 x 64 piece: 128 x 128 tiles (2 x 2) in general, 256 x 64
 // (4 x 1) when N = 64 (the early ResNet convolutions and the stem) so no MFMA work is spent on padding.
 // Only K-major sources may sit on a 64-wide side (the MN-major swizzle assumes 256-B rows).
-// LEAN: the staged bf16 epilogue (also the only one with the BN-statistics reduction).
+// EPI, XF: the form (the table above TileEpi; the static_asserts below hold the pairs that exist), each its own
+// instantiation. The Lean kinds are the staged bf16 epilogues (the only ones with the column-sum reduction).
 // (Rounds 2-3 also had a BatchNorm-BACKWARD statistics epilogue for the data gradients, the BN input tile DMA'd
 // into LDS beside the operands; it measured a net loss on ResNet-50 both rounds and was removed -- ops/conv.py.)
-// XEPI (lean only): bias / ReLU / GELU / pre-activation copy in the staged epilogue (the transformer linears'
-// forward); its own instantiation so the convolutions' lean kernels stay as small as before (the extra epilogue
-// code compiled into every lean kernel cost ResNet-50 1.1 %, measured new/old/new/old on one box).
-// F32S (general epilogue only): fp32 outputs without bias / activation / statistics / row remap -- the weight
-// gradients and their split-K slabs -- go through LDS and leave as whole 256-B row segments; its own instantiation
-// for the weight-gradient operand pairs.
-// XF (normalize on load, see XForm): 1 = the A operand (K-major: a convolution's activation), 2 = the B operand
-// (MN-major: a weight gradient's im2col / activation operand) is loaded through VGPRs, transformed and written to
-// its LDS slot by ds_write instead of by LDS-DMA (same lane-linear image, same swizzle). The staging registers of
-// the next K step are filled behind this step's MFMAs and written after them, before the step's barrier.
-// BST (lean only): the BatchNorm-backward sums epilogue of a data gradient (Epi::bb) instead of the statistics.
-// IEPI (lean only, XF == 0): the inference epilogue of a convolution followed by a folded BatchNorm -- a per-column
-// fp32 affine (scale = XForm::p, shift = Epi::bias, both [N]) in the register pass, one rounding into the staged
-// tile; the copy-out adds an optional bf16 residual (Epi::addsrc, the output's layout, ldc == N) and applies the
-// ReLU (Epi::act). Identity rows, plain stores, no statistics; its own instantiation, as XEPI.
-template <class ASrc, class BSrc, int NBUF, int WM = 2, int WN = 2, bool LEAN = false, bool XEPI = false,
-          bool F32S = false, int XF = 0, bool BST = false, bool IEPI = false>
-__global__ void __launch_bounds__(GEMM_THREADS, (NBUF == 1 && (XF == 0 || (XF == 1 && WM == 2))) ? 3 : 2)
+// LeanLinear and LeanInfer apart from Lean so the convolutions' lean kernels stay as small as before (the extra
+// epilogue code compiled into every lean kernel cost ResNet-50 1.1 %, measured new/old/new/old on one box).
+// OnLoad A / B: that operand is loaded through VGPRs, transformed and written to its LDS slot by ds_write instead of by
+// LDS-DMA (same lane-linear image, same swizzle). The staging registers of the next K step are filled behind this
+// step's MFMAs and written after them, before the step's barrier.
+// LeanInfer: the column affine runs in the register pass, one rounding into the staged tile; the copy-out adds the
+// residual and applies the ReLU.
+template <class ASrc, class BSrc, int NBUF, int WM, int WN, TileEpi EPI, OnLoad XF>
+__global__ void __launch_bounds__(GEMM_THREADS,
+                                  (NBUF == 1 && (XF == OnLoad::None || (XF == OnLoad::A && WM == 2))) ? 3 : 2)
 gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XForm X) {
   constexpr int BM = 64 * WM, BN = 64 * WN;
   constexpr int TA = BM * BK * 2, TB = BN * BK * 2;  // operand tile bytes
+  // ---- the forms that exist
   static_assert(WM * WN == 4, "4 waves");
   static_assert((WM == 2 || ASrc::kmajor) && (WN == 2 || BSrc::kmajor), "MN-major operands need a 128 side");
   static_assert(BM * BN * 2 <= TA + TB, "the C tile fits one operand buffer");
-  static_assert(!IEPI || (LEAN && !XEPI && !BST && XF == 0), "the inference epilogue is a plain lean instantiation");
+  static_assert(XF == OnLoad::None || (XF == OnLoad::A && EPI == TileEpi::Lean) ||
+                    (XF == OnLoad::B && EPI == TileEpi::F32Rows),
+                "normalize on load: A with Lean (the convolution forward), B with F32Rows (the weight gradients)");
+  static_assert(XF != OnLoad::A || ASrc::kmajor, "OnLoad::A transforms a K-major A");
+  static_assert(XF != OnLoad::B || !BSrc::kmajor, "OnLoad::B transforms an MN-major B");
+  static_assert((EPI != TileEpi::F32Rows && EPI != TileEpi::LeanBnBwd) || (WM == 2 && WN == 2),
+                "F32Rows and LeanBnBwd are written for the 2 x 2 tile");
+  // the epilogue body's short names for the kinds
+  constexpr bool LEAN = EPI != TileEpi::General && EPI != TileEpi::F32Rows;
+  constexpr bool XEPI = EPI == TileEpi::LeanLinear, F32S = EPI == TileEpi::F32Rows, BST = EPI == TileEpi::LeanBnBwd,
+                 IEPI = EPI == TileEpi::LeanInfer;
   __shared__ __attribute__((aligned(1024))) char smem[NBUF * (TA + TB)];  // [buf][A|B]
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
@@ -457,8 +503,6 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
 #pragma unroll
     for (int rd = 0; rd < RB; ++rd) cb[rd] = B.cursor(rd * GEMM_THREADS + tid, n0);
   }
-  static_assert(XF == 0 || (XF == 1 && ASrc::kmajor) || (XF == 2 && !BSrc::kmajor),
-                "normalize-on-load: K-major A or MN-major B");
   // LDS-DMA staging of the operands that are not transformed
   auto stage = [&](int buf, int k0) {
     char* ta = smem + buf * (TA + TB);
@@ -466,21 +510,21 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
     if constexpr (HOIST) {
       const auto tpa = A.tap(k0);
       const auto tpb = B.tap(k0);
-      if constexpr (XF != 1) {
+      if constexpr (XF != OnLoad::A) {
 #pragma unroll
         for (int rd = 0; rd < RA; ++rd) glds16(A.at(ca[rd], tpa), ta + (rd * GEMM_THREADS + wid_u * 64) * 16);
       }
-      if constexpr (XF != 2) {
+      if constexpr (XF != OnLoad::B) {
 #pragma unroll
         for (int rd = 0; rd < RB; ++rd) glds16(B.at(cb[rd], tpb), tb + (rd * GEMM_THREADS + wid_u * 64) * 16);
       }
     } else {
-      if constexpr (XF != 1) {
+      if constexpr (XF != OnLoad::A) {
 #pragma unroll
         for (int rd = 0; rd < RA; ++rd)
           glds16(A.src(rd * GEMM_THREADS + tid, m0, k0), ta + (rd * GEMM_THREADS + wid_u * 64) * 16);
       }
-      if constexpr (XF != 2) {
+      if constexpr (XF != OnLoad::B) {
 #pragma unroll
         for (int rd = 0; rd < RB; ++rd)
           glds16(B.src(rd * GEMM_THREADS + tid, n0, k0), tb + (rd * GEMM_THREADS + wid_u * 64) * 16);
@@ -488,20 +532,20 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
     }
   };
   // ---- normalize on load: the transformed operand goes global -> VGPR (xload) -> transform -> LDS (xstore)
-  constexpr int RX = XF == 1 ? RA : (XF == 2 ? RB : 1);
+  constexpr int RX = XF == OnLoad::A ? RA : (XF == OnLoad::B ? RB : 1);
   bf16x8_t xr[RX];
   bool xok[RX];
   float xsc[8], xsh[8];
   // a thread's 16-B slots all cover the same 8 channels: K-major chunk (tid & 7) ^ ((tid >> 4) & 7) of the K step
   // (A), or MN-major unit (tid & 15) ^ mn_swz(tid >> 4) of the tile's columns (B) -- fixed for the whole kernel
-  if constexpr (XF == 2) {
+  if constexpr (XF == OnLoad::B) {
     const int col = n0 + (((tid & 15) ^ mn_swz(tid >> 4)) << 3);
     const int ch = col < N ? col - X.fC.div(col) * X.C : 0;
     load_f8g(X.p + ch, xsc);
     load_f8g(X.p + X.C + ch, xsh);
   }
   auto xload = [&](int k0) {
-    if constexpr (XF == 1) {
+    if constexpr (XF == OnLoad::A) {
       const int ch = A.chan0(k0) + (((tid & 7) ^ ((tid >> 4) & 7)) << 3);
       load_f8g(X.p + ch, xsc);
       load_f8g(X.p + X.C + ch, xsh);
@@ -521,7 +565,7 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
           xr[rd] = *reinterpret_cast<const bf16x8_t*>(q);
         }
       }
-    } else if constexpr (XF == 2) {
+    } else if constexpr (XF == OnLoad::B) {
       if constexpr (HOIST) {
         const auto tpb = B.tap(k0);
 #pragma unroll
@@ -541,8 +585,8 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
     }
   };
   auto xstore = [&](int buf) {
-    if constexpr (XF != 0) {
-      char* t = smem + buf * (TA + TB) + (XF == 1 ? 0 : TA);
+    if constexpr (XF != OnLoad::None) {
+      char* t = smem + buf * (TA + TB) + (XF == OnLoad::A ? 0 : TA);
 #pragma unroll
       for (int rd = 0; rd < RX; ++rd)
         *reinterpret_cast<bf16x8_t*>(t + (rd * GEMM_THREADS + tid) * 16) = bn_relu8(xr[rd], xsc, xsh, xok[rd]);
@@ -568,6 +612,8 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
         __syncthreads();
       }
     } else if (t + 1 < nt) {
+      // (Issuing the next K step's loads behind the first MFMA half sped up the isolated 56x56 / 28x28 3x3
+      // convolutions 7-12 % but cost the ResNet-50 step 1.5 % at any K threshold -- round 2's A/B; removed.)
       stage(cur ^ 1, kbeg + (t + 1) * BK);
       xload(kbeg + (t + 1) * BK);
     }
@@ -613,7 +659,7 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
     }
     // bias (fp32, added before the one bf16 rounding of the staged value): this lane's 4 columns of each j
     float bj[4][4];
-    float sj[IEPI ? 4 : 1][4];  // IEPI: the columns' scale (bj holds their shift)
+    float sj[IEPI ? 4 : 1][4];  // LeanInfer: the columns' scale (bj holds their shift)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int n = n0 + wn * 64 + j * 16 + (lane >> 4) * 4;
@@ -838,12 +884,7 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
       const int m = m0 + row, n = n0 + c * 8;
       if (m >= M || n >= N) continue;
       long orow = m;
-      if (E.rst) {
-        const int hw = E.rHo * E.rWo;
-        const int nimg = m / hw, rem = m - nimg * hw;
-        const int ii = rem / E.rWo, jj = rem - ii * E.rWo;
-        orow = ((long)nimg * E.rH + ii * E.rst + E.ra) * E.rW + jj * E.rst + E.rb;
-      }
+      if (E.rst) orow = subgrid_row(E, m);
       bf16x8_t o = *reinterpret_cast<const bf16x8_t*>(ctile + row * BN + ((c ^ (row % CPR)) << 3));
       uint16_t* cp = reinterpret_cast<uint16_t*>(ec) + orow * E.ldc + n;
       if constexpr (XEPI) {
@@ -903,49 +944,15 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
     }
     }
     if (stat_out) {
-      // partials [GEMM_THREADS][16] in LDS, then thread (which, col) sums the GEMM_THREADS / CPR partials of its
-      // column: one atomic per (column, sum | sum of squares) per block
-      __syncthreads();
-      float* part = reinterpret_cast<float*>(smem);
-#pragma unroll
-      for (int r = 0; r < 8; ++r) {
-        part[tid * 16 + r] = ps[r];
-        part[tid * 16 + 8 + r] = pq[r];
-      }
-      __syncthreads();
-      if (tid < 2 * BN) {
-        const int col = tid % BN, which = tid / BN;
-        const int n = n0 + col;
-        if (n < N) {
-          const int c = col >> 3, r = col & 7;
-          float v = 0.f;
-#pragma unroll 4
-          for (int t = c; t < GEMM_THREADS; t += CPR) v += part[t * 16 + which * 8 + r];
-          atomicAdd(stat_out + (long)(tm % STAT_REPL) * 2 * N + (long)which * N + n, v);
-        }
-      }
+      colsum_reduce<BN, 2>(smem, ps, pq, stat_out + (long)(tm % STAT_REPL) * 2 * N, tid, n0, N);
       if constexpr (BST) {
-        if (E.bb.x2) {  // the second BatchNorm's sum g (x2 - mean2) into sums2[.][1] (its sum g is the first's)
-          __syncthreads();
-#pragma unroll
-          for (int r = 0; r < 8; ++r) part[tid * 16 + r] = pq2[r];
-          __syncthreads();
-          if (tid < BN) {
-            const int n = n0 + tid;
-            if (n < N) {
-              const int c = tid >> 3, r = tid & 7;
-              float v = 0.f;
-#pragma unroll 4
-              for (int t = c; t < GEMM_THREADS; t += CPR) v += part[t * 16 + r];
-              atomicAdd(E.bb.sums2 + (long)(tm % STAT_REPL) * 2 * N + N + n, v);
-            }
-          }
-        }
+        // the second BatchNorm's sum g (x2 - mean2) into sums2[.][1] (its sum g is the first's)
+        if (E.bb.x2) colsum_reduce<BN, 1>(smem, pq2, pq2, E.bb.sums2 + (long)(tm % STAT_REPL) * 2 * N + N, tid, n0, N);
       }
     }
     return;
   } else {
-    if constexpr (F32S && WM == 2 && WN == 2) {
+    if constexpr (F32S) {
       if (E.out_f32 && emode != 2 && !E.bias && !E.pre && E.act == 0 && !E.stats && !E.rst && (E.ldc & 3) == 0 &&
           (N & 3) == 0) {
         __syncthreads();  // every wave is past its last K-loop LDS read
@@ -991,12 +998,7 @@ gemm_bf16_kernel(ASrc A, BSrc B, Epi E, int M, int N, int K, int k_per_split, XF
       const int m = m0 + wm * 64 + i * 16 + (lane & 15);
       if (m >= M) continue;
       long orow = m;
-      if (E.rst) {
-        const int hw = E.rHo * E.rWo;
-        const int nimg = m / hw, rem = m - nimg * hw;
-        const int ii = rem / E.rWo, jj = rem - ii * E.rWo;
-        orow = ((long)nimg * E.rH + ii * E.rst + E.ra) * E.rW + jj * E.rst + E.rb;
-      }
+      if (E.rst) orow = subgrid_row(E, m);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int n = n0 + wn * 64 + j * 16 + (lane >> 4) * 4;
@@ -1123,135 +1125,160 @@ static int effective_splits(int K, int splits) {
   return (K + kps - 1) / kps;
 }
 
-template <class ASrc, class BSrc, int WM, int WN, bool LEAN, bool XEPI = false, bool F32S = false, int XF = 0,
-          bool BST = false, bool IEPI = false>
-static void launch_tiles2(const ASrc& a, const BSrc& b, const Epi& e, int M, int N, int K, int kps, int splits,
-                          hipStream_t st, const XForm& x = XForm{nullptr, 0, FastDiv{}}) {
-  const int tiles = ((M + 64 * WM - 1) / (64 * WM)) * ((N + 64 * WN - 1) / (64 * WN));
-  if (kps <= single_buf_maxk())
-    hipLaunchKernelGGL((gemm_bf16_kernel<ASrc, BSrc, 1, WM, WN, LEAN, XEPI, F32S, XF, BST, IEPI>), dim3(tiles, 1, splits),
-                       dim3(GEMM_THREADS), 0, st, a, b, e, M, N, K, kps, x);
-  else
-    hipLaunchKernelGGL((gemm_bf16_kernel<ASrc, BSrc, 2, WM, WN, LEAN, XEPI, F32S, XF, BST, IEPI>), dim3(tiles, 1, splits),
-                       dim3(GEMM_THREADS), 0, st, a, b, e, M, N, K, kps, x);
+// ---- which form a launch takes: the legal (operand pair, kind) rows, one predicate per kind, one chooser
+enum class Pair { KK, KM, MK, MM, ConvK, ConvGK, MWg };  // the (A, B) operand sources the hosts launch
+template <class A, class B> struct PairOf;
+template <> struct PairOf<KMajor, KMajor> { static constexpr Pair v = Pair::KK; };      // linear forward, 1x1 convolution
+template <> struct PairOf<KMajor, MNMajorK> { static constexpr Pair v = Pair::KM; };    // data gradient
+template <> struct PairOf<MNMajorK, KMajor> { static constexpr Pair v = Pair::MK; };
+template <> struct PairOf<MNMajorK, MNMajorK> { static constexpr Pair v = Pair::MM; };  // dense weight gradient
+template <> struct PairOf<ConvA, KMajor> { static constexpr Pair v = Pair::ConvK; };    // convolution, C % 64 == 0
+template <> struct PairOf<ConvAG, KMajor> { static constexpr Pair v = Pair::ConvGK; };  // convolution, any C % 8 == 0
+template <> struct PairOf<MNMajorK, ConvWgB> { static constexpr Pair v = Pair::MWg; };  // convolution weight gradient
+
+constexpr unsigned kbit(TileEpi k) { return 1u << (int)k; }
+constexpr unsigned kG = kbit(TileEpi::General), kF = kbit(TileEpi::F32Rows), kL = kbit(TileEpi::Lean),
+                   kX = kbit(TileEpi::LeanLinear), kS = kbit(TileEpi::LeanBnBwd), kI = kbit(TileEpi::LeanInfer);
+// Per pair: whether N <= 64 takes 256 x 64 tiles, the kinds it has, and the operand it can normalize on load (A with
+// Lean, B with F32Rows): the kernel's instantiations (x 1 / 2 buffers). F32Rows and LeanBnBwd: 2 x 2 tile only.
+struct PairForms { bool t41; unsigned kinds; OnLoad on; };
+constexpr PairForms kPairForms[] = {
+    /* KK     */ {true, kG | kL | kX | kS | kI, OnLoad::A},
+    /* KM     */ {false, kG | kL | kS, OnLoad::None},
+    /* MK     */ {false, kG | kL, OnLoad::None},
+    /* MM     */ {false, kG | kL | kF, OnLoad::B},
+    /* ConvK  */ {true, kG | kL | kS | kI, OnLoad::A},
+    /* ConvGK */ {true, kG | kL | kI, OnLoad::None},
+    /* MWg    */ {false, kG | kF, OnLoad::B},
+};
+constexpr bool tile_form_legal(Pair p, int wm, TileEpi k, OnLoad l) {
+  const PairForms& r = kPairForms[(int)p];
+  if (wm == 4 ? !r.t41 : wm != 2) return false;
+  if (l != OnLoad::None) return l == r.on && k == (l == OnLoad::A ? TileEpi::Lean : TileEpi::F32Rows);
+  if (wm == 4 && (k == TileEpi::F32Rows || k == TileEpi::LeanBnBwd)) return false;
+  return (r.kinds & kbit(k)) != 0;
 }
 
-// the lean epilogue applies: bf16 C (16-B aligned rows), store or accumulate, no atomics; bias / ReLU / GELU /
-// pre-activation copy in store mode on identity rows without statistics (the transformer linears: measured on
-// BERT-base's QKV / FFN1 forward 81 / 105 us per call through the general per-lane epilogue)
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static bool epi_extra(const Epi& e) { return e.bias || e.pre || e.act != 0; }
-static bool lean_epi(const Epi& e, int N, bool allow_extra) {
-  if (epi_extra(e) && (!allow_extra || e.mode != 0 || e.rst || e.stats || e.addsrc ||
-                       (reinterpret_cast<uintptr_t>(e.pre) & 15) != 0))
-    return false;
-  return !e.out_f32 && (e.mode == 0 || e.mode == 1) && (e.ldc & 7) == 0 && (N & 7) == 0 &&
-         (reinterpret_cast<uintptr_t>(e.c) & 15) == 0;
+// what every Lean* kind needs: bf16 C (16-B aligned rows), store or accumulate, no atomics
+static bool lean_out(const Epi& e, int N) {
+  return !e.out_f32 && (e.mode == 0 || e.mode == 1) && (e.ldc & 7) == 0 && (N & 7) == 0 && aligned16(e.c);
+}
+// a form's whole gate over the Epi fields: whether kind k (operand l transformed on load) can run this Epi
+static bool tile_epi_takes(TileEpi k, OnLoad l, Pair p, const Epi& e, int N, int splits) {
+  switch (k) {
+    case TileEpi::General:
+    case TileEpi::LeanInfer:  // (launch_conv_infer checks its own arguments)
+      return true;
+    case TileEpi::F32Rows:
+      return e.out_f32 && e.mode != 2 && !epi_extra(e) && !e.stats && !e.rst;
+    case TileEpi::Lean:  // normalize on load: the convolution forward (identity rows, no separate addend)
+      return lean_out(e, N) && !epi_extra(e) && (l == OnLoad::None || (!e.rst && !e.addsrc));
+    case TileEpi::LeanLinear:
+      // bias / ReLU / GELU / pre-activation copy in store mode on identity rows without statistics (the transformer
+      // linears: measured on BERT-base's QKV / FFN1 forward 81 / 105 us per call through the General epilogue)
+      return lean_out(e, N) && epi_extra(e) && e.mode == 0 && !e.rst && !e.stats && !e.addsrc && aligned16(e.pre);
+    case TileEpi::LeanBnBwd:
+      if (!lean_out(e, N) || epi_extra(e) || e.stats || splits != 1) return false;
+      // identity rows: a data gradient (K-major dy, MN-major w), stored, or accumulated for a mask-kind BatchNorm
+      if (!e.rst) return p == Pair::KM && (e.mode == 0 || e.bb.mask) && (!e.addmask || e.addsrc) && e.ldc == N;
+      // sub-grid rows: a 1x1 parity accumulating a residual BatchNorm's correction (mask kind), or a parity of a
+      // stride-2 convolution's data gradient storing with a BatchNorm + ReLU's sums (relu kind; the 1x1 parity on the
+      // K-major source, the others on the implicit GEMM)
+      return p != Pair::KM && !e.addsrc && !e.addmask && (e.bb.mask ? e.mode == 1 && p == Pair::KK : e.mode == 0);
+  }
+  return false;
 }
 
-template <class ASrc, class BSrc, int WM, int WN>
-static void launch_tiles(const ASrc& a, const BSrc& b, const Epi& e, int M, int N, int K, int kps, int splits,
-                         hipStream_t st, const XForm* xf = nullptr) {
-  // normalize-on-load instantiations: the convolution forward (A = the BN input, lean epilogue with statistics) and
-  // the weight gradients (B = the BN input, fp32 output or split-K slab through the F32S epilogue)
-  if (xf) {
-    if constexpr ((std::is_same_v<ASrc, ConvA> || std::is_same_v<ASrc, KMajor>) && std::is_same_v<BSrc, KMajor>) {
-      if (lean_epi(e, N, false) && !e.rst && !e.addsrc) {
-        launch_tiles2<ASrc, BSrc, WM, WN, true, false, false, 1>(a, b, e, M, N, K, kps, splits, st, *xf);
-        return;
-      }
-    }
-    if constexpr (std::is_same_v<ASrc, MNMajorK> && (std::is_same_v<BSrc, ConvWgB> || std::is_same_v<BSrc, MNMajorK>) &&
-                  WM == 2 && WN == 2) {
-      if (e.out_f32 && e.mode != 2 && !epi_extra(e) && !e.stats && !e.rst) {
-        launch_tiles2<ASrc, BSrc, WM, WN, false, false, true, 2>(a, b, e, M, N, K, kps, splits, st, *xf);
-        return;
-      }
-    }
+struct TileForm { TileEpi epi; OnLoad on; };
+enum class XUse { None, BnRelu, Affine };  // a launch's XForm: none, normalize on load, LeanInfer's column scale
+static TileForm choose_tile_form(Pair p, int wm, const Epi& e, int N, int splits, XUse xu) {
+  auto ok = [&](TileEpi k, OnLoad l) { return tile_form_legal(p, wm, k, l) && tile_epi_takes(k, l, p, e, N, splits); };
+  if (xu == XUse::Affine) {
+    if (ok(TileEpi::LeanInfer, OnLoad::None)) return {TileEpi::LeanInfer, OnLoad::None};
+    throw std::runtime_error("inference epilogue: a convolution's operand pair (K-major weights)");
+  }
+  if (xu == XUse::BnRelu) {  // the convolution forward (A = the BN input) and the weight gradients (B = the BN input)
+    if (ok(TileEpi::Lean, OnLoad::A)) return {TileEpi::Lean, OnLoad::A};
+    if (ok(TileEpi::F32Rows, OnLoad::B)) return {TileEpi::F32Rows, OnLoad::B};
     throw std::runtime_error("normalize-on-load: no instantiation for this operand pair / epilogue");
   }
-  // a data gradient (K-major dy, MN-major w) with the BatchNorm-backward sums of its output
   if (e.bb.sums) {
-    if constexpr (std::is_same_v<ASrc, KMajor> && std::is_same_v<BSrc, MNMajorK> && WM == 2 && WN == 2) {
-      if (lean_epi(e, N, false) && (e.mode == 0 || (e.mode == 1 && e.bb.mask)) && !e.stats && !e.rst &&
-          (!e.addmask || e.addsrc) && splits == 1 && e.ldc == N) {
-        launch_tiles2<ASrc, BSrc, WM, WN, true, false, false, 0, true>(a, b, e, M, N, K, kps, splits, st);
-        return;
-      }
-    }
-    // the row-remapped (sub-grid) data gradients: a 1x1 parity accumulating a residual BatchNorm's correction (mask
-    // kind), or a parity of a stride-2 convolution's data gradient storing with a BatchNorm + ReLU's sums (relu kind;
-    // the 1x1 parity on the K-major source, the others on the implicit GEMM)
-    if constexpr ((std::is_same_v<ASrc, KMajor> || std::is_same_v<ASrc, ConvA>) && std::is_same_v<BSrc, KMajor> &&
-                  WM == 2 && WN == 2) {
-      if (lean_epi(e, N, false) && !e.stats && e.rst && !e.addsrc && !e.addmask && splits == 1 &&
-          ((e.mode == 1 && e.bb.mask && std::is_same_v<ASrc, KMajor>) || (e.mode == 0 && !e.bb.mask))) {
-        launch_tiles2<ASrc, BSrc, WM, WN, true, false, false, 0, true>(a, b, e, M, N, K, kps, splits, st);
-        return;
-      }
-    }
+    if (ok(TileEpi::LeanBnBwd, OnLoad::None)) return {TileEpi::LeanBnBwd, OnLoad::None};
     throw std::runtime_error("BatchNorm-backward sums epilogue: a plain bf16 data gradient (K-major dy, MN-major w)");
   }
-  // the linear forward (both operands K-major) is the one pair with a bias / activation epilogue instantiation
-  constexpr bool kXepi = std::is_same_v<ASrc, KMajor> && std::is_same_v<BSrc, KMajor>;
-  if constexpr (kXepi) {
-    if (epi_extra(e) && lean_epi(e, N, true)) {
-      launch_tiles2<ASrc, BSrc, WM, WN, true, true>(a, b, e, M, N, K, kps, splits, st);
-      return;
-    }
-  }
-  if constexpr (!std::is_same_v<BSrc, ConvWgB>) {
-    if (lean_epi(e, N, false)) {
-      launch_tiles2<ASrc, BSrc, WM, WN, true>(a, b, e, M, N, K, kps, splits, st);
-      return;
-    }
-  }
+  for (TileEpi k : {TileEpi::LeanLinear, TileEpi::Lean})
+    if (ok(k, OnLoad::None)) return {k, OnLoad::None};
   if (e.addsrc || e.addmask) throw std::runtime_error("a separate (masked) addend needs the lean epilogue");
-  // weight gradients (both operands MN-major: dense or im2col) with an fp32 output or split-K slab
-  constexpr bool kWgrad = std::is_same_v<ASrc, MNMajorK> &&
-                          (std::is_same_v<BSrc, MNMajorK> || std::is_same_v<BSrc, ConvWgB>);
-  if constexpr (kWgrad && WM == 2 && WN == 2) {
-    if (e.out_f32 && e.mode != 2 && !epi_extra(e) && !e.stats && !e.rst) {
-      launch_tiles2<ASrc, BSrc, WM, WN, false, false, true>(a, b, e, M, N, K, kps, splits, st);
-      return;
-    }
-  }
-  launch_tiles2<ASrc, BSrc, WM, WN, false>(a, b, e, M, N, K, kps, splits, st);
+  if (ok(TileEpi::F32Rows, OnLoad::None)) return {TileEpi::F32Rows, OnLoad::None};
+  return {TileEpi::General, OnLoad::None};
 }
 
+template <TileEpi K> using EpiC = std::integral_constant<TileEpi, K>;
+template <OnLoad L> using OnC = std::integral_constant<OnLoad, L>;
+
+// Every launch of the tile kernel: 256 x 64 tiles when N <= 64 and both operands are K-major (no half-empty 128-wide
+// column tile), the form by choose_tile_form, single- or double-buffered by the K range per block. xf: the BatchNorm
+// of a normalize-on-load launch, or (affine) LeanInfer's scale.
 template <class ASrc, class BSrc>
 static void launch(const ASrc& a, const BSrc& b, const Epi& e, int M, int N, int K, int splits, hipStream_t st,
-                   const XForm* xf = nullptr) {
+                   const XForm* xf = nullptr, bool affine = false) {
+  constexpr Pair P = PairOf<ASrc, BSrc>::v;
   const int kps = ((K + splits - 1) / splits + BK - 1) / BK * BK;
   splits = (K + kps - 1) / kps;
-  if constexpr (ASrc::kmajor && BSrc::kmajor) {
-    if (N <= 64) {  // 256 x 64 tiles: no half-empty 128-wide column tile
-      launch_tiles<ASrc, BSrc, 4, 1>(a, b, e, M, N, K, kps, splits, st, xf);
-      return;
+  const int wm = kPairForms[(int)P].t41 && N <= 64 ? 4 : 2;
+  const TileForm f = choose_tile_form(P, wm, e, N, splits, !xf ? XUse::None : affine ? XUse::Affine : XUse::BnRelu);
+  const XForm x = xf ? *xf : XForm{nullptr, 0, FastDiv{}};
+  const dim3 grid(((M + 64 * wm - 1) / (64 * wm)) * ((N + 256 / wm - 1) / (256 / wm)), 1, splits);
+  auto run = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(GEMM_THREADS), 0, st, a, b, e, M, N, K, kps, x); };
+  auto arm = [&](auto wmc, auto kc, auto lc) {  // instantiated for the pair's legal forms only
+    constexpr int WM = decltype(wmc)::value;
+    constexpr TileEpi EPI = decltype(kc)::value;
+    constexpr OnLoad ON = decltype(lc)::value;
+    if constexpr (tile_form_legal(P, WM, EPI, ON)) {
+      if (wm != WM) return;
+      if (kps <= single_buf_maxk()) run(gemm_bf16_kernel<ASrc, BSrc, 1, WM, 4 / WM, EPI, ON>);
+      else run(gemm_bf16_kernel<ASrc, BSrc, 2, WM, 4 / WM, EPI, ON>);
     }
+  };
+  auto go = [&](auto kc, auto lc) {
+    arm(std::integral_constant<int, 2>{}, kc, lc);
+    arm(std::integral_constant<int, 4>{}, kc, lc);
+  };
+  if (f.on == OnLoad::A) return go(EpiC<TileEpi::Lean>{}, OnC<OnLoad::A>{});
+  if (f.on == OnLoad::B) return go(EpiC<TileEpi::F32Rows>{}, OnC<OnLoad::B>{});
+  switch (f.epi) {
+    case TileEpi::General: return go(EpiC<TileEpi::General>{}, OnC<OnLoad::None>{});
+    case TileEpi::F32Rows: return go(EpiC<TileEpi::F32Rows>{}, OnC<OnLoad::None>{});
+    case TileEpi::Lean: return go(EpiC<TileEpi::Lean>{}, OnC<OnLoad::None>{});
+    case TileEpi::LeanLinear: return go(EpiC<TileEpi::LeanLinear>{}, OnC<OnLoad::None>{});
+    case TileEpi::LeanBnBwd: return go(EpiC<TileEpi::LeanBnBwd>{}, OnC<OnLoad::None>{});
+    case TileEpi::LeanInfer: return go(EpiC<TileEpi::LeanInfer>{}, OnC<OnLoad::None>{});
   }
-  launch_tiles<ASrc, BSrc, 2, 2>(a, b, e, M, N, K, kps, splits, st, xf);
 }
 
-static Epi make_epi(void* c, long ldc, bool out_f32, const float* bias, int act, uint16_t* pre, int mode,
-                    float alpha) {
-  Epi e;
-  e.c = c;
-  e.ldc = ldc;
-  e.bias = bias;
-  e.pre = pre;
-  e.out_f32 = out_f32;
-  e.act = act;
-  e.mode = mode;
-  e.alpha = alpha;
-  e.stats = nullptr;
-  e.slab = 0;
-  e.rst = e.rHo = e.rWo = e.rH = e.rW = e.ra = e.rb = 0;
-  e.addsrc = nullptr;
-  e.addmask = nullptr;
-  e.bb = BnBwdSums{};
-  // (Issuing the next K step's loads behind the first MFMA half sped up the isolated 56x56 / 28x28 3x3 convolutions
-  // 7-12 % but cost the ResNet-50 step 1.5 % at any K threshold -- round 2, scripts/gpurun/bench_ab.sh; removed.)
-  return e;
+// The chooser by plain values, for tests without a GPU (launchers.h TileFormQuery): the pointers an Epi would hold
+// are stand-ins with the asked-for presence and alignment.
+const char* gemm_tile_form(const TileFormQuery& q) {
+  static const char* const kPairs[] = {"KK", "KM", "MK", "MM", "ConvK", "ConvGK", "MWg"};
+  static const char* const kNames[3][6] = {
+      {"General", "F32Rows", "Lean", "LeanLinear", "LeanBnBwd", "LeanInfer"},
+      {"", "", "Lean+A", "", "", ""},
+      {"", "F32Rows+B", "", "", "", ""}};
+  int p = 0;
+  while (p < 7 && std::strcmp(kPairs[p], q.pair) != 0) ++p;
+  if (p == 7 || (q.wm != 2 && q.wm != 4) || q.xuse < 0 || q.xuse > 2)
+    throw std::runtime_error("gemm_tile_form: pair KK / KM / MK / MM / ConvK / ConvGK / MWg, wm 2 or 4, xuse 0-2");
+  alignas(16) static char mem[32];
+  auto ptr = [&](bool has, bool aligned = true) { return has ? (void*)(mem + (aligned ? 0 : 8)) : nullptr; };
+  Epi e{ptr(true, q.c_aligned), q.ldc, (const float*)ptr(q.bias), (uint16_t*)ptr(q.pre, q.pre_aligned), q.out_f32,
+        q.act, q.mode};
+  e.stats = (float*)ptr(q.stats), e.rst = q.rst ? 2 : 0;
+  e.addsrc = (const uint16_t*)ptr(q.addsrc), e.addmask = (const uint8_t*)ptr(q.addmask);
+  e.bb.sums = (float*)ptr(q.bb_sums), e.bb.mask = (const uint8_t*)ptr(q.bb_mask);
+  const TileForm f = choose_tile_form((Pair)p, q.wm, e, q.N, q.splits, (XUse)q.xuse);
+  return kNames[(int)f.on][(int)f.epi];
 }
 
 // Choose split-K for small-MN / tall-K products (weight gradients) with a wave-quantisation cost model:
@@ -1322,7 +1349,8 @@ void launch_gemm(const uint16_t* A, long lda, bool a_kmajor, const uint16_t* B, 
     return;
   }
   const bool slab = splits > 1;
-  Epi e = make_epi(slab ? (void*)ws : C, slab ? (long)N : ldc, c_f32, bias, act, pre, slab ? 3 : mode, alpha);
+  Epi e{slab ? (void*)ws : C, slab ? (long)N : ldc, bias, pre, c_f32, act, slab ? 3 : mode};
+  e.alpha = alpha;
   e.slab = (long)M * N;
   if (add) {
     if (slab || mode != 1) throw std::runtime_error("a separate addend needs accumulate mode and no split-K");
@@ -1345,7 +1373,7 @@ void launch_gemm(const uint16_t* A, long lda, bool a_kmajor, const uint16_t* B, 
 }
 
 // dx[M, N] = dy[M, K] . w[K, N] (bf16, the 1x1 data gradient) on the tile kernel with the BatchNorm-backward sums
-// of dx for the relu(BN(x)) that produced the convolution's input (Epi::bb, BST instantiation).
+// of dx for the relu(BN(x)) that produced the convolution's input (Epi::bb, TileEpi::LeanBnBwd).
 void launch_gemm_dgrad_bnstats(const uint16_t* A, const uint16_t* B, uint16_t* C, int M, int N, int K,
                                const BnBwdSums& bb, hipStream_t st, bool accumulate, const uint16_t* add_src,
                                const uint8_t* add_mask) {
@@ -1356,7 +1384,7 @@ void launch_gemm_dgrad_bnstats(const uint16_t* A, const uint16_t* B, uint16_t* C
     throw std::runtime_error("gemm dgrad BatchNorm-backward sums: x / mean / sums (+ gamma / beta / invstd without a "
                              "mask; accumulate only with one), N % 8 == 0");
   if ((add_src || add_mask) && !accumulate) throw std::runtime_error("gemm dgrad BatchNorm sums: an addend accumulates");
-  Epi e = make_epi(C, N, false, nullptr, 0, nullptr, accumulate ? 1 : 0, 1.f);
+  Epi e{C, N, nullptr, nullptr, 0, 0, accumulate ? 1 : 0};
   e.bb = bb;
   e.addsrc = add_src;  // out = product + (add_mask bit ? add_src : 0) (a ResNet identity block's residual gradient)
   e.addmask = add_mask;
@@ -1384,7 +1412,7 @@ void launch_conv_fwd(const uint16_t* x, const uint16_t* w, void* y, bool y_f32, 
   }
   const int M = N * Ho * Wo, RSC = R * S * C;
   KMajor b{w, (long)RSC, K, RSC};
-  Epi e = make_epi(y, K, y_f32, bias, act, nullptr, mode, 1.f);
+  Epi e{y, K, bias, nullptr, y_f32, act, mode};
   e.stats = stats;
   if (bb) e.bb = *bb;
   if (sg) {
@@ -1440,18 +1468,8 @@ void launch_conv_fwd(const uint16_t* x, const uint16_t* w, void* y, bool y_f32, 
 }
 
 // Inference convolution with the following BatchNorm folded to a per-channel affine, an optional residual and ReLU
-// (the IEPI epilogue): y = act(bf16(conv(x, w) * scale + shift) + res). Every shape runs on the tile kernel: the
+// (TileEpi::LeanInfer): y = act(bf16(conv(x, w) * scale + shift) + res). Every shape runs on the tile kernel: the
 // K-major source for a plain 1x1, the per-tile im2col for C % 64 == 0, the per-unit one for any other C % 8 == 0.
-template <class ASrc>
-static void launch_infer(const ASrc& a, const KMajor& b, const Epi& e, int M, int N, int K, const XForm& x,
-                         hipStream_t st) {
-  const int kps = (K + BK - 1) / BK * BK;
-  if (N <= 64)
-    launch_tiles2<ASrc, KMajor, 4, 1, true, false, false, 0, false, true>(a, b, e, M, N, K, kps, 1, st, x);
-  else
-    launch_tiles2<ASrc, KMajor, 2, 2, true, false, false, 0, false, true>(a, b, e, M, N, K, kps, 1, st, x);
-}
-
 void launch_conv_infer(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int C, int K, int R,
                        int S, int stride, int pad, int Ho, int Wo, const float* scale, const float* shift,
                        const uint16_t* res, bool relu, hipStream_t st) {
@@ -1464,19 +1482,19 @@ void launch_conv_infer(const uint16_t* x, const uint16_t* w, uint16_t* y, int N,
                              "shift, fewer than 2^31 output pixels");
   if (M == 0) return;
   KMajor b{w, RSC, K, (int)RSC};
-  Epi e = make_epi(y, K, false, shift, relu ? 1 : 0, nullptr, 0, 1.f);
+  Epi e{y, K, shift, nullptr, 0, relu ? 1 : 0, 0};
   e.addsrc = res;
   const XForm xs{scale, 0, FastDiv{}};
   if (R == 1 && S == 1 && stride == 1 && pad == 0 && C % 64 == 0) {
-    launch_infer(KMajor{x, (long)C, (int)M}, b, e, (int)M, K, (int)RSC, xs, st);
+    launch(KMajor{x, (long)C, (int)M}, b, e, (int)M, K, (int)RSC, 1, st, &xs, true);
   } else if (C % 64 == 0) {
     ConvA a{x, N, H, W, C, Ho, Wo, S, stride, pad, 1, (int)M,
             make_fastdiv(C), make_fastdiv(S), make_fastdiv(Ho * Wo), make_fastdiv(Wo)};
-    launch_infer(a, b, e, (int)M, K, (int)RSC, xs, st);
+    launch(a, b, e, (int)M, K, (int)RSC, 1, st, &xs, true);
   } else {
     ConvAG a{x, N, H, W, C, Ho, Wo, S, stride, pad, 1, (int)M, (int)RSC,
              make_fastdiv(C), make_fastdiv(S), make_fastdiv(Ho * Wo), make_fastdiv(Wo)};
-    launch_infer(a, b, e, (int)M, K, (int)RSC, xs, st);
+    launch(a, b, e, (int)M, K, (int)RSC, 1, st, &xs, true);
   }
 }
 
@@ -1491,8 +1509,7 @@ void launch_conv_wgrad(const uint16_t* x, const uint16_t* dy, float* dw, int N, 
   splits = effective_splits(M, splits);
   const int RSC = R * S * C;
   const bool slab = splits > 1;
-  Epi e = make_epi(slab ? (void*)ws : (void*)dw, (long)RSC, true, nullptr, 0, nullptr, slab ? 3 : (accumulate ? 1 : 0),
-                   1.f);
+  Epi e{slab ? (void*)ws : (void*)dw, (long)RSC, nullptr, nullptr, 1, 0, slab ? 3 : (accumulate ? 1 : 0)};
   e.slab = (long)K * RSC;
   if (xform) {
     const XForm xf{xform, C, make_fastdiv(C)};

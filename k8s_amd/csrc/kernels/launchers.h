@@ -144,7 +144,7 @@ struct BnBwdSums {
   const float* invstd = nullptr;
   float* sums = nullptr;
   // mask kind (a residual BatchNorm's packed ReLU bits instead of the affine ReLU decision): the row-remapped
-  // accumulating data gradient's correction (gemm.hip BST sub-grid path); gamma / beta / invstd unused
+  // accumulating data gradient's correction (gemm.hip TileEpi::LeanBnBwd, sub-grid rows); gamma / beta / invstd unused
   const uint8_t* mask = nullptr;
   // mask kind, the two-BatchNorm form (a ResNet downsample block's output: bn3 and the downsample BN share g):
   // sums2[.][1] += sum g (x2 - mean2) (identity-row path only)
@@ -167,6 +167,20 @@ void launch_gemm_short(const uint16_t* A, const uint16_t* B, long ldb, bool b_mn
 void launch_gemm_dgrad_bnstats(const uint16_t* A, const uint16_t* B, uint16_t* C, int M, int N, int K,
                                const BnBwdSums& bb, hipStream_t st, bool accumulate = false,
                                const uint16_t* add_src = nullptr, const uint8_t* add_mask = nullptr);
+// Which form of the tile kernel (gemm.hip TileEpi, "+A" / "+B" with an operand normalized on load) a launch described
+// by plain values takes: the chooser every launch goes through, for tests without a GPU. Throws as the launch would.
+struct TileFormQuery {
+  const char* pair = "KK";  // operand sources: KK KM MK MM ConvK ConvGK MWg (gemm.hip Pair)
+  int wm = 2;               // 2: 128 x 128 tiles, 4: 256 x 64
+  int N = 128, splits = 1;
+  int xuse = 0;             // the launch's XForm: 0 none, 1 normalize on load, 2 the inference scale
+  long ldc = 128;
+  int out_f32 = 0, mode = 0, act = 0;
+  // which Epi pointers are set (rst: a sub-grid output), and whether c / pre are 16-B aligned
+  bool bias = false, pre = false, stats = false, rst = false, addsrc = false, addmask = false, bb_sums = false,
+       bb_mask = false, c_aligned = true, pre_aligned = true;
+};
+const char* gemm_tile_form(const TileFormQuery& q);
 void launch_gemm(const uint16_t* A, long lda, bool a_kmajor, const uint16_t* B, long ldb, bool b_kmajor, void* C,
                  long ldc, bool c_f32, int M, int N, int K, const float* bias, int act, uint16_t* pre, int mode,
                  float alpha, int splits, float* ws, hipStream_t st, const AddEpi* add = nullptr,
@@ -252,7 +266,7 @@ void launch_conv_fwd(const uint16_t* x, const uint16_t* w, void* y, bool y_f32, 
                      int R, int S, int stride, int pad, int dil, int Ho, int Wo, const float* bias, int act,
                      int mode, float* stats, hipStream_t st, const SubGrid* sg = nullptr, const float* xform = nullptr,
                      const BnBwdSums* bb = nullptr);
-// Inference convolution + folded BatchNorm (+ residual) (+ ReLU) on the tile kernel (gemm.hip IEPI):
+// Inference convolution + folded BatchNorm (+ residual) (+ ReLU) on the tile kernel (gemm.hip TileEpi::LeanInfer):
 //   y = act(bf16(conv(x, w) * scale[k] + shift[k]) + res), scale / shift fp32 [K], res bf16 with y's layout or null.
 // C % 8 == 0, K % 8 == 0, dilation 1, 16-B aligned pointers; throws outside that contract.
 void launch_conv_infer(const uint16_t* x, const uint16_t* w, uint16_t* y, int N, int H, int W, int C, int K, int R,

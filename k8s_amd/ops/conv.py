@@ -156,7 +156,7 @@ def conv_fwd(x, w, stride, padding, stats=None):
 
 
 def infer_ok(x, w, scale, shift, residual=None) -> bool:
-    """The inference epilogue's contract (gemm.hip IEPI): bf16 GPU operands, C % 8 == 0, K % 8 == 0, contiguous
+    """The inference epilogue's contract (gemm.hip TileEpi::LeanInfer): bf16 GPU operands, C % 8 == 0, K % 8 == 0, contiguous
     16-B aligned tensors, fp32 scale / shift."""
     ts = [x, w] + ([residual] if residual is not None else [])
     return (_hip(*ts) and x.shape[-1] % 8 == 0 and w.shape[0] % 8 == 0
@@ -379,7 +379,7 @@ def _plan_dgrad_strided(gy, w, stride, padding, H, W, addend, bn_link):
     kind = _link_kind(bn_link, (gy.shape[0], H, W, C))
     if bn_link is not None and bn_link.pending:
         # completing a residual BN's backward sums started by the first data gradient into `addend`
-        # (short_entry_pending): the live parity's epilogue adds the changes it makes (gemm.hip BST sub-grid path)
+        # (short_entry_pending): the live parity's epilogue adds the changes it makes (gemm.hip TileEpi::LeanBnBwd, sub-grid rows)
         if (kind is not None and R == 1 and S == 1 and padding == 0 and torch.is_tensor(addend)
                 and addend.is_contiguous() and addend.shape == bn_link.x.shape):
             return "parity_complete_sums"

@@ -684,7 +684,7 @@ def test_conv3x3_dgrad_bnstats_epilogue(cuda, N, H, C, K):
                                    # stream-K tail (1176 tiles: 152 of 256 left; the tail: test_gemm256_gpu.py)
                                    (65536, 1024, 256), (150528, 2048, 512)])
 def test_gemm_dgrad_bnstats_epilogue(cuda, M, K, N):
-    """The 1x1 data gradient on its regular kernel (the tile kernel's BST epilogue, or the 4-wave kernel's copy_out_bnbwd)
+    """The 1x1 data gradient on its regular kernel (the tile kernel's LeanBnBwd epilogue, or the 4-wave kernel's copy_out_bnbwd)
     with the BatchNorm-backward sums of the relu(BN(x)) that fed the convolution: dx bitwise equal to the
     plain dgrad, the sums against fp32 sums over the stored dx with the forward's ReLU decision."""
     C_ = _C()
@@ -713,7 +713,7 @@ def test_gemm_dgrad_bnstats_epilogue(cuda, M, K, N):
 def test_stage_entry_bn_sums_two_dgrads(cuda, N, H, K1, C, K2):
     """A residual BN's backward sums over the sum of two data gradients into its output (a ResNet stage-entry block:
     conv1's 1x1 dgrad, then the downsample's 1x1 / stride-2 dgrad accumulated onto it): the first takes the sums over
-    its values (gemm_short EPI 5), the second adds the changes it makes at its parity (gemm.hip BST sub-grid path).
+    its values (gemm_short EPI 5), the second adds the changes it makes at its parity (gemm.hip LeanBnBwd, sub-grid rows).
     Against fp32 sums over the final tensor with the BN's packed ReLU bits."""
     from k8s_amd.ops import conv as kc
     from k8s_amd.ops import nn as K
@@ -749,7 +749,7 @@ def test_stage_entry_bn_sums_two_dgrads(cuda, N, H, K1, C, K2):
 def test_gemm_dgrad_bnstats_mask_accumulate(cuda):
     """The second of two stride-1 data gradients into the stem pool's output (layer 1's downsample after its conv1):
     the tile kernel accumulates onto the first's gradient and takes the BatchNorm-backward sums (mask kind) over the
-    final tensor in its epilogue (gemm.hip BST fast path; ops.conv._dgrad_hip, BnStatLink pool kind) -- against fp32
+    final tensor in its epilogue (gemm.hip LeanBnBwd, identity rows; ops.conv._dgrad_hip, BnStatLink pool kind) -- against fp32
     sums. Ragged M (not a multiple of the 128-row tile)."""
     from k8s_amd.ops import conv as kc
     from k8s_amd.ops import nn as K
@@ -785,7 +785,7 @@ def test_gemm_dgrad_bnstats_mask_accumulate(cuda):
 def test_gemm_dgrad_bnstats_masked_addend(cuda, M, N, K, dual):
     """A stage-4 identity block's conv1 data gradient (K = 512: not a gemm_short depth) on the tile kernel: out =
     dgrad + (addend bit ? addend : 0) with the residual BatchNorm's backward sums of out in the same epilogue
-    (gemm.hip BST fast path, masked addend), against fp32."""
+    (gemm.hip LeanBnBwd, identity rows, masked addend), against fp32."""
     C_ = _C()
     torch.manual_seed(23)
     gy = torch.randn(M, K, device=cuda).bfloat16()
@@ -814,7 +814,7 @@ def test_gemm_dgrad_bnstats_masked_addend(cuda, M, N, K, dual):
 @pytest.mark.parametrize("N,H,C,K", [(4, 28, 128, 128), (2, 14, 256, 256), (3, 13, 128, 192)])
 def test_strided_dgrad_bn_relu_sums(cuda, monkeypatch, N, H, C, K):
     """A stride-2 3x3 data gradient (ResNet's stage-entry conv2) as its four parities, each storing its own pixels and
-    adding the BatchNorm + ReLU backward sums of the bn1 that fed the convolution (gemm.hip BST sub-grid path, relu
+    adding the BatchNorm + ReLU backward sums of the bn1 that fed the convolution (gemm.hip LeanBnBwd, sub-grid rows, relu
     kind; the 1x1 parity on the K-major source, the others on the implicit GEMM): dx equal to the parity path without
     the sums, the sums against fp32 sums over the stored dx with the forward's ReLU decision. Odd H: ragged parities."""
     from k8s_amd.ops import conv as kc

@@ -248,7 +248,7 @@ def test_resnet50_large_batch_indexing_matches_half_batch(cuda, half):
 
 def test_bn_backward_sums_in_dgrad_epilogue_match_reduction(cuda):
     """BatchNorm-backward sums taken in the data-gradient epilogues (ops.nn.BnStatLink: the residual BNs in the
-    identity-block conv1 dgrad, gemm_short.hip EPI 3 / 4; the on-load bn2 in conv3's tile-kernel dgrad, gemm.hip BST)
+    identity-block conv1 dgrad, gemm_short.hip EPI 3 / 4; the on-load bn2 in conv3's tile-kernel dgrad, gemm.hip LeanBnBwd)
     against the BatchNorms' own reduction sweeps (ops.nn.BN_BSTATS off), whole model, both against the fp32 torch twin:
     the fused path's error may not exceed the separate path's beyond summation-order noise. (Compared through the
     reference, not to each other: in this net -- every BatchNorm gamma in [0.6, 1.4], bn3 included -- an fp32-ulp
